@@ -9,12 +9,21 @@ in HBM: zero_grad, forward (backbone + PPM + POP head + fused upsample/CE + orth
 AdamW step(s).  Workload at every N: BASELINE.json configs[1] per GPU -- PSPNet-POP ResNet-50, bf16, batch 16, 512x512,
 8 logit channels -- so scaling is weak and `value` is the whole-job tiles/s.
 
-The JSON line also carries
-  roofline     : the dominant kernel (picked by an instrumented warm-up pass), timed live with HIP events on the
-                 launch stream during the timed steps; achieved = algorithmic FLOPs of that launch / mean duration,
-                 peak = 2500 TFLOP/s (bf16 dense MFMA, MI355X_MICROARCH.md);
+A plain run sets up, warms up, times the K steps and prints the JSON line (value, ms_per_step and the fields derived
+from the timed steps alone).  With --full the line also carries
+  families, executed_tflops, optimizer_ms_per_step : one instrumented warm-up step, per kernel family;
+  roofline     : the dominant kernel (picked by that instrumented warm-up step), timed live with HIP events on the
+                 launch stream in K more kernel-by-kernel steps after the timed ones; achieved = algorithmic FLOPs of
+                 that launch / mean duration, peak = 2500 TFLOP/s (bf16 dense MFMA, MI355X_MICROARCH.md);
+  other_configs: BASELINE configs 3, 4 and 5, each in a fresh child process -- default workload, N = 1 only;
   cpu_baseline : the CPU oracle (a port: oracle/pop_oracle.py) running the same loop body on config C1 (batch 2,
                  fp32) on this host's cores -- rank 0, N = 1 only.  Reported, not a target.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0), as float32 / float64 .npy files: loss_<key>.npy
+for every entry of the loss dict the step returns, and params_sample.npy / grads_sample.npy / buffers_sample.npy, the
+parameters after the step, their gradients and the floating-point buffers (BatchNorm running statistics), each
+concatenated in named order and, above 2^22 elements, cut to a fixed seeded sample of 2^22 of them.  Same arguments,
+same inputs: two builds can be compared file for file.
 """
 import argparse
 import contextlib
@@ -46,17 +55,21 @@ def parse():
     p.add_argument('--backbone', default=None)
     p.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'])
     p.add_argument('--size', type=int, default=512)
+    p.add_argument('--full', action='store_true', help='also measure what the headline figure does not need: the instrumented warm-up step (families, step floor), the '
+                   'roofline region, the other BASELINE configurations and the CPU baseline (the last two can still be dropped with --no-other-configs / --no-cpu-baseline)')
+    p.add_argument('--dump-outputs', default='', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (losses; seeded samples of the parameters, '
+                   'gradients and buffers after it)')
     p.add_argument('--no-cpu-baseline', action='store_true')
     p.add_argument('--cpu-budget', type=float, default=40.0, help='seconds of CPU work allowed for the cpu_baseline sample')
     p.add_argument('--torch-optimizer', action='store_true', help='torch.optim.AdamW(fused=True) instead of segland_amd.optim.AdamW')
     p.add_argument('--single-step', action='store_true', help='one AdamW step per iteration (the reference does two, train_base.py:262-264)')
     p.add_argument('--no-step-graph', action='store_true', help='issue the timed steps kernel by kernel (default on one GPU: they replay the step as ONE HIP graph, segland_amd/graph_step.py, '
-                   'like train_base does).  Either way a second region of instrumented kernel-by-kernel steps carries the roofline events')
-    p.add_argument('--profile-table', default='', help='write a per-kernel-shape timing table (instrumented extra pass) to this file')
+                   'like train_base does).  Either way --full adds a second region of instrumented kernel-by-kernel steps that carries the roofline events')
+    p.add_argument('--profile-table', default='', help='write a per-kernel-shape timing table (instrumented warm-up step) to this file')
     p.add_argument('--side-config', default='', choices=['', 'c3', 'c4', 'c5'], help='internal: measure ONE of the other BASELINE configurations and print its JSON object (the default N = 1 run '
                    'starts one fresh child process per configuration, so that a fault in a side measurement cannot take the headline line with it)')
     p.add_argument('--no-other-configs', action='store_true', help='skip the short measurements of BASELINE configs 3 (ResNet-101 shard), 4 (fine-tune pair) and 5 (Swin-T shard) '
-                   'that ride on the default N = 1 run (`other_configs` in the JSON line); profiling runs pass this so that the trace holds the headline workload only')
+                   'that ride on the default N = 1 --full run (`other_configs` in the JSON line); profiling runs pass this so that the trace holds the headline workload only')
     return p.parse_args()
 
 
@@ -174,6 +187,36 @@ def visible_gpus():
         if v is not None:
             n = min(n, len([x for x in v.split(',') if x.strip() != '']))
     return n
+
+
+DUMP_SAMPLE = 1 << 22           # elements per sampled array: 16 MB in float32, three of them well inside the 64 MB budget of a dump
+
+
+def _sampled(tensors, n=DUMP_SAMPLE, seed=0):
+    """The tensors flattened and concatenated as float32 on the host; above n elements a fixed seeded sample of n of them (sorted positions)."""
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors]) if tensors else torch.zeros(0)
+    if flat.numel() > n:
+        idx = torch.randint(0, flat.numel(), (n,), generator=torch.Generator(device='cpu').manual_seed(seed)).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.cpu().numpy()
+
+
+def dump_outputs(path, result, model):
+    """What one step hands its caller: the loss dict it returns, and the parameters, gradients and running statistics it leaves behind."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    losses = result
+    while isinstance(losses, (tuple, list)):                       # a graph replay returns (loss dict, scaler output)
+        losses = losses[0]
+    if not isinstance(losses, dict):
+        raise RuntimeError('--dump-outputs: the timed step returned %s, not a loss dict' % type(result).__name__)
+    for k, v in losses.items():
+        np.save(os.path.join(path, 'loss_%s.npy' % k), np.asarray(v.detach().double().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64))
+    params = [p for _, p in model.named_parameters() if p.requires_grad]
+    np.save(os.path.join(path, 'params_sample.npy'), _sampled(params))
+    np.save(os.path.join(path, 'grads_sample.npy'), _sampled([p.grad if p.grad is not None else torch.zeros_like(p) for p in params]))
+    np.save(os.path.join(path, 'buffers_sample.npy'), _sampled([b for _, b in model.named_buffers() if b.is_floating_point()]))
 
 
 def lib_sha16():
@@ -362,12 +405,13 @@ def main():
 
     eager_fn = ((lambda img, mask: replica.train_iteration(opt, img, mask, double)) if replica is not None      # noqa: E731
                 else (lambda img, mask: train_step(net, opt, img, mask, params, double, grad_div)))
-    # ---- warm-up; the last warm-up step is instrumented to find the dominant kernel shape
+    # ---- warm-up; with --full (or a profile table) the last warm-up step is instrumented to find the dominant kernel shape
+    instrument = a.full or bool(a.profile_table)
     for i in range(a.warmup):
-        if i == a.warmup - 1:
+        if instrument and i == a.warmup - 1:
             ops.PROFILER.start()
         eager_fn(img, mask)
-    if a.warmup == 0:
+    if instrument and a.warmup == 0:
         ops.PROFILER.start()
         eager_fn(img, mask)
     torch.cuda.synchronize()
@@ -401,26 +445,30 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
+        result = None
         t0 = time.perf_counter()
         marks[0].record()
         for k in range(a.steps):
             img, mask = batches[k % len(batches)]
-            step_fn(img, mask)
+            result = step_fn(img, mask)
             marks[k + 1].record()                          # per-step GPU time without a host synchronisation (median below)
         torch.cuda.synchronize()
         if use_ddp:
             dist.barrier()
-        return time.perf_counter() - t0, marks
+        return time.perf_counter() - t0, marks, result
 
     # Region 1 -- the K timed steps of `value`: uninstrumented (graph replays on one GPU; kernel by kernel under DDP).
-    # Region 2 -- K more steps issued kernel by kernel with HIP-event pairs around every launch of the roofline kernel (each pair costs two
+    # Region 2 (--full) -- K more steps issued kernel by kernel with HIP-event pairs around every launch of the roofline kernel (each pair costs two
     # ~5.7 us queue markers: 0.3 ms per R50 step, more next to DDP's RCCL stream, so they stay out of the number the driver compares).
-    dt_s, marks = timed_region((lambda img, mask: graphed(img, mask)) if graphed is not None else eager_fn)
+    dt_s, marks, last = timed_region((lambda img, mask: graphed(img, mask)) if graphed is not None else eager_fn)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last, model)          # before region 2, which steps the model further
+    last = None
     eager_ms = None
-    if os.environ.get('SEGLAND_BENCH_NOEVENTS') != '1':
+    if a.full and os.environ.get('SEGLAND_BENCH_NOEVENTS') != '1':
         if dominant is not None:
             ops.PROFILER.start(only=dominant['family'])
-        dt_e, _ = timed_region(eager_fn)
+        dt_e, _, _ = timed_region(eager_fn)
         eager_ms = 1e3 * dt_e / a.steps
     live = ops.PROFILER.stop()
     if use_ddp:
@@ -467,37 +515,38 @@ def main():
         per = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(a.steps))
         out['ms_per_step_median'] = round(per[len(per) // 2], 3)
         out['value_at_median'] = round(a.batch * world / (per[len(per) // 2] * 1e-3), 1)
-        out['tflops_note'] = ('whole_step_tflops = tiles/s x the REFERENCE algorithm FLOPs per tile (%.1f GFLOP: what a plain implementation executes); '
-                              'executed_tflops = tiles/s x the FLOPs this build launches on the MFMA kernels (collapsed head, pooled-grid PPM: see DESIGN.md 3)' % GFLOP_PER_TILE.get(a.backbone, 0))
-        exec_gflop = sum(e['gflop'] for e in table.values())
-        out['executed_tflops'] = round(value * exec_gflop / max(a.batch, 1) / 1e3, 1)
-        fams = {}
-        for k_, e in table.items():
-            fams[k_] = {'tflops': round(e['gflop'] / max(e['ms_total'], 1e-9), 1), 'ms_per_step': round(e['ms_total'], 3), 'launches': e['calls'], 'floor_ms': round(e['floor_ms'], 3)}
-            if e.get('gbytes'):
-                # algorithmic operand + result bytes (activations in and out, weights once, residual addend + gate bits): the HBM-bound families
-                # (conv_gemm_sk_kernel: K <= 256 1x1 convs; conv_c64k3_kernel) are judged on this figure against the 8 TB/s peak, the MFMA-bound ones on tflops
-                fams[k_]['gb_per_s'] = round(e['gbytes'] / max(e['ms_total'], 1e-9) * 1e3, 0)
-        for k_, e in table_bytes.items():
-            fams[k_] = {'gb_per_s': round(e['gbytes'] / max(e['ms_total'], 1e-9) * 1e3, 0), 'ms_per_step': round(e['ms_total'], 3), 'launches': e['calls'], 'gbytes_per_step': round(e['gbytes'], 3),
-                        'floor_ms': round(e['floor_ms'], 3)}
-        out['families'] = fams               # one instrumented (un-timed) step: MFMA families in TFLOP/s, BatchNorm passes in algorithmic GB/s vs the 8 TB/s HBM peak
-        # ---- the step's own speed of light: every instrumented launch priced at max(FLOP / dense MFMA peak, algorithmic bytes / 6.3 TB/s achievable HBM);
-        # what is not instrumented (finalize / column-sum launches, pyramid row GEMMs, head combine, dispatch gaps) enters at its MEASURED time, so the floor errs high
-        opt_key = 'optimizer (clip_grad_norm_ + AdamW)'
-        inst_ms = sum(e['ms_total'] for e in table.values()) + sum(e['ms_total'] for e in table_bytes.values())
-        inst_floor = sum(e['floor_ms'] for e in table.values()) + sum(e['floor_ms'] for e in table_bytes.values())
-        step_ms = 1e3 * dt_s / a.steps
-        rest_ms = max(0.0, step_ms - inst_ms)
-        if opt_key in table_bytes:
-            out['optimizer_ms_per_step'] = round(table_bytes[opt_key]['ms_total'], 3)
-            out['optimizer_note'] = ('clip_grad_norm_(5.0) coefficient + both AdamW steps of train_base.py:262-264 (one launch), HIP events in the instrumented step; it is INSIDE '
-                                     'ms_per_step and value (fwd + bwd alone: ms_per_step - optimizer_ms_per_step)')
-        step_floor = {'step_floor_ms': round(inst_floor + rest_ms, 3), 'frac_of_floor': round((inst_floor + rest_ms) / max(step_ms, 1e-9), 4),
-                      'instrumented_ms': round(inst_ms, 3), 'instrumented_floor_ms': round(inst_floor, 3), 'uninstrumented_ms_at_measured_time': round(rest_ms, 3),
-                      'conv_floor_ms': round(sum(e['floor_ms'] for e in table.values()), 3), 'streaming_floor_ms': round(sum(e['floor_ms'] for e in table_bytes.values()), 3),
-                      'note': 'sum over the launches of one instrumented step of max(FLOP / %g TFLOP/s, algorithmic bytes / 6.3 TB/s); families[*].floor_ms has it per kernel family; '
-                              'frac_of_floor = step_floor_ms / ms_per_step (1.0 = the step runs at its own speed of light)' % peak}
+        if table:                            # an instrumented warm-up step ran (--full, --profile-table): per-kernel figures and the step floor
+            out['tflops_note'] = ('whole_step_tflops = tiles/s x the REFERENCE algorithm FLOPs per tile (%.1f GFLOP: what a plain implementation executes); '
+                                  'executed_tflops = tiles/s x the FLOPs this build launches on the MFMA kernels (collapsed head, pooled-grid PPM: see DESIGN.md 3)' % GFLOP_PER_TILE.get(a.backbone, 0))
+            exec_gflop = sum(e['gflop'] for e in table.values())
+            out['executed_tflops'] = round(value * exec_gflop / max(a.batch, 1) / 1e3, 1)
+            fams = {}
+            for k_, e in table.items():
+                fams[k_] = {'tflops': round(e['gflop'] / max(e['ms_total'], 1e-9), 1), 'ms_per_step': round(e['ms_total'], 3), 'launches': e['calls'], 'floor_ms': round(e['floor_ms'], 3)}
+                if e.get('gbytes'):
+                    # algorithmic operand + result bytes (activations in and out, weights once, residual addend + gate bits): the HBM-bound families
+                    # (conv_gemm_sk_kernel: K <= 256 1x1 convs; conv_c64k3_kernel) are judged on this figure against the 8 TB/s peak, the MFMA-bound ones on tflops
+                    fams[k_]['gb_per_s'] = round(e['gbytes'] / max(e['ms_total'], 1e-9) * 1e3, 0)
+            for k_, e in table_bytes.items():
+                fams[k_] = {'gb_per_s': round(e['gbytes'] / max(e['ms_total'], 1e-9) * 1e3, 0), 'ms_per_step': round(e['ms_total'], 3), 'launches': e['calls'], 'gbytes_per_step': round(e['gbytes'], 3),
+                            'floor_ms': round(e['floor_ms'], 3)}
+            out['families'] = fams               # one instrumented (un-timed) step: MFMA families in TFLOP/s, BatchNorm passes in algorithmic GB/s vs the 8 TB/s HBM peak
+            # ---- the step's own speed of light: every instrumented launch priced at max(FLOP / dense MFMA peak, algorithmic bytes / 6.3 TB/s achievable HBM);
+            # what is not instrumented (finalize / column-sum launches, pyramid row GEMMs, head combine, dispatch gaps) enters at its MEASURED time, so the floor errs high
+            opt_key = 'optimizer (clip_grad_norm_ + AdamW)'
+            inst_ms = sum(e['ms_total'] for e in table.values()) + sum(e['ms_total'] for e in table_bytes.values())
+            inst_floor = sum(e['floor_ms'] for e in table.values()) + sum(e['floor_ms'] for e in table_bytes.values())
+            step_ms = 1e3 * dt_s / a.steps
+            rest_ms = max(0.0, step_ms - inst_ms)
+            if opt_key in table_bytes:
+                out['optimizer_ms_per_step'] = round(table_bytes[opt_key]['ms_total'], 3)
+                out['optimizer_note'] = ('clip_grad_norm_(5.0) coefficient + both AdamW steps of train_base.py:262-264 (one launch), HIP events in the instrumented step; it is INSIDE '
+                                         'ms_per_step and value (fwd + bwd alone: ms_per_step - optimizer_ms_per_step)')
+            step_floor = {'step_floor_ms': round(inst_floor + rest_ms, 3), 'frac_of_floor': round((inst_floor + rest_ms) / max(step_ms, 1e-9), 4),
+                          'instrumented_ms': round(inst_ms, 3), 'instrumented_floor_ms': round(inst_floor, 3), 'uninstrumented_ms_at_measured_time': round(rest_ms, 3),
+                          'conv_floor_ms': round(sum(e['floor_ms'] for e in table.values()), 3), 'streaming_floor_ms': round(sum(e['floor_ms'] for e in table_bytes.values()), 3),
+                          'note': 'sum over the launches of one instrumented step of max(FLOP / %g TFLOP/s, algorithmic bytes / 6.3 TB/s); families[*].floor_ms has it per kernel family; '
+                                  'frac_of_floor = step_floor_ms / ms_per_step (1.0 = the step runs at its own speed of light)' % peak}
         if live:
             e = list(live.values())[0]
             ach = e['gflop'] / max(e['ms_total'], 1e-9)        # GFLOP / ms == TFLOP/s
@@ -558,7 +607,7 @@ def main():
                                        + ' (every shape it serves; a weight-gradient span includes the small fixed-order slab reduce launched behind the kernel); achieved = sum of algorithmic FLOPs / sum of HIP-event time; '
                                        + 'peak is the 2.4 GHz figure: clock_ghz_measured is what the chip sustained under this kernel on N(0,1) operands in the counter pass (the same binary on '
                                        + 'all-zero operands runs +26...+36 % faster, profiles/r2_dvfs_zero_operands.txt, DESIGN.md 3.1c)'}
-        if world == 1 and not use_ddp and not a.no_other_configs and a.model == 'pspnet_pop' and a.backbone == 'resnet50' and a.dtype == 'bf16' and a.batch == 16 and a.size == 512:
+        if a.full and world == 1 and not use_ddp and not a.no_other_configs and a.model == 'pspnet_pop' and a.backbone == 'resnet50' and a.dtype == 'bf16' and a.batch == 16 and a.size == 512:
             # the other BASELINE configurations that fit one GPU, ~5 s each, each in a FRESH child process (round-4 advisor: a memory fault, hang or OOM kill in a side
             # measurement must not cost the headline line; the children are started with subprocess -- this GPU-initialised process never execs)
             model = opt = net = params = batches = graphed = eager_fn = fn = img = mask = replica = None      # noqa: F841
@@ -575,7 +624,7 @@ def main():
                 except Exception as e:                  # noqa: BLE001
                     others[key] = {'error': '%s: %s' % (type(e).__name__, str(e).splitlines()[0] if str(e) else '')}
             out['other_configs'] = others
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(a.cpu_budget, a.backbone, a.model)
         print(json.dumps(out), flush=True)
     if use_ddp:

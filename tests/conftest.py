@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -16,7 +17,11 @@ def pytest_configure(config):
 
 
 def golden(name):
-    return dict(np.load(os.path.join(GOLDEN, name + '.npz'), allow_pickle=False))
+    """tests/golden/<name>.npz, merged with its <name>.partN.npz files (a record too large for one committed file is stored in parts)."""
+    out = dict(np.load(os.path.join(GOLDEN, name + '.npz'), allow_pickle=False))
+    for part in sorted(glob.glob(os.path.join(GOLDEN, glob.escape(name) + '.part*.npz'))):
+        out.update(np.load(part, allow_pickle=False))
+    return out
 
 
 @pytest.fixture(scope='session')

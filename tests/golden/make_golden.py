@@ -77,6 +77,11 @@ def save(name, **arrs):
         out[k] = np.asarray(v)
     path = os.path.join(HERE, name + '.npz')
     np.savez_compressed(path, **out)
+    if os.path.getsize(path) > 1 << 20 and len(out) > 1:
+        # over the 1 MiB limit of a committed file: the largest arrays go to <name>.part2.npz (tests/conftest.py:golden merges the parts)
+        big = sorted(out, key=lambda k: -out[k].nbytes)[:max(1, len(out) // 4)]
+        np.savez_compressed(os.path.join(HERE, name + '.part2.npz'), **{k: out[k] for k in big})
+        np.savez_compressed(path, **{k: v for k, v in out.items() if k not in big})
     print('wrote', path, '%.1f KB' % (os.path.getsize(path) / 1024))
 
 

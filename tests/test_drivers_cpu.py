@@ -134,6 +134,7 @@ def _small_oracle():
 def _worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), WORLD_SIZE=str(world), RANK=str(rank), LOCAL_RANK=str(rank))
     torch.set_num_threads(2)
+    torch.cuda.is_available = lambda: False          # a CPU test: the ranks stay on the CPU (gloo) also on a host with a GPU
     from segland_amd.drivers import build_parser
     from segland_amd.engine import Engine
     with Engine(custom_parser=build_parser(False), argv=['--model', 'pspnet_pop', '--batch-size', '4']) as engine:
@@ -199,9 +200,9 @@ def test_bench_self_launch_starts_fresh_child_ranks(monkeypatch, capsys):
     assert cmd[:3] == [sys.executable, '-m', 'torch.distributed.run'] and '--nproc-per-node' in cmd and cmd[cmd.index('--nproc-per-node') + 1] == '4'
     assert '--master-addr' in cmd and cmd[cmd.index('--master-addr') + 1] == '127.0.0.1' and cmd[-4:] == ['--gpus', '4', '--steps', '5']
     assert env['HSA_ENABLE_IPC_MODE_LEGACY'] == '0'
-    # end to end in a real child: no GPU in this container -> the rank-count message and exit code 3, not a usage error
+    # end to end in a real child that sees no GPU (none visible, also on a host with one) -> the rank-count message and exit code 3, not a usage error
     r = subprocess.run([sys.executable, bench.__file__, '--gpus', '2', '--steps', '1', '--warmup', '0'], capture_output=True, text=True, timeout=600,
-                       env={k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')})
+                       env=dict({k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}, HIP_VISIBLE_DEVICES='', ROCR_VISIBLE_DEVICES=''))
     assert r.returncode == 3 and 'one rank per GPU' in r.stderr and 'usage' not in r.stderr.lower(), (r.returncode, r.stderr[-500:])
 
 

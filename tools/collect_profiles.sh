@@ -25,10 +25,10 @@ for target in "$@"; do
   cd $R
   case $target in
   bench)
-    python bench.py 2>$O/bench_err.txt | json_line > $O/${ROUND}_bench_default.json
-    python bench.py --no-cpu-baseline --no-other-configs --no-step-graph --profile-table $O/${ROUND}_conv_shapes.txt 2>/dev/null | json_line > $O/${ROUND}_bench_kernel_by_kernel.json
-    python bench.py --backbone resnet101 --no-cpu-baseline --profile-table $O/${ROUND}_conv_shapes_r101.txt 2>/dev/null | json_line > $O/${ROUND}_bench_r101.json
-    python bench.py --model swin_pop 2>/dev/null | json_line > $O/${ROUND}_bench_swin.json
+    python bench.py --full 2>$O/bench_err.txt | json_line > $O/${ROUND}_bench_default.json
+    python bench.py --full --no-cpu-baseline --no-other-configs --no-step-graph --profile-table $O/${ROUND}_conv_shapes.txt 2>/dev/null | json_line > $O/${ROUND}_bench_kernel_by_kernel.json
+    python bench.py --full --backbone resnet101 --no-cpu-baseline --profile-table $O/${ROUND}_conv_shapes_r101.txt 2>/dev/null | json_line > $O/${ROUND}_bench_r101.json
+    python bench.py --full --model swin_pop 2>/dev/null | json_line > $O/${ROUND}_bench_swin.json
     for a in "--dtype bf16" "--dtype bf16 --model swin_pop" "--dtype bf16 --pairs 8" "--dtype bf16 --no-step-graph"; do python tools/bench_ft.py $a 2>/dev/null | grep '^{'; done > $O/${ROUND}_bench_ft.txt
     head -c 900 $O/${ROUND}_bench_default.json; echo ;;
   stats)
@@ -44,7 +44,7 @@ for target in "$@"; do
     python3 $R/tools/prof_summary.py /tmp/prof_ft 25 $O/${ROUND}_ft_kernel_stats.txt "tools/bench_ft.py --dtype bf16 --steps 20 --warmup 5 (one tile pair per step; 5 kernel-by-kernel warm-up steps, capture, 20 replays): rocprofv3 --kernel-trace, averaged over 25 steps" > /dev/null ;;
   pmc|pmc_swin)
     cd /tmp && export TMPDIR=/tmp
-    if [ $target = pmc ]; then ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-step-graph --no-other-configs"; TAG=""; else ARGS="--model swin_pop --steps 3 --warmup 1 --no-cpu-baseline --no-step-graph"; TAG="_swin"; fi
+    if [ $target = pmc ]; then ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-step-graph --no-other-configs"; TAG=""; else ARGS="--full --model swin_pop --steps 3 --warmup 1 --no-cpu-baseline --no-step-graph"; TAG="_swin"; fi
     rm -rf /tmp/pmcA /tmp/pmcB /tmp/pmcC /tmp/pmcD
     timeout 600 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d /tmp/pmcA -o b -- python3 $R/bench.py $ARGS > $O/pmc_passA.log 2>&1
     timeout 600 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY -d /tmp/pmcB -o b -- python3 $R/bench.py $ARGS > $O/pmc_passB.log 2>&1

@@ -25,7 +25,7 @@ def load(path):
     return per, dur
 
 
-min_ms, cmd = 0.25, 'python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-step-graph --no-other-configs'
+min_ms, cmd = 0.25, 'python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-step-graph --no-other-configs'
 args = sys.argv[1:]
 while args and args[0].startswith('--'):              # --min-ms X: families below X ms per step are left out;  --cmd '...': the profiled command, for the header
     if args[0] == '--min-ms': min_ms = float(args[1])

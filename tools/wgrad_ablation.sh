@@ -40,5 +40,5 @@ if [ "$1" = run_nst ]; then
       SEGLAND_LIB_PATH=$C/libsegland_$v.so python $R/tools/wgrad_trace.py --k 1 --dil 1 --cin $1 --cout $2 2>&1 | grep -v amdgpu.ids | head -3
     done
   done
-  for v in hip nst5 nst6 hip nst5 nst6; do echo -n "lib $v: "; SEGLAND_LIB_PATH=$C/libsegland_$v.so python $R/bench.py --no-cpu-baseline --no-other-configs --steps 100 2>/dev/null | grep "^{" | python -c "import sys,json; d=json.loads(sys.stdin.read()); f=d['families']; print(d['value'], d['ms_per_step'], {k: v['ms_per_step'] for k, v in f.items() if 'wgrad_glds' in k})"; done
+  for v in hip nst5 nst6 hip nst5 nst6; do echo -n "lib $v: "; SEGLAND_LIB_PATH=$C/libsegland_$v.so python $R/bench.py --full --no-cpu-baseline --no-other-configs --steps 100 2>/dev/null | grep "^{" | python -c "import sys,json; d=json.loads(sys.stdin.read()); f=d['families']; print(d['value'], d['ms_per_step'], {k: v['ms_per_step'] for k, v in f.items() if 'wgrad_glds' in k})"; done
 fi
