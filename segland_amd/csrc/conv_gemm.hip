@@ -8,9 +8,6 @@ namespace {
 // rows per block of the kernel that will run for an M-row problem (also the granularity of the BN partial statistics): 256-row tiles need enough row blocks
 // to fill 256 CUs; the 4-stage ring replaces the 2-stage kernel from 16 blocks of 128 rows (Swin-T stage 3 / 4 GEMMs of 8 192 / 2 048 tokens: +4 %)
 constexpr int MIN_TILES256 = 96, RING128_MIN = 16;
-#ifndef SL_C64K3_GATE
-#define SL_C64K3_GATE 1       // 0: the gated 64 -> 64 3x3 data gradient back on the two-stage 256 x 64 tile kernel (A/B builds, tools/build_variant.sh)
-#endif
 static int block_rows(long long M) { return M >= 256LL * MIN_TILES256 ? 256 : 128; }
 // (Measured and dropped, tools/ft_shapes.py: 256 x 256 tiles by TILE count on short M -- 8 192 rows x 1024 / 2048 channels are 128 / 256 tiles -- lose to the 128 x 128
 // ring kernel with two blocks per CU on three of four shapes: 256 -> 1024 25.0 vs 11.2 us, 512 -> 1024 29.4 vs 16.3, 512 -> 2048 35.1 vs 32.7, 1024 -> 2048 44.9 vs 51.0.)
@@ -35,20 +32,43 @@ static int splitk_parts(const ConvGemmParams& p, int dtype) {
 static bool ring192_on() { return g_sl_debug.conv_ring192 != 0; }          // the 128 x 192 ring tile
 static bool rows_small_on() { return g_sl_debug.conv_rows_small != 0; }    // <= 32-row launches on conv_rows_small_kernel
 static bool ringn64_on() { return g_sl_debug.conv_ringn64 != 0; }          // 64-column inference layers on 128 x 64 ring tiles
-// Which kernel a launch runs on: 1000000 * family + 1000 * BM + BN (family 8 = 3x3 patch (+ 10000000: split-K), 7 = 64 -> 64 patch,
-// 6 = pixel-stationary K <= 256, 5 = half-tile, 4 = ring, 2 = two-stage glds).  The ONE predicate chain: launch_gemm switches on it, sl_conv2d_tile_config(_ex) and
-// sl_conv2d_stat_rows answer from it (round-4 advisor: the query had drifted from the dispatch).
-static int choose_kernel(const ConvGemmParams& p, int dtype) {
+
+// Data gradient of a stride-2 3x3 conv (resnet.py:46, a stage entry's conv2): a destination pixel of parity (py, px) receives only the taps with ky = py + pad, kx = px + pad
+// (mod 2) -- one, two, two or four of the nine.  The undecomposed launch multiplies all nine per pixel, three quarters of them against the zero page (layer2.0.conv2 at the
+// bench shape: 177 us at 109 TFLOP/s; its forward takes 41).  Here the four parity classes run as four launches of the ring kernel's SUBP instantiation, each over the
+// half-resolution grid with its own tap list, writing its pixels in place (the store phases address 2 N elements apart).  Same store phases, same partial-row count.
+static bool parity_shape(const ConvGemmParams& p) {
+  if (!g_sl_debug.conv_parity || p.mode != 1 || p.stride != 2 || p.KH != 3 || p.KW != 3 || p.C2 || (p.C1 % 32)) return false;
+  if (p.Hd != 2 * p.Hs || p.Wd != 2 * p.Ws || (p.N % 128)) return false;
+  if (p.bias || p.scale || p.relu || p.mask_src || p.pre_addend || p.row_scale || p.out2 || p.addend_mask || p.ksplit > 1 || (p.flags & 4) || p.addend_half) return false;
+  if (p.gate ? (p.addend || !p.stat_partial) : (p.addend && p.stat_partial)) return false;         // the three fast store phases: gated statistics, plain (+ statistics), + addend
+  const int Wh = p.Wd / 2, hw = (p.Hd / 2) * Wh;
+  const long long Ms = (long long)p.B * hw;
+  return !((Wh & (Wh - 1)) || Wh % 32 || hw % 256 || Ms < 256LL * MIN_TILES256);              // a sweep inside one image row, a tile inside one image, enough tiles per plane
+}
+static long long plane_rows(const ConvGemmParams& p) { return (long long)p.B * (p.Hd / 2) * (p.Wd / 2); }
+
+// How a launch runs: kernel code cfg = 1000000 * family + 1000 * BM + BN (family 8 = 3x3 patch (+ 10000000: split-K), 7 = 64 -> 64 patch, 6 = pixel-stationary K <= 256,
+// 5 = half-tile, 4 = ring, 3 = <= 32 rows, 2 = two-stage glds); parity: cfg runs as four launches, one per parity plane (parity_shape), instead of one.
+struct Plan {
+  int cfg;
+  bool parity;
+  Plan(int c, bool par = false) : cfg(c), parity(par) {}
+};
+// The ONE predicate chain: launch_gemm runs its plan, sl_conv2d_tile_config(_ex) reports its cfg, and sl_conv2d_stat_rows / sl_conv2d_bwd_data_bnstat_rows count the
+// partial rows of its launches (stat_rows) -- round 4 found the query drifted from the dispatch.  A parity-plane plan reports the ring code of its planes.
+static Plan choose_kernel(const ConvGemmParams& p, int dtype) {
   const bool n128 = (p.N % 128 == 0), n256 = (p.N % 256 == 0);
   const bool big = block_rows(p.M) == 256;           // tiny problems (PPM stages, prototype rows) stay on 128-row tiles
   if (dtype == SL_BF16) {
+    if (parity_shape(p)) return Plan(n256 ? 4256256 : 4256128, true);
     // <= 32 rows of a 1x1 layer (prototype rows of the POP head's MLP): one wave per 32 columns, operands straight from global memory (conv_rows_small_kernel)
     if (rows_small_on() && p.M <= 32 && p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.C2 == 0 && p.Hs == p.Hd && p.Ws == p.Wd && p.N % 32 == 0 && p.ksplit <= 1 &&
         !(p.bias || p.scale || p.addend || p.pre_addend || p.row_scale || p.out2 || p.stat_partial || p.gate || p.addend_mask || (p.flags & 4)))
       return 3032032;
     if (p.ksplit > 1) return 18256256;                                                // planned by splitk_parts: the shape is served by the patch kernel
     if (c64k3_shape(SL_BF16, p.KH, p.KW, p.stride, p.pad, p.dil, p.C1 + p.C2, p.C1, p.N, p.M) && p.Hs == p.Hd && p.Ws == p.Wd &&
-        !(p.bias || p.scale || p.relu || p.addend || p.mask_src || p.pre_addend || p.row_scale || p.out2) && (!p.gate || (SL_C64K3_GATE && p.stat_partial && p.bn_x)))
+        !(p.bias || p.scale || p.relu || p.addend || p.mask_src || p.pre_addend || p.row_scale || p.out2) && (!p.gate || (p.stat_partial && p.bn_x)))
       return 7016016;                                                                  // (round 6: also the gated data gradient with BN-backward column sums)
     if (sk_shape(SL_BF16, p.KH, p.KW, p.stride, p.pad, p.C1 + p.C2, p.C1, p.N, p.M) && p.Hs == p.Hd && p.Ws == p.Wd &&
         !(p.bias || p.scale || p.relu || p.mask_src || p.pre_addend || p.row_scale || p.out2) && (p.gate || !(p.addend && p.stat_partial)) && (p.addend || !p.addend_mask) &&
@@ -94,36 +114,33 @@ static int choose_kernel(const ConvGemmParams& p, int dtype) {
   return 2128064;
 }
 
-// Data gradient of a stride-2 3x3 conv (resnet.py:46, a stage entry's conv2): a destination pixel of parity (py, px) receives only the taps with ky = py + pad, kx = px + pad
-// (mod 2) -- one, two, two or four of the nine.  The undecomposed launch multiplies all nine per pixel, three quarters of them against the zero page (layer2.0.conv2 at the
-// bench shape: 177 us at 109 TFLOP/s; its forward takes 41).  Here the four parity classes run as four launches of the ring kernel's SUBP instantiation, each over the
-// half-resolution grid with its own tap list, writing its pixels in place (the store phases address 2 N elements apart).  Same store phases, same partial-row count.
-static int parity_cfg(const ConvGemmParams& p, int dtype) {
-  if (!g_sl_debug.conv_parity || dtype != SL_BF16 || p.mode != 1 || p.stride != 2 || p.KH != 3 || p.KW != 3 || p.C2 || (p.C1 % 32)) return 0;
-  if (p.Hd != 2 * p.Hs || p.Wd != 2 * p.Ws || (p.N % 128)) return 0;
-  if (p.bias || p.scale || p.relu || p.mask_src || p.pre_addend || p.row_scale || p.out2 || p.addend_mask || p.ksplit > 1 || (p.flags & 4) || p.addend_half) return 0;
-  if (p.gate ? (p.addend || !p.stat_partial) : (p.addend && p.stat_partial)) return 0;             // the three fast store phases: gated statistics, plain (+ statistics), + addend
-  const int Wh = p.Wd / 2, hw = (p.Hd / 2) * Wh;
-  const long long Ms = (long long)p.B * hw;
-  if ((Wh & (Wh - 1)) || Wh % 32 || hw % 256 || Ms < 256LL * MIN_TILES256) return 0;                // a sweep inside one image row, a tile inside one image, enough tiles per plane
-  return p.N % 256 == 0 ? 4256256 : 4256128;
+// Rows of BN statistic partials the plan's launches write: one per row block (conv_c64k3_kernel: per 16 x 16-pixel tile), the four parity planes one after the other
+static long long stat_rows(const Plan& pl, const ConvGemmParams& p) {
+  if (pl.cfg == 7016016) return (long long)p.B * cdiv(p.Hd, C64_T) * cdiv(p.Wd, C64_T);
+  const int bm = (pl.cfg / 1000) % 1000;
+  return pl.parity ? 4LL * cdiv(plane_rows(p), bm) : cdiv(p.M, bm);
 }
-static int launch_parity_planes(int cfg, int dtype, const ConvGemmParams& p, hipStream_t st) {
-  const long long Ms = (long long)p.B * (p.Hd / 2) * (p.Wd / 2);
+
+static int launch_parity_planes(const Plan& pl, int dtype, const ConvGemmParams& p, hipStream_t st) {
+  const long long Ms = plane_rows(p);
+  const int bm = (pl.cfg / 1000) % 1000;
+  const long long rows = Ms / bm;                                                                  // plane k's row blocks: partial rows [k rows, (k + 1) rows)
+  SL_REQUIRE(!p.stat_partial || (Ms % bm == 0 && 4 * rows == stat_rows(pl, p)),
+             "conv parity planes: four planes of %lld rows on %d-row tiles miss the %lld partial rows sl_conv2d_bwd_data_bnstat_rows promises", Ms, bm, stat_rows(pl, p));
   for (int k = 0; k < 4; ++k) {
     ConvGemmParams q = p;
     q.sub = 1; q.sub_py = k >> 1; q.sub_px = k & 1; q.M = (int)Ms;
-    if (q.stat_partial) q.stat_partial = p.stat_partial + (size_t)k * (Ms / 256) * 2 * p.N;       // plane k's row blocks: partial rows [k Ms / 256, (k + 1) Ms / 256)
-    if (int e = launch_tile(cfg, dtype, q, st)) return e;
+    if (q.stat_partial) q.stat_partial = p.stat_partial + (size_t)k * rows * 2 * p.N;
+    if (int e = launch_tile(pl.cfg, dtype, q, st)) return e;
   }
   return 0;
 }
 
 int launch_gemm(int dtype, ConvGemmParams& p, hipStream_t st) {
-  if (const int pc = parity_cfg(p, dtype)) return launch_parity_planes(pc, dtype, p, st);
-  const int cfg = choose_kernel(p, dtype);
+  const Plan pl = choose_kernel(p, dtype);
+  if (pl.parity) return launch_parity_planes(pl, dtype, p, st);
   if (dtype == SL_BF16) {
-    switch (cfg) {
+    switch (pl.cfg) {
       case 18256256: case 8256256: return launch_p9(p, st);
       case 7016016: return launch_c64k3(p, st);
       case 6256064: return launch_sk(p, st);
@@ -131,7 +148,7 @@ int launch_gemm(int dtype, ConvGemmParams& p, hipStream_t st) {
       default: break;
     }
   }
-  return launch_tile(cfg, dtype, p, st);       // families 4 (ring) and 2 (two-stage): conv_gemm_tiles.hip
+  return launch_tile(pl.cfg, dtype, p, st);    // families 4 (ring), 3 (<= 32 rows) and 2 (two-stage): conv_gemm_tiles.hip
 }
 
 int run_gemm(int dtype, ConvGemmParams& p, hipStream_t st) {
@@ -141,6 +158,7 @@ int run_gemm(int dtype, ConvGemmParams& p, hipStream_t st) {
   SL_REQUIRE(p.C1 > 0 && p.C1 % bke == 0 && p.C2 % bke == 0, "conv: source channels (%d,%d) must be multiples of %d", p.C1, p.C2, bke);
   SL_REQUIRE(p.N > 0 && p.N % 64 == 0, "conv: output channels %d must be a multiple of 64", p.N);
   SL_REQUIRE(p.M > 0, "conv: empty output");
+  SL_REQUIRE(!(p.gate && p.bias), "conv: no kernel serves a gated data gradient with a bias");
   return launch_gemm(dtype, p, st);
 }
 
@@ -162,9 +180,9 @@ int check_desc(const SlConvDesc* d) {
 // SL_EPI_AFFINE (bias / folded BN / ReLU / residual: the inference forms), SL_EPI_ADDEND (data gradient + shortcut gradient), SL_EPI_ADDEND_BITS (gated by ReLU bits),
 // SL_EPI_GATE (gated result + BN-backward column sums, sl_conv2d_bwd_data_bnstat), SL_EPI_SPLITK (the split-K plan of sl_conv2d_affine_fwd_ex applies).
 // sl_conv2d_tile_config(d, mode) = the training forms: forward with statistics, plain data gradient.
+// The parameter block the entry points would build for this descriptor (mode 0: forward, 1: data gradient; epi: SL_EPI_* as above), dummy buffers where they pass some
 static unsigned char g_cfg_dummy[16];
-extern "C" int sl_conv2d_tile_config_ex(const SlConvDesc* d, int mode, int epi) {
-  if (!d) return SL_EINVAL;
+static ConvGemmParams query_params(const SlConvDesc* d, int mode, int epi) {
   ConvGemmParams p{};
   void* dm = (void*)g_cfg_dummy;
   p.src1 = dm; p.wt = dm; p.out = dm;
@@ -181,19 +199,20 @@ extern "C" int sl_conv2d_tile_config_ex(const SlConvDesc* d, int mode, int epi) 
   if (epi & SL_EPI_GATE) { p.gate = (const unsigned char*)dm; p.bn_x = dm; p.bn_mean = (const float*)dm; p.bn_invstd = (const float*)dm; p.stat_partial = (float*)dm; }
   if (epi & SL_EPI_GELU) { p.mask_src = dm; p.flags = 4; }
   p.ksplit = (epi & SL_EPI_SPLITK) ? splitk_parts(p, d->dtype) : 1;
-  return choose_kernel(p, d->dtype);
+  return p;
+}
+extern "C" int sl_conv2d_tile_config_ex(const SlConvDesc* d, int mode, int epi) {
+  if (!d) return SL_EINVAL;
+  return choose_kernel(query_params(d, mode, epi), d->dtype).cfg;
 }
 extern "C" int sl_conv2d_tile_config(const SlConvDesc* d, int mode) { return sl_conv2d_tile_config_ex(d, mode, mode == 0 ? SL_EPI_STATS : 0); }
 
-extern "C" int sl_conv2d_tile_config(const SlConvDesc* d, int mode);
-// Rows of the BN statistic partials a forward launch writes: derived from the SAME predicate chain as launch_gemm (sl_conv2d_tile_config), so a
-// change of the dispatch thresholds can never make the caller allocate rows the kernel does not write.
+// Rows of the BN statistic partials a forward launch writes: counted from the plan launch_gemm runs, so a change of the dispatch thresholds can never make the caller
+// allocate rows the kernel does not write.
 extern "C" int sl_conv2d_stat_rows(const SlConvDesc* d) {
   if (!d) return SL_EINVAL;
-  const long long M = (long long)d->B * d->Ho * d->Wo;
-  const int cfg = sl_conv2d_tile_config(d, 0);
-  if (cfg == 7016016) return d->B * cdiv(d->H, C64_T) * cdiv(d->W, C64_T);    // conv_c64k3_kernel: one row per 16 x 16 tile
-  return (int)cdiv(M, (long long)((cfg / 1000) % 1000));
+  const ConvGemmParams p = query_params(d, 0, SL_EPI_STATS);
+  return (int)stat_rows(choose_kernel(p, d->dtype), p);
 }
 
 extern "C" int sl_conv2d_fwd_ex(const SlConvDesc* d, const void* x, const void* x2, const void* w, const void* pre_addend,
@@ -306,13 +325,13 @@ extern "C" int sl_conv2d_bwd_data_gelu(const SlConvDesc* d, const void* dy, cons
 // shapes that the tile kernels with the LDS-staged store phase take (half-tile, 3x3 patch, ring, two-stage) when every row block is full.
 extern "C" int sl_conv2d_bwd_data_bnstat_rows(const SlConvDesc* d) {
   if (!d) return 0;
-  const int cfg = sl_conv2d_tile_config_ex(d, 1, SL_EPI_GATE);
-  const int fam = cfg / 1000000, bm = (cfg / 1000) % 1000;
-  const long long M = (long long)d->B * d->H * d->W;
-  if (cfg == 7016016) return d->B * cdiv(d->H, C64_T) * cdiv(d->W, C64_T);      // conv_c64k3_kernel: one row per 16 x 16 tile (as the forward's statistics)
-  if (!(fam == 5 || fam == 8 || fam == 4 || fam == 2) || bm <= 0 || M % bm != 0) return 0;
-  if (cfg % 1000 == 192) return 0;      // the 128 x 192 ring tile's gated-statistics store phase is not exercised by any BatchNorm model (192-multiple widths are Swin's LayerNorm layers): not offered
-  return (int)(M / bm);
+  const ConvGemmParams p = query_params(d, 1, SL_EPI_GATE);
+  const Plan pl = choose_kernel(p, d->dtype);
+  const int fam = pl.cfg / 1000000, bm = (pl.cfg / 1000) % 1000;
+  if (pl.cfg == 7016016) return (int)stat_rows(pl, p);                  // conv_c64k3_kernel: one row per 16 x 16 tile (as the forward's statistics)
+  if (!(fam == 5 || fam == 8 || fam == 4 || fam == 2) || bm <= 0 || (pl.parity ? plane_rows(p) : p.M) % bm != 0) return 0;
+  if (pl.cfg % 1000 == 192) return 0;      // the 128 x 192 ring tile's gated-statistics store phase is not exercised by any BatchNorm model (192-multiple widths are Swin's LayerNorm layers): not offered
+  return (int)stat_rows(pl, p);
 }
 
 extern "C" int sl_conv2d_bwd_data_bnstat(const SlConvDesc* d, const void* dy, const void* wt, const uint8_t* gate, const void* bn_x, const float* bn_mean,
@@ -325,37 +344,6 @@ extern "C" int sl_conv2d_bwd_data_bnstat(const SlConvDesc* d, const void* dy, co
   p.B = d->B; p.Hs = d->Ho; p.Ws = d->Wo; p.Hd = d->H; p.Wd = d->W;
   p.N = d->Cin; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.mode = 1;
   p.gate = gate; p.bn_x = bn_x; p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.stat_partial = stat_partial;
-  p.M = d->B * d->H * d->W;
-  return run_gemm(d->dtype, p, (hipStream_t)stream);
-}
-
-// The same with the BatchNorm-backward APPLY pass of the conv's own output folded into the data gradient (resnet.py:66-70 backward of conv3 -> bn3, 1x1 convs):
-//   dc3 = cA g + cB (c3 - mean) + cC  and  c3 = a2 W3^T   =>   da2 = dc3 W3 = [g | a2] [diag(cA) W3 ; W3^T diag(cB) W3] + (cC - cB mean) W3
-// i.e. the data gradient reads the GATED incoming gradient g (Cout channels) and the conv's own input a2 (Cin channels) as one virtual concat against an extended
-// weight wt_ext [Cin][Cout + Cin] (sl_bn_fold_weights) plus a per-column bias; the apply pass over (g, c3) -- 6 bytes per element of the Cout-channel tensor -- and
-// the tensor dc3 disappear.  Served: the half-tile kernel's shapes (Cin % 256 == 0, whole 256-row tiles); rows of stat_partial as sl_conv2d_bwd_data_bnstat_rows(d).
-extern "C" int sl_conv2d_bwd_data_bnstat_folded_rows(const SlConvDesc* d) {
-  if (!d || d->dtype != SL_BF16 || d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->H != d->Ho || d->W != d->Wo) return 0;
-  const long long M = (long long)d->B * d->H * d->W;
-  if (d->Cin % 256 || d->Cout % 64 || M % 256 || block_rows((int)M) != 256) return 0;
-  ConvGemmParams p{};
-  p.src1 = p.src2 = p.wt = p.out = (void*)g_cfg_dummy;
-  p.C1 = d->Cout; p.C2 = d->Cin; p.B = d->B; p.Hs = d->Ho; p.Ws = d->Wo; p.Hd = d->H; p.Wd = d->W; p.N = d->Cin; p.M = (int)M;
-  p.KH = p.KW = 1; p.stride = 1; p.pad = 0; p.dil = 1; p.mode = 1; p.ksplit = 1;
-  p.gate = (const unsigned char*)g_cfg_dummy; p.bn_x = g_cfg_dummy; p.bn_mean = p.bn_invstd = p.bias = (const float*)g_cfg_dummy; p.stat_partial = (float*)g_cfg_dummy;
-  return choose_kernel(p, d->dtype) == 5256256 ? (int)(M / 256) : 0;
-}
-
-extern "C" int sl_conv2d_bwd_data_bnstat_folded(const SlConvDesc* d, const void* g, const void* x, const void* wt_ext, const float* bias, const uint8_t* gate, const void* bn_x,
-                                                const float* bn_mean, const float* bn_invstd, void* dx, float* stat_partial, sl_stream_t stream) {
-  if (int e = check_desc(d)) return e;
-  SL_REQUIRE(g && x && wt_ext && bias && dx && gate && bn_x && bn_mean && bn_invstd && stat_partial, "conv bwd_data_bnstat_folded: null buffer");
-  SL_REQUIRE(sl_conv2d_bwd_data_bnstat_folded_rows(d) > 0, "conv bwd_data_bnstat_folded: shape not served (sl_conv2d_bwd_data_bnstat_folded_rows == 0)");
-  ConvGemmParams p{};
-  p.src1 = g; p.src2 = x; p.C1 = d->Cout; p.C2 = d->Cin; p.wt = wt_ext; p.out = dx;
-  p.B = d->B; p.Hs = d->Ho; p.Ws = d->Wo; p.Hd = d->H; p.Wd = d->W;
-  p.N = d->Cin; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.dil = 1; p.mode = 1;
-  p.bias = bias; p.gate = gate; p.bn_x = bn_x; p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.stat_partial = stat_partial;
   p.M = d->B * d->H * d->W;
   return run_gemm(d->dtype, p, (hipStream_t)stream);
 }

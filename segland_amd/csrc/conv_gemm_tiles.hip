@@ -151,10 +151,6 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_glds_kernel(ConvGemmPa
   conv_epilogue_lds<T, BM, BN, WM, WN>(p, acc, bm, bn, wm, wn, lane, tid, smem);
 }
 
-#ifndef SL_RING_LATE
-#define SL_RING_LATE 1          // 0: the round-3..5 schedule (A/B builds: tools/ab_libs.sh)
-#endif
-
 template <typename T, int BM, int BN, int WM, int WN, int RBYTES, int NST>
 struct RingGeom {
   static constexpr int STAGE = (BM + BN) * RBYTES;
@@ -323,7 +319,6 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_ring_kernel(ConvGemmPa
 #pragma unroll
   for (int st = 0; st < D; ++st)
     if (st < nk) issue(st);
-#if SL_RING_LATE
   // Round 6 schedule: a stage is waited for where its first fragments are read -- before the LAST k-step of the iteration in front of it -- not one iteration earlier.
   // Invariant at the top of iteration i: stage i is complete and visible to every wave, the fragments of (stage i, k-step 0) are in registers, stages i+1 .. i+D-1 fly;
   // the slot stage i+D goes to (the one of stage i-1) was released by the barrier inside iteration i-1, behind that iteration's last fragment reads of it.  Same MFMA
@@ -352,29 +347,6 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_ring_kernel(ConvGemmPa
     }
     slot = nslot;
   }
-#else
-  wait_stages(min(nk, D) - 2);                            // stages 0 and 1 landed (later ones may still fly)
-  __builtin_amdgcn_s_barrier();
-  ldfrag(afA, bfA, 0, 0);
-
-  int slot = 0;
-  for (int i = 0; i < nk; ++i) {
-    if (i + D < nk) { int ns = slot + D; if (ns >= NST) ns -= NST; issue(ns); }
-    int nslot = slot + 1; if (nslot == NST) nslot = 0;
-#pragma unroll
-    for (int s2 = 0; s2 < KS; s2 += 2) {
-      ldfrag(afB, bfB, slot, s2 + 1);
-      mma(afA, bfA);
-      if (s2 + 2 < KS) ldfrag(afA, bfA, slot, s2 + 2);
-      else             ldfrag(afA, bfA, nslot, 0);          // first k-step of the next stage (complete by the invariant)
-      mma(afB, bfB);
-    }
-    // make stage i+2 complete before anyone starts iteration i+1; stages i+3 .. i+D (already issued) may stay in flight
-    wait_stages(min(i + D, nk - 1) - (i + 2));
-    __builtin_amdgcn_s_barrier();
-    slot = nslot;
-  }
-#endif
   __syncthreads();
   if constexpr (BN == 192) {
     // 192-column tile (a wave owns 32 rows x all 192 columns): the store phases map a 64 * WM * WN-thread block onto power-of-two row widths, so the tile leaves as three

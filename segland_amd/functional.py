@@ -246,8 +246,6 @@ def _frozen(ctx, *bns):
 
 _PPM_WGRAD_GROUPED = True  # test hook: the pyramid's eight row-GEMM weight gradients as two grouped launches (ops.ppm_rows_wgrad); False: one generic weight-gradient launch + slab reduce per level
 _STAGE_BN_GROUPED = True   # test hook: the pyramid stages' BatchNorm backward in one launch (ops.ppm_stage_bn_bwd); SyncBatchNorm stages always take the per-level chain
-_BN3_FOLD = False          # test hook (default OFF: built and measured 678.3 vs 679.7 tiles/s, profiles/r6_ab_bn3_fold.txt): bn3's backward apply pass folded into conv3's data and weight gradient where the incoming gradient arrived gated and reduced
-_WGRAD_BATCH = False       # test hook: the flat slab reduces of a bottleneck's 1x1 weight gradients in one launch (ops.WgradBatch).  Measured NEGATIVE on the ResNet-50 step (691.1 vs 693.2 tiles/s, profiles/r6_ab_r50_wbatch.txt: the deferred reduce reads cold slabs); kept for the Swin blocks, whose slabs are small
 _DS_HALF = True            # test hook: the data gradient of a stride-2 1x1 downsample conv stays on its own grid (conv2d_bwd_data_addend_half)
 _BASE_CHAIN_CACHE = True   # test hook: ft mode, the frozen base classifier's rows are computed once (False: every iteration)
 # The ONE environment switch of the BatchNorm-backward fusions (A/B of the whole feature against stand-alone reduce passes): SEGLAND_BN_FUSE=0 switches all three off.
@@ -257,7 +255,7 @@ _BN_CROSS = _BN_FUSE       # test hook: bn3's column sums from the NEXT block's 
 
 
 def conv_bn_bwd(dy, y_mask, c, x, conv, bn, mean, invstd, need_dx, need_dw, want_dres=False, addend=None, x2=None, dx_out=None,
-                bits=None, addend_bits=None, pre_partial=None, below=None, bn_done=None, prev3=None, prevd=None, dx_half=False, addend_half=False, wbatch=None):
+                bits=None, addend_bits=None, pre_partial=None, below=None, bn_done=None, prev3=None, prevd=None, dx_half=False, addend_half=False):
     """Backward of y = act(bn(conv(x))).  Returns (dx, dw, dgamma, dbeta, dres, partial_below).
     ReLU gate of dy: `bits` (bit mask from the forward) or `y_mask` (the activation itself).  `addend` (+ optional
     `addend_bits` gate) is accumulated into dx by the dgrad epilogue.
@@ -266,8 +264,7 @@ def conv_bn_bwd(dy, y_mask, c, x, conv, bn, mean, invstd, need_dx, need_dw, want
     store phase, its epilogue gates dx with those bits and emits that layer's column sums (partial_below is then not None and dx is gated).
     bn_done = (dc, dgamma, dbeta): the BatchNorm part was already done by the caller (ops.bn_bwd2: two BatchNorms behind one ReLU in one sweep).
     prev3 = (bits, c3, mean, invstd) of the PREVIOUS bottleneck's bn3 + output ReLU: dx (with its addend, which must be gated already) is that block's incoming
-    gradient; where the pixel-stationary kernel serves the shape it is gated there and reduced against c3 (partial_below = that block's bn3 column sums).
-    wbatch (ops.WgradBatch): a flat (1x1) slab reduce joins the caller's one reduce launch -- dw is filled by wbatch.run()."""
+    gradient; where the pixel-stationary kernel serves the shape it is gated there and reduced against c3 (partial_below = that block's bn3 column sums)."""
     gw, gg, gb = (grad_dst(conv.weight), grad_dst(bn.weight), grad_dst(bn.bias)) if need_dw else (None, None, None)
     if bn_done is not None:
         (dc, dgamma, dbeta), dres = bn_done, None
@@ -279,7 +276,7 @@ def conv_bn_bwd(dy, y_mask, c, x, conv, bn, mean, invstd, need_dx, need_dw, want
     spec = spec_of(conv)
     dx = dw = part_below = None
     if need_dw:
-        dw = grad_alias(ops.conv2d_bwd_weight(x, dc, spec, x2=x2, out=gw, defer=wbatch), gw)
+        dw = grad_alias(ops.conv2d_bwd_weight(x, dc, spec, x2=x2, out=gw), gw)
     if need_dx and dx_half:
         # a 1x1 stride-2 conv (a stage entry's downsample branch): its data gradient is non-zero at the even positions only -- return the DENSE gradient on the conv's own
         # output grid; the consumer adds it at the even positions (ops.conv2d_bwd_data_addend_half), the zero-filled tensor is never written
@@ -432,38 +429,17 @@ class BottleneckFn(torch.autograd.Function):
             prev3 = None
         prevd = plink.bnd if prev3 is not None else None
         want_dres = prev3 is not None and not ctx.has_ds and k3 is not None and p3 is None and done3 is None
-        wbatch = ops.WgradBatch() if (need_w and _WGRAD_BATCH) else None       # the 1x1 convs' slab reduces of this block: one launch at the end (round 6)
-        fold = (_BN3_FOLD and p3 is not None and not ctx.has_ds and need_w and blk.bn3.training and blk.bn2.training and not sync_world(blk.bn3) and k2 is not None
-                and ops.conv2d_bwd_data_bnstat_folded_ok(a2, spec_of(blk.conv3)))
-        if fold:
-            # bn3's apply pass folded into conv3's two gradients: dout arrived gated with its column sums; dc3 is never formed
-            spec3 = spec_of(blk.conv3)
-            g3_, b3_ = grad_dst(blk.bn3.weight), grad_dst(blk.bn3.bias)
-            rows3 = c3.numel() // c3.shape[-1]
-            cA, cB, cC, dg3, db3 = ops.bn_bwd_coeffs(p3, rows3, blk.bn3.weight, m3, i3, dgamma_out=g3_, dbeta_out=b3_)
-            wf3, wb3 = prepared(blk.conv3.weight, c3.dtype)
-            gx, gsum = ops.conv2d_bwd_weight_dy2(a2, dout, a2)      # [g | a2]^T a2 and the column sums of both from one pass over a2
-            n3 = spec3.cout
-            xtx, xsum = gx[n3:], gsum[n3:]
-            wext, vbias = ops.bn_fold_weights(wf3, wb3, cA, cB, db3, xsum, rows3)
-            dg3, db3 = grad_alias(dg3, g3_), grad_alias(db3, b3_)
-            da2, p2 = ops.conv2d_bwd_data_bnstat_folded(dout, a2, wext, vbias, spec3, k2, c2, m2, i2)
-            gw3 = grad_dst(blk.conv3.weight)
-            dw3 = ops.bn_fold_wgrad(gx[:n3], xtx, xsum, wf3, cA, cB, cC, m3, out=gw3 if gw3 is not None else torch.empty((n3, spec3.cin, 1, 1), dtype=torch.float32, device=a2.device))
-            dw3 = grad_alias(dw3, gw3)
-            dres = None
-        else:
-            da2, dw3, dg3, db3, dres, p2 = conv_bn_bwd(dout, None, c3, a2, blk.conv3, blk.bn3, m3, i3, True, need_w, bits=k3, pre_partial=p3,
-                                                       below=(k2, c2, m2, i2) if blk.bn2.training else None, bn_done=done3, want_dres=want_dres, wbatch=wbatch)
+        da2, dw3, dg3, db3, dres, p2 = conv_bn_bwd(dout, None, c3, a2, blk.conv3, blk.bn3, m3, i3, True, need_w, bits=k3, pre_partial=p3,
+                                                   below=(k2, c2, m2, i2) if blk.bn2.training else None, bn_done=done3, want_dres=want_dres)
         da1, dw2, dg2, db2, _, p1 = conv_bn_bwd(da2, None, c2, a1, blk.conv2, blk.bn2, m2, i2, True, need_w, bits=None if p2 is not None else k2, pre_partial=p2,
-                                                below=(k1, c1, m1, i1) if blk.bn1.training else None, wbatch=wbatch)
+                                                below=(k1, c1, m1, i1) if blk.bn1.training else None)
         grads_ds = ()
         if ctx.has_ds:
             cd, md, idd = sv[14:17]
             dsc = blk.downsample[0]
             half = (_DS_HALF and need_x and dsc.kernel_size == (1, 1) and dsc.stride == (2, 2) and dsc.padding == (0, 0) and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0
                     and ops.conv2d_bwd_data_addend_half_ok(x, spec_of(blk.conv1)))
-            dxd, dwd, dgd, dbd, _, _ = conv_bn_bwd(dout, None, cd, x, dsc, blk.downsample[1], md, idd, need_x, need_w, bits=k3, bn_done=doned, dx_half=half, wbatch=wbatch)
+            dxd, dwd, dgd, dbd, _, _ = conv_bn_bwd(dout, None, cd, x, dsc, blk.downsample[1], md, idd, need_x, need_w, bits=k3, bn_done=doned, dx_half=half)
             grads_ds = (dwd, dgd, dbd)
             addend, abits = dxd, None
         elif dres is not None:
@@ -474,9 +450,7 @@ class BottleneckFn(torch.autograd.Function):
             prev3 = None
         dx, dw1, dg1, db1, _, pp = conv_bn_bwd(da1, None, c1, x, blk.conv1, blk.bn1, m1, i1, need_x, need_w,
                                                addend=addend if need_x else None, addend_bits=abits if need_x else None, bits=None if p1 is not None else k1, pre_partial=p1,
-                                               prev3=prev3, prevd=prevd, addend_half=ctx.has_ds and half, wbatch=wbatch)
-        if wbatch is not None:
-            wbatch.run()
+                                               prev3=prev3, prevd=prevd, addend_half=ctx.has_ds and half)
         if pp is not None and prev3 is not None:
             plink.pre3 = (dx.data_ptr(), tuple(dx.shape), pp)
         return (dx, None, dw1, dg1, db1, dw2, dg2, db2, dw3, dg3, db3) + grads_ds

@@ -406,25 +406,13 @@ def workspace(nbytes, dev, tag=None):
     return w
 
 
-def conv2d_bwd_weight(x, dy, spec, x2=None, out=None, out_ci_off=0, defer=None):
+def conv2d_bwd_weight(x, dy, spec, x2=None, out=None, out_ci_off=0):
     """dw (float OIHW).  `out`: a wider [Cout][Ctot][k][k] gradient tensor; this conv's channels land at input-channel offset out_ci_off.  The fixed-order slab
-    reduce follows the MFMA kernel on the same stream -- or, with defer (WgradBatch), joins the batch's one reduce launch where the shape has a flat (1x1) reduce:
-    dw is then filled by defer.run()."""
+    reduce follows the MFMA kernel on the same stream."""
     B, H, W, C1 = x.shape
     d = conv_desc(x.dtype, B, H, W, spec, C1 if x2 is not None else None)
     dw = out if out is not None else torch.empty((spec.cout, spec.cin, spec.k, spec.k), dtype=torch.float32, device=x.device)
     tot = dw.shape[1]
-    if defer is not None and out_ci_off == 0 and tot == spec.cin and dw.is_contiguous():
-        L = _lib.lib()
-        ws = workspace(L.sl_conv2d_bwd_weight_workspace(C.byref(d)), x.device, 'wgrad_d%d' % len(defer.items))
-        item = _lib.SlWgradReduce()
-        tok = PROFILER.begin('conv_wgrad', d)
-        check(L.sl_conv2d_bwd_weight_defer(C.byref(d), _p(x), _p(x2), _p(dy), _p(dw), 0, 0, _p(ws), ws.numel(), None, C.byref(item), _s()), 'conv2d_bwd_weight_defer')
-        PROFILER.end(tok)
-        if item.splits > 0:
-            defer.items.append(item)
-            defer.keep.append((ws, dy, dw))
-        return dw
     ws = workspace(_lib.lib().sl_conv2d_bwd_weight_workspace(C.byref(d)), x.device, 'wgrad')
     tok = PROFILER.begin('conv_wgrad', d)
     check(_lib.lib().sl_conv2d_bwd_weight_ex(C.byref(d), _p(x), _p(x2), _p(dy), _p(dw), tot, out_ci_off, _p(ws), ws.numel(), _s()), 'conv2d_bwd_weight')
@@ -579,82 +567,6 @@ def bn_bwd(dy, y, x, mean, invstd, gamma, train=True, want_dres=False, mask=None
     check(L.sl_bn_bwd_apply(dt(x), _p(dy), _p(y), _p(mask), _p(x), _p(o[2]), _p(o[3]), _p(o[4]), _p(mean), _p(dx), _p(dres), rows, Cn, _s()), 'bn_bwd_apply')
     PROFILER.end_bytes(tok)
     return dx, dres, dg, db
-
-
-def bn_bwd_coeffs(part, rows, gamma, mean, invstd, dgamma_out=None, dbeta_out=None):
-    """Train-mode BatchNorm backward up to the coefficients: (cA, cB, cC, dgamma, dbeta) with dx = cA dy + cB (x - mean) + cC, from the column-sum partials a data-gradient
-    epilogue produced (no reduce pass, no apply pass: the caller folds the apply into the next kernels, bn_fold_weights / bn_fold_wgrad)."""
-    Cn = part.shape[-1]
-    o = _f32((5, Cn), part.device)
-    dg = o[0] if dgamma_out is None else dgamma_out
-    db = o[1] if dbeta_out is None else dbeta_out
-    check(_lib.lib().sl_bn_bwd_finalize(_p(part), part.shape[0], Cn, int(rows), _p(gamma), _p(mean), _p(invstd), 1, _p(dg), _p(db), _p(o[2]), _p(o[3]), _p(o[4]), _s()),
-          'bn_bwd_finalize')
-    return o[2], o[3], o[4], dg, db
-
-
-def conv2d_bwd_data_bnstat_folded_ok(x, spec):
-    """Would conv2d_bwd_data_bnstat_folded serve the data gradient of the 1x1 conv `spec` on input x [B,H,W,Cin]?"""
-    if x.dtype != torch.bfloat16 or spec.k != 1:
-        return False
-    B, H, W, _ = x.shape
-    return _lib.lib().sl_conv2d_bwd_data_bnstat_folded_rows(C.byref(conv_desc(x.dtype, B, H, W, spec, None))) > 0
-
-
-def bn_fold_weights(wf, wb, cA, cB, gsum, xsum, rows):
-    """(wt_ext [Cin][Cout + Cin] bf16, bias [Cin]) of conv2d_bwd_data_bnstat_folded from the layer's prepared weights wf [Cout][Cin], wb [Cin][Cout], the BatchNorm-backward
-    coefficients of its output (bn_bwd_coeffs) and the column sums of the two inputs (gsum = dbeta, xsum = colsum(x))."""
-    Cout, Cin = cA.numel(), xsum.numel()
-    assert wf.numel() == Cout * Cin == wb.numel() and wf.dtype == torch.bfloat16 and gsum.numel() == Cout and gsum.is_contiguous() and xsum.is_contiguous()
-    wext = torch.empty((Cin, Cout + Cin), dtype=torch.bfloat16, device=wf.device)
-    bias = _f32((Cin,), wf.device)
-    check(_lib.lib().sl_bn_fold_weights(Cout, Cin, _p(wf), _p(wb), _p(cA), _p(cB), _p(gsum), _p(xsum), int(rows), _p(wext), _p(bias), _s()), 'bn_fold_weights')
-    return wext, bias
-
-
-def bn_fold_wgrad(gtx, xtx, xsum, wf, cA, cB, cC, mean, out=None):
-    """The weight gradient [Cout][Cin] of a 1x1 conv whose output BatchNorm's apply pass was folded, from gtx = g^T x, xtx = x^T x, xsum = colsum(x); out: its destination
-    (default: in place on gtx)."""
-    Cout, Cin = cA.numel(), xsum.numel()
-    dw = gtx if out is None else out
-    assert gtx.numel() == Cout * Cin == dw.numel() and gtx.is_contiguous() and dw.is_contiguous() and xtx.numel() == Cin * Cin and xtx.is_contiguous()
-    assert gtx.dtype == torch.float32 == xtx.dtype == dw.dtype and xsum.is_contiguous()
-    check(_lib.lib().sl_bn_fold_wgrad(Cout, Cin, _p(gtx), _p(dw), _p(xtx), _p(xsum), _p(wf), _p(cA), _p(cB), _p(cC), _p(mean), _s()), 'bn_fold_wgrad')
-    return dw
-
-
-def conv2d_bwd_weight_dy2(x, dy1, dy2):
-    """[dy1 | dy2]^T x [C1 + C2][Cin] (float) and the column sums of [dy1 | dy2] from ONE weight-gradient launch (1x1 layers; conv_wgrad.hip: two gradient tensors)."""
-    B, H, W, Cin = x.shape
-    c1, c2 = dy1.shape[-1], dy2.shape[-1]
-    spec = ConvSpec(Cin, c1 + c2, 1, 1, 0, 1)
-    d = conv_desc(x.dtype, B, H, W, spec, None)
-    L = _lib.lib()
-    ws = workspace(L.sl_conv2d_bwd_weight_workspace(C.byref(d)), x.device, 'wgrad')
-    dw = torch.empty((c1 + c2, Cin), dtype=torch.float32, device=x.device)
-    part = _f32((_bias_rows(d, 0, 0), c1 + c2), x.device)
-    tok = PROFILER.begin('conv_wgrad', d)
-    check(L.sl_conv2d_bwd_weight_dy2(C.byref(d), _p(x), _p(dy1), _p(dy2), c1, _p(dw), _p(ws), ws.numel(), _p(part), _s()), 'conv2d_bwd_weight_dy2')
-    PROFILER.end(tok)
-    return dw, colsum(part).contiguous()
-
-
-def conv2d_bwd_data_bnstat_folded(g, x, wext, bias, spec, gate, bn_x, mean, invstd):
-    """Data gradient of the 1x1 conv `spec` (input x, gated incoming gradient g of its BatchNorm's output) with that BatchNorm's backward apply pass folded into the weights
-    (bn_fold_weights); the result is gated with `gate` and reduced against bn_x as in conv2d_bwd_data_bnstat.  -> (dx, partial)."""
-    B, H, W, _ = x.shape
-    d = conv_desc(x.dtype, B, H, W, spec, None)
-    L = _lib.lib()
-    rows = L.sl_conv2d_bwd_data_bnstat_folded_rows(C.byref(d))
-    assert rows > 0
-    dx = torch.empty((B, H, W, spec.cin), dtype=x.dtype, device=x.device)
-    part = _f32((rows, 2, spec.cin), x.device)
-    tok = PROFILER.begin('conv_dgrad', d, EPI_GATE)
-    check(L.sl_conv2d_bwd_data_bnstat_folded(C.byref(d), _p(g), _p(x), _p(wext), _p(bias), _p(gate), _p(bn_x), _p(mean), _p(invstd), _p(dx), _p(part), _s()),
-          'conv2d_bwd_data_bnstat_folded')
-    if tok is not None:
-        PROFILER.end(tok, bn_x.numel() * bn_x.element_size() + gate.numel() + x.numel() * x.element_size())
-    return dx, part
 
 
 def bn_bwd2(dy, mask, x1, mean1, invstd1, gamma1, x2, mean2, invstd2, gamma2, outs1=(None, None), outs2=(None, None), pre_partials=None):

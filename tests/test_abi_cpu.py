@@ -146,3 +146,16 @@ def test_dispatch_queries_answer_from_the_dispatch_itself(lib):
         units = B * dil * dil * (W // dil // 16)
         assert tiles == (cout // 128) * (cin // 64) and splits * ppb >= units * ppu and SP == L + (1 if ppu == 1 else 2) and L * ppu >= H // dil
         assert lib.sl_conv2d_bwd_weight_workspace(C.byref(d)) >= nblk * 8 * 4 * 9 * 64 * 4 * 4
+
+
+def test_parity_plane_statistic_rows_come_from_the_launch_plan(lib):
+    """A stride-2 3x3 data gradient runs as four parity-plane launches of the ring kernel; sl_conv2d_bwd_data_bnstat_rows counts the partial rows of those four launches
+    from the same plan launch_gemm runs (host code only).  layer2.0.conv2 at the bench shape (128 -> 128, B 16, 128 x 128 input): four planes of 16 x 64 x 64 rows on
+    256-row tiles.  A batch of one has too few rows per plane: the plan is one launch over all 16 384 rows on 128-row tiles."""
+    GATE = 16
+    d = _desc(_lib.SL_BF16, 16, 128, 128, 128, 128, 3, 2, 1, 1)
+    assert lib.sl_conv2d_tile_config_ex(C.byref(d), 1, GATE) == 4256128
+    assert lib.sl_conv2d_bwd_data_bnstat_rows(C.byref(d)) == 4 * (16 * 64 * 64 // 256)
+    d = _desc(_lib.SL_BF16, 1, 128, 128, 128, 128, 3, 2, 1, 1)
+    assert lib.sl_conv2d_tile_config_ex(C.byref(d), 1, GATE) == 4128128
+    assert lib.sl_conv2d_bwd_data_bnstat_rows(C.byref(d)) == 128 * 128 // 128

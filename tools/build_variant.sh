@@ -1,6 +1,6 @@
 #!/bin/bash
 # A variant build of libsegland_hip.so for a same-box A/B (tools/ab_libs.sh): ONE source file recompiled with extra -D flags, linked with the product's other objects.
-#   bash tools/build_variant.sh <name> <source.hip> -DSL_RING_LATE=0 [...]   ->  segland_amd/csrc/libsegland_<name>.so (git-ignored; delete after the A/B)
+#   bash tools/build_variant.sh <name> <source.hip> -DSL_RING192_NST=3 [...]   ->  segland_amd/csrc/libsegland_<name>.so (git-ignored; delete after the A/B)
 set -eu
 R=$(cd "$(dirname "$0")/.." && pwd); C=$R/segland_amd/csrc
 NAME=$1; SRC=$2; shift 2
