@@ -716,6 +716,22 @@ __device__ __forceinline__ void glds16_asm(const void* g, unsigned lds_addr) {
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(g), "s"(lds_addr) : "memory");
 }
+// Two 16-byte pieces of one (half, operand) pair, LDS rows dst and dst + 1024, from ONE statement: M0 is saved and restored once (7 + 1 instructions for two pieces
+// instead of 10).  M0 is written in the statement that reads it (the compiler may keep a value of its own there); the s_nop follows every M0 write in front of an LDS-DMA.
+// s_add_u32 writes SCC: it is in the clobber list.  The caller counts the two loads in its vmcnt arithmetic exactly like two glds16_asm.
+__device__ __forceinline__ void glds16x2_asm(const void* g0, const void* g1, unsigned lds_addr) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
+               "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(g0), "v"(g1), "s"(lds_addr) : "memory", "scc");
+}
+// The same with a wave-uniform 64-bit base and a 32-bit byte offset per lane (global saddr form): rows that can never be out of range (weight rows)
+__device__ __forceinline__ void glds16x2_sbase_asm(const void* sbase, unsigned off0, unsigned off1, unsigned lds_addr) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %1\n\ts_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
+               "global_load_lds_dwordx4 %3, %1\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "s"(sbase), "v"(off0), "v"(off1), "s"(lds_addr) : "memory", "scc");
+}
 __device__ __forceinline__ unsigned lds_addr_of(const unsigned char* p) {
   return (unsigned)(size_t)((const __attribute__((address_space(3))) unsigned char*)p);
 }

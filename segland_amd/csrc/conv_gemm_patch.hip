@@ -98,7 +98,12 @@ __device__ __forceinline__ int p8_slot_a1(int par) { return (par ? 2 : 7) * P8_S
 __device__ __forceinline__ int p8_slot_b1(int par) { return (par ? 3 : 8) * P8_SLOT; }
 __device__ __forceinline__ int p8_slot_b0(int j) { return (j == 0 ? 9 : j + 3) * P8_SLOT; }
 
-template <int EPI>       // 0: the store phases without MODE 3, 1: with the gated-statistics store phase (MODE 3), 2: with the affine store phases (inference convs, biased Linears)
+// K1: the 1x1 form (one tap, pad 0, one source, no parity plane; any stride, both modes).  Same issue order, slots, waits and MFMA order as the generic form -- results are
+// bit-identical -- but nothing of the tap machinery is left in the K-tile body: `setup` resolves each lane's pixel row to ONE byte pointer per (half, piece) that the issue
+// sites advance by 128 bytes per K-tile (rows past M or outside the source: the zero page, step 0), the weight rows are a wave-uniform base (advanced in scalar registers)
+// plus a 32-bit lane offset, both pieces of a (half, operand) pair leave from one statement (glds16x2_asm), and the last two K-tiles are peeled so that the steady body has
+// one unconditional wait_vmcnt<8> at each of its two wait points.  tools/loop_density.py prints the body's instruction mix next to the generic one.
+template <int EPI, bool K1>       // EPI 0: the store phases without MODE 3, 1: with the gated-statistics store phase (MODE 3), 2: with the affine store phases (inference convs, biased Linears)
 __global__ __launch_bounds__(512) void conv_gemm_p8_kernel(ConvGemmParams p) {
   constexpr bool GATE = EPI == 1, AFF = EPI == 2;
   using T = bf16_t;
@@ -110,8 +115,8 @@ __global__ __launch_bounds__(512) void conv_gemm_p8_kernel(ConvGemmParams p) {
   unsigned long long tr0 = 0, tr1 = 0, tr2 = 0;
   if (p.trace) tr0 = __builtin_amdgcn_s_memtime();
   const int ntiles = p.gridM * p.gridN;
-  const int taps = p.KH * p.KW;
-  const int CT = p.C1 + p.C2;
+  const int taps = K1 ? 1 : p.KH * p.KW;
+  const int CT = K1 ? p.C1 : p.C1 + p.C2;
   const int nk = taps * (CT / 64);
   const int sgn = p.mode == 0 ? 1 : -1;
 
@@ -119,6 +124,8 @@ __global__ __launch_bounds__(512) void conv_gemm_p8_kernel(ConvGemmParams p) {
   const int lr = lane >> 3, lpos = lane & 7;
   int rbase[2][2]; unsigned vmask[2][2]; int rsw[2];
   const unsigned char* wptr[2][2];
+  const unsigned char* aptr[2][2]; unsigned astep[2][2];                // K1: this lane's source piece of the NEXT K-tile to be issued, and its step per K-tile (128 or 0)
+  const unsigned char* wbase[2]; unsigned woff[2];                      // K1: weight rows of half h = wbase[h] (wave-uniform, next K-tile to be issued) + woff[j]
   const size_t wpitch = (size_t)taps * CT * sizeof(T);
 #pragma unroll
   for (int j = 0; j < 2; ++j) rsw[j] = (lpos ^ (((j * 8 + lr) >> 1) & 7)) * 16;
@@ -129,6 +136,29 @@ __global__ __launch_bounds__(512) void conv_gemm_p8_kernel(ConvGemmParams p) {
   };
 
   auto setup = [&](int bm, int bn) {
+    if constexpr (K1) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int m = bm * BM + h * 128 + wave * 16 + j * 8 + lr;
+          aptr[h][j] = g_zero_page + lpos * 16; astep[h][j] = 0;
+          if (m < p.M) {
+            const int b = m / (p.Hd * p.Wd), rem = m - b * (p.Hd * p.Wd);
+            const int yd = rem / p.Wd, xd = rem - yd * p.Wd;
+            const int ry = p.mode == 0 ? yd * p.stride : yd, rx = p.mode == 0 ? xd * p.stride : xd;
+            if ((unsigned)ry < (unsigned)p.Hs && (unsigned)rx < (unsigned)p.Ws) {
+              aptr[h][j] = (const unsigned char*)p.src1 + (size_t)((unsigned)((b * p.Hs + ry) * p.Ws + rx)) * (p.C1 * (unsigned)sizeof(T)) + rsw[j];
+              astep[h][j] = 128;
+            }
+          }
+        }
+        wbase[h] = (const unsigned char*)p.wt + (size_t)(bn * BN + h * 128 + wave * 16) * wpitch;
+      }
+#pragma unroll
+      for (int j = 0; j < 2; ++j) woff[j] = (unsigned)(j * 8 + lr) * (unsigned)wpitch + rsw[j];
+      return;
+    }
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -157,6 +187,12 @@ __global__ __launch_bounds__(512) void conv_gemm_p8_kernel(ConvGemmParams p) {
   const unsigned lds_base = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
   auto issueA = [&](int h, int tap, int ct, int slot_off) {
     const unsigned dst = lds_base + slot_off + wave * 2048;
+    if constexpr (K1) {
+      glds16x2_asm(aptr[h][0], aptr[h][1], dst);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) aptr[h][j] += astep[h][j];
+      return;
+    }
     const int c0 = ct * 64;
     const unsigned char* base; unsigned pitchb;
     if (c0 < p.C1) { base = (const unsigned char*)p.src1 + (size_t)c0 * sizeof(T); pitchb = p.C1 * (unsigned)sizeof(T); }
@@ -172,11 +208,16 @@ __global__ __launch_bounds__(512) void conv_gemm_p8_kernel(ConvGemmParams p) {
   };
   auto issueB = [&](int h, int tap, int ct, int slot_off) {
     const unsigned dst = lds_base + slot_off + wave * 2048;
+    if constexpr (K1) {
+      glds16x2_sbase_asm(wbase[h], woff[0], woff[1], dst);
+      wbase[h] += 128;
+      return;
+    }
     const size_t koff = ((size_t)tap * CT + ct * 64) * sizeof(T);
 #pragma unroll
     for (int j = 0; j < 2; ++j) glds16_asm(wptr[h][j] + koff, dst + j * 1024);
   };
-  auto adv = [&](int& tap, int& ct) { if (++tap == taps) { tap = 0; ++ct; } };
+  auto adv = [&](int& tap, int& ct) { if constexpr (!K1) { if (++tap == taps) { tap = 0; ++ct; } } };      // K1: the pointers themselves advance
   auto issue_first = [&]() { issueB(0, 0, 0, p8_slot_b0(0)); issueA(0, 0, 0, p8_slot_a0(0)); issueA(1, 0, 0, p8_slot_a1(0)); issueB(1, 0, 0, p8_slot_b1(0)); };
 
   // ---- fragment side: lane (l31, fh) reads row base + l31, 16-byte chunk 2*ks + fh (swizzled) of a slot
@@ -225,6 +266,7 @@ __global__ __launch_bounds__(512) void conv_gemm_p8_kernel(ConvGemmParams p) {
     for (int ks = 0; ks < 4; ++ks) { a[ks][0] = ldA(p8_slot_a0(0), 0, ks); a[ks][1] = ldA(p8_slot_a0(0), 1, ks); b0k[ks] = ldB(p8_slot_b0(0), ks); }
 
     int s3 = 0;                                 // i mod 3
+    if constexpr (!K1) {
     for (int i = 0; i < nk; ++i) {
       const int par = i & 1;
       const int s3n = s3 == 2 ? 0 : s3 + 1, s3nn = s3 == 0 ? 2 : s3 - 1;                                   // (i+1) % 3, (i+2) % 3
@@ -257,6 +299,45 @@ __global__ __launch_bounds__(512) void conv_gemm_p8_kernel(ConvGemmParams p) {
       }
       adv(tap2, ct2);
       s3 = s3 == 2 ? 0 : s3 + 1;
+    }
+    } else {
+      // The same K-tile with what the run-time ladder above decides fixed at compile time; the loop is peeled.  TAIL 0: two more K-tiles follow (K-tile i+2 is issued,
+      // both waits leave its 8 loads in flight), 1: the last but one (nothing to issue; at the end of P2 only A1(i+1), B1(i+1) may be in flight), 2: the last.
+      // (Kept apart from the generic loop on purpose: routed through one shared lambda the generic form compiled to 474 instead of 416 other instructions per K-tile.)
+      auto ktile = [&](int i, auto tail_c) {
+        constexpr int TAIL = decltype(tail_c)::value;
+        const int par = i & 1;
+        const int s3n = s3 == 2 ? 0 : s3 + 1, s3nn = s3 == 0 ? 2 : s3 - 1;
+        const int b0nxt = p8_slot_b0(s3n), b0nn = p8_slot_b0(s3nn);
+        const int a1cur = p8_slot_a1(par), b1cur = p8_slot_b1(par), a0nxt = p8_slot_a0(s3n), a0nn = p8_slot_a0(s3nn);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int ph = q >> 2, ks = q & 3;
+          const int ih = ph >> 1, jh = (ph == 1 || ph == 2) ? 1 : 0;
+          if (TAIL == 0 && (ks == 0 || ks == 2) && (ks == 2) == (wm == 1)) {                   // the two-k-step skew of the SIMD's two waves, as above
+            if (ph == 0) issueB(0, 0, 0, b0nn);
+            if (ph == 1) issueA(0, 0, 0, a0nn);
+            if (ph == 3) { issueA(1, 0, 0, a1cur); issueB(1, 0, 0, b1cur); }
+          }
+          if (ph == 0) b1k[ks] = ldB(b1cur, ks);
+          const uint4 bq = (ph == 0 || ph == 3) ? b0k[ks] : b1k[ks];
+          Mma<T>::run(bq, a[ks][0], acc[ih * 2 + 0][jh]);
+          Mma<T>::run(bq, a[ks][1], acc[ih * 2 + 1][jh]);
+          if (ph == 1) { a[ks][0] = ldA(a1cur, 0, ks); a[ks][1] = ldA(a1cur, 1, ks); }
+          if (ph == 3) { a[ks][0] = ldA(a0nxt, 0, ks); a[ks][1] = ldA(a0nxt, 1, ks); b0k[ks] = ldB(b0nxt, ks); }
+          if (ks == 3) {
+            if (ph == 2) wait_vmcnt<TAIL == 0 ? 8 : TAIL == 1 ? 4 : 0>();
+            if (ph == 3) wait_vmcnt<TAIL == 0 ? 8 : 0>();
+            if (ph >= 2) __builtin_amdgcn_s_barrier();
+          }
+        }
+        s3 = s3 == 2 ? 0 : s3 + 1;
+      };
+      int i = 0;
+#pragma unroll 1
+      for (; i + 2 < nk; ++i) ktile(i, std::integral_constant<int, 0>());
+      if (nk > 1) { ktile(i, std::integral_constant<int, 1>()); ++i; }
+      ktile(i, std::integral_constant<int, 2>());
     }
     if (p.trace && tile == (int)blockIdx.x) tr2 = __builtin_amdgcn_s_memtime();
     lds_barrier();
@@ -294,16 +375,19 @@ int slconv::launch_p8(ConvGemmParams& p, hipStream_t st) {
   p.flags |= 1;                                 // the next tile's first wait is counted past the epilogue's own loads and stores
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_gemm_p8_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P8_LDS);
-    (void)hipFuncSetAttribute((const void*)conv_gemm_p8_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P8_LDS);
-    (void)hipFuncSetAttribute((const void*)conv_gemm_p8_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P8_LDS);
+    const void* all[6] = {(const void*)conv_gemm_p8_kernel<0, false>, (const void*)conv_gemm_p8_kernel<1, false>, (const void*)conv_gemm_p8_kernel<2, false>,
+                          (const void*)conv_gemm_p8_kernel<0, true>,  (const void*)conv_gemm_p8_kernel<1, true>,  (const void*)conv_gemm_p8_kernel<2, true>};
+    for (const void* f : all) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P8_LDS);
     attr_set = true;
   }
   const int ntiles = p.gridM * p.gridN;
   // persistent: min(tiles, 256) blocks walk over the tiles; the instantiation with the gated-statistics store phase only where it is used
-  if (p.gate) hipLaunchKernelGGL(conv_gemm_p8_kernel<1>, dim3(ntiles > 256 ? 256 : ntiles), dim3(512), P8_LDS, st, p);
-  else if ((p.bias || p.scale) && !p.stat_partial) hipLaunchKernelGGL(conv_gemm_p8_kernel<2>, dim3(ntiles > 256 ? 256 : ntiles), dim3(512), P8_LDS, st, p);
-  else        hipLaunchKernelGGL(conv_gemm_p8_kernel<0>, dim3(ntiles > 256 ? 256 : ntiles), dim3(512), P8_LDS, st, p);
+  const int epi = p.gate ? 1 : (p.bias || p.scale) && !p.stat_partial ? 2 : 0;
+  // the 1x1 form of the K-tile body (test hook sl_debug_conv_p8_k1: 0 sends these launches through the generic form, which gives the same bits)
+  const bool k1 = g_sl_debug.conv_p8_k1 && p.KH == 1 && p.KW == 1 && p.pad == 0 && p.C2 == 0 && !p.sub;
+  void (*const kern[2][3])(ConvGemmParams) = {{conv_gemm_p8_kernel<0, false>, conv_gemm_p8_kernel<1, false>, conv_gemm_p8_kernel<2, false>},
+                                              {conv_gemm_p8_kernel<0, true>, conv_gemm_p8_kernel<1, true>, conv_gemm_p8_kernel<2, true>}};
+  hipLaunchKernelGGL(kern[k1][epi], dim3(ntiles > 256 ? 256 : ntiles), dim3(512), P8_LDS, st, p);
   SL_LAUNCH_CHECK("conv_gemm_p8_kernel");
   return 0;
 }
