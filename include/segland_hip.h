@@ -263,6 +263,31 @@ size_t sl_stem_conv_bwd_weight_workspace(int B, int H, int W);
 int sl_stem_conv_bwd_weight(int dtype, const float* img_nchw, const void* dc0, float* dw_oihw, void* workspace,
                             size_t workspace_bytes, int B, int H, int W, sl_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------ stem (deep)
+ * resnet.py:144-153,186-190 (ResNetv2): conv 3x3 s2 p1 3->64, BN, ReLU, conv 3x3 64->64, BN, ReLU, conv 3x3 64->128, BN, ReLU, maxpool 3x3 s2 p1.
+ * conv2 / conv3 are sl_conv2d_* layers; the entries below are the first conv (NCHW float image in, no im2col in memory) and the pool for C channels. */
+/* resnet.py:144,187: rows of the statistic partials of sl_stem3_conv_fwd (one per 16 x 16 output tile; the launch's own grid) */
+int sl_stem3_conv_stat_rows(int B, int H, int W);
+size_t sl_stem3_conv_fwd_workspace(int dtype);                                /* bytes of caller-provided scratch (bf16: the weights in MFMA fragment order) */
+/* resnet.py:144,187: y [B][(H+1)/2][(W+1)/2][64] dtype = conv1(img).  stat_partial (nullable): [sl_stem3_conv_stat_rows][2][64] (sum, sum of squares) of the fp32
+ * accumulators, the format sl_bn_finalize_train consumes.  scale / shift (nullable, a pair; stat_partial must then be NULL): y = relu(conv * scale + shift),
+ * bn1 on frozen statistics + relu1 (resnet.py:145-146) in the same launch. */
+int sl_stem3_conv_fwd(int dtype, const float* img_nchw, const float* w_oihw, const float* scale, const float* shift, void* y, float* stat_partial,
+                      int B, int H, int W, void* workspace, sl_stream_t stream);
+/* resnet.py:144 backward: dw [64][3][3][3] float from the image and dc1 [B][(H+1)/2][(W+1)/2][64]; per-block partials in the workspace, summed in a fixed order
+ * (run-to-run bit-identical).  The image needs no data gradient. */
+size_t sl_stem3_conv_bwd_weight_workspace(int B, int H, int W);
+int sl_stem3_conv_bwd_weight(int dtype, const float* img_nchw, const void* dc1, float* dw_oihw, void* workspace, size_t workspace_bytes,
+                             int B, int H, int W, sl_stream_t stream);
+/* resnet.py:151-153,189-190: sl_stem_bn_relu_pool_fwd for C channels (a multiple of 64, at most 1024; any Hc, Wc >= 1): pooled / argmax [B][(Hc+1)/2][(Wc+1)/2][C].
+ * At C = 64 the result is byte for byte that of sl_stem_bn_relu_pool_fwd. */
+int sl_stem_bn_relu_pool_fwd_c(int dtype, const void* c0, const float* scale, const float* shift, void* pooled,
+                               uint8_t* argmax, int B, int Hc, int Wc, int C, sl_stream_t stream);
+/* resnet.py:151-153,189-190 backward: sl_stem_pool_relu_bwd_bnstat for C channels; stat_partial [sl_stem_pool_relu_bwd_bnstat_c_rows][2][C] */
+int sl_stem_pool_relu_bwd_bnstat_c_rows(int B, int Hc, int Wc, int C);
+int sl_stem_pool_relu_bwd_bnstat_c(int dtype, const void* dpooled, const uint8_t* argmax, const void* c0, const float* scale, const float* shift,
+                                   const float* mean, const float* invstd, void* g0, float* stat_partial, int B, int Hc, int Wc, int C, sl_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------ pyramid pooling
  * pspnet_pop.py:26 AdaptiveAvgPool2d(1,2,3,6) (bins [floor(i*H/s), ceil((i+1)*H/s))) and :33 bilinear
  * (align_corners=False) upsampling of the four stage outputs.  Level l has s_l*s_l cells; the pooled / stage tensors

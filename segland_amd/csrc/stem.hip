@@ -219,11 +219,13 @@ __global__ __launch_bounds__(256) void stem_conv_fwd_mfma_kernel(const float* __
 }
 
 // pooled = maxpool3x3s2p1(relu(c0*scale+shift)); idx = first-max window position ky*3+kx (ATen scan order)
-template <typename T>
+// CH: the channel count as a compile-time constant (64: the 7x7 stem, 128: the deep stem's bn3), 0: any multiple of 64 from the argument Cr.
+template <typename T, int CH>
 __global__ void stem_bn_relu_pool_fwd_kernel(const T* __restrict__ c0, const float* __restrict__ scale, const float* __restrict__ shift,
-                                             T* __restrict__ pooled, uint8_t* __restrict__ idx, int B, int Hc, int Wc) {
-  constexpr int V = Vec16<T>::N, NV = 64 / V;
-  const int Hp = Hc / 2, Wp = Wc / 2;
+                                             T* __restrict__ pooled, uint8_t* __restrict__ idx, int B, int Hc, int Wc, int Cr) {
+  constexpr int V = Vec16<T>::N;
+  const int Cn = CH ? CH : Cr, NV = Cn / V;
+  const int Hp = (Hc + 1) / 2, Wp = (Wc + 1) / 2;      // floor((n + 2 - 3) / 2) + 1
   const long long total = (long long)B * Hp * Wp * NV;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int v = (int)(i % NV); long long r = i / NV;
@@ -242,7 +244,7 @@ __global__ void stem_bn_relu_pool_fwd_kernel(const T* __restrict__ c0, const flo
         const int xx = 2 * px - 1 + kx;
         if ((unsigned)xx >= (unsigned)Wc) continue;
         float xv[V];
-        unpack16<T>(*(const uint4*)(c0 + ((size_t)(b * Hc + yy) * Wc + xx) * 64 + v * V), xv);
+        unpack16<T>(*(const uint4*)(c0 + ((size_t)(b * Hc + yy) * Wc + xx) * Cn + v * V), xv);
 #pragma unroll
         for (int k = 0; k < V; ++k) {
           float a = xv[k] * sc[k] + sh[k];
@@ -251,7 +253,7 @@ __global__ void stem_bn_relu_pool_fwd_kernel(const T* __restrict__ c0, const flo
         }
       }
     }
-    const size_t o = ((size_t)(b * Hp + py) * Wp + px) * 64 + v * V;
+    const size_t o = ((size_t)(b * Hp + py) * Wp + px) * Cn + v * V;
     *(uint4*)(pooled + o) = pack16<T>(best);
     if (idx) {
 #pragma unroll
@@ -264,12 +266,14 @@ __global__ void stem_bn_relu_pool_fwd_kernel(const T* __restrict__ c0, const flo
 // STAT: also the reduce pass of bn1's backward (resnet.py:124 backward): the kernel reads c0 anyway, so the column sums (sum g0, sum g0 * xhat) of each block's
 // elements leave with it as part[block][2][64] (fixed order; the same partial format as bn_bwd_reduce_kernel) -- bn_bwd_reduce's sweep over g0 and c0 (268 MB at the
 // bench shape, 48 us) disappears.  A thread's channel vector is the same in every iteration (the grid stride is a multiple of the vectors per pixel).
-template <typename T, bool STAT>
+// CH as in the forward kernel.  The block has a multiple of NV threads (256 for the power-of-two channel counts), which is what keeps a thread on one channel vector.
+template <typename T, bool STAT, int CH>
 __global__ __launch_bounds__(256) void stem_pool_relu_bwd_kernel(const T* __restrict__ dp, const uint8_t* __restrict__ idx, const T* __restrict__ c0,
                                           const float* __restrict__ scale, const float* __restrict__ shift, T* __restrict__ g0,
-                                          int B, int Hc, int Wc, const float* __restrict__ mean, const float* __restrict__ invstd, float* __restrict__ part) {
-  constexpr int V = Vec16<T>::N, NV = 64 / V;
-  const int Hp = Hc / 2, Wp = Wc / 2;
+                                          int B, int Hc, int Wc, const float* __restrict__ mean, const float* __restrict__ invstd, float* __restrict__ part, int Cr) {
+  constexpr int V = Vec16<T>::N;
+  const int Cn = CH ? CH : Cr, NV = Cn / V;
+  const int Hp = (Hc + 1) / 2, Wp = (Wc + 1) / 2;
   const long long total = (long long)B * Hc * Wc * NV;
   float s1[V], s2[V], mu[V], is[V];
   if (STAT) {
@@ -292,7 +296,7 @@ __global__ __launch_bounds__(256) void stem_pool_relu_bwd_kernel(const T* __rest
       for (int px = px_lo; px <= px_hi; ++px) {
         if (px >= Wp) continue;
         const int kx = x - (2 * px - 1);
-        const size_t o = ((size_t)(b * Hp + py) * Wp + px) * 64 + v * V;
+        const size_t o = ((size_t)(b * Hp + py) * Wp + px) * Cn + v * V;
         float d[V];
         unpack16<T>(*(const uint4*)(dp + o), d);
         const int want = ky * 3 + kx;
@@ -300,7 +304,7 @@ __global__ __launch_bounds__(256) void stem_pool_relu_bwd_kernel(const T* __rest
         for (int k = 0; k < V; ++k) if (idx[o + k] == want) g[k] += d[k];
       }
     }
-    const size_t oc = ((size_t)(b * Hc + y) * Wc + x) * 64 + v * V;
+    const size_t oc = ((size_t)(b * Hc + y) * Wc + x) * Cn + v * V;
     unpack16<T>(*(const uint4*)(c0 + oc), xv);
 #pragma unroll
     for (int k = 0; k < V; ++k) g[k] = (xv[k] * scale[v * V + k] + shift[v * V + k]) > 0.f ? g[k] : 0.f;
@@ -318,11 +322,12 @@ __global__ __launch_bounds__(256) void stem_pool_relu_bwd_kernel(const T* __rest
 #pragma unroll
     for (int k = 0; k < V; ++k) { red[threadIdx.x * 2 * V + k] = s1[k]; red[threadIdx.x * 2 * V + V + k] = s2[k]; }
     __syncthreads();
-    if (threadIdx.x < 128) {
-      const int which = threadIdx.x >> 6, c = threadIdx.x & 63, v = c / V, k = c % V;
+    const int nthr = CH ? 256 : (int)blockDim.x;
+    for (int e = threadIdx.x; e < 2 * Cn; e += nthr) {
+      const int which = e / Cn, c = e - which * Cn, v = c / V, k = c % V;
       float a = 0.f;
-      for (int j = 0; j < 256 / NV; ++j) a += red[(j * NV + v) * 2 * V + which * V + k];
-      part[((size_t)blockIdx.x * 2 + which) * 64 + c] = a;
+      for (int j = 0; j < nthr / NV; ++j) a += red[(j * NV + v) * 2 * V + which * V + k];
+      part[((size_t)blockIdx.x * 2 + which) * Cn + c] = a;
     }
   }
 }
@@ -540,14 +545,55 @@ extern "C" int sl_stem_conv_fwd(int dtype, const float* img_nchw, const float* w
   return 0;
 }
 
+// ---- BN + ReLU + maxpool and its backward for C channels (C = 64: the 7x7 stem; C = 128: behind the deep stem's conv3, resnet.py:189-190)
+namespace {
+
+inline bool pool_c_ok(int C) { return C >= 64 && C % 64 == 0 && C <= 1024; }
+// threads per block of the backward: a multiple of the 16-byte vectors per pixel, so that a thread stays on one channel vector (256 for 64 / 128 / 256 / 512 channels)
+inline int pool_bwd_threads(int dtype, int C) { const int nv = C / (dtype == SL_BF16 ? 8 : 4); return 256 / nv * nv; }
+inline int pool_bwd_stat_rows(int B, int Hc, int Wc, int C) {
+  if (B <= 0 || Hc <= 0 || Wc <= 0 || !pool_c_ok(C)) return 0;
+  const long long blocks = ((long long)B * Hc * Wc * (C / 8) + 255) / 256;           // at least one 16-byte vector per thread in either dtype
+  return (int)(blocks < 2048 ? blocks : 2048);
+}
+
+template <typename T>
+void launch_pool_fwd(const void* c0, const float* scale, const float* shift, void* pooled, uint8_t* argmax, int B, int Hc, int Wc, int C, hipStream_t st) {
+  const long long total = (long long)B * ((Hc + 1) / 2) * ((Wc + 1) / 2) * (C / Vec16<T>::N);
+  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+  if (C == 64) hipLaunchKernelGGL((stem_bn_relu_pool_fwd_kernel<T, 64>), dim3(blocks), dim3(256), 0, st, (const T*)c0, scale, shift, (T*)pooled, argmax, B, Hc, Wc, C);
+  else if (C == 128) hipLaunchKernelGGL((stem_bn_relu_pool_fwd_kernel<T, 128>), dim3(blocks), dim3(256), 0, st, (const T*)c0, scale, shift, (T*)pooled, argmax, B, Hc, Wc, C);
+  else hipLaunchKernelGGL((stem_bn_relu_pool_fwd_kernel<T, 0>), dim3(blocks), dim3(256), 0, st, (const T*)c0, scale, shift, (T*)pooled, argmax, B, Hc, Wc, C);
+}
+
+template <typename T, bool STAT>
+void launch_pool_bwd(int blocks, int threads, const void* dp, const uint8_t* argmax, const void* c0, const float* scale, const float* shift, void* g0, int B, int Hc, int Wc, int C,
+                     const float* mean, const float* invstd, float* part, hipStream_t st) {
+  if (C == 64) hipLaunchKernelGGL((stem_pool_relu_bwd_kernel<T, STAT, 64>), dim3(blocks), dim3(threads), 0, st, (const T*)dp, argmax, (const T*)c0, scale, shift, (T*)g0, B, Hc, Wc, mean, invstd, part, C);
+  else if (C == 128) hipLaunchKernelGGL((stem_pool_relu_bwd_kernel<T, STAT, 128>), dim3(blocks), dim3(threads), 0, st, (const T*)dp, argmax, (const T*)c0, scale, shift, (T*)g0, B, Hc, Wc, mean, invstd, part, C);
+  else hipLaunchKernelGGL((stem_pool_relu_bwd_kernel<T, STAT, 0>), dim3(blocks), dim3(threads), 0, st, (const T*)dp, argmax, (const T*)c0, scale, shift, (T*)g0, B, Hc, Wc, mean, invstd, part, C);
+}
+
+}  // namespace
+
+extern "C" int sl_stem_bn_relu_pool_fwd_c(int dtype, const void* c0, const float* scale, const float* shift, void* pooled,
+                                          uint8_t* argmax, int B, int Hc, int Wc, int C, sl_stream_t stream) {
+  SL_REQUIRE(c0 && scale && shift && pooled && B > 0 && Hc > 0 && Wc > 0, "stem_bn_relu_pool_fwd_c: bad args");
+  SL_REQUIRE(pool_c_ok(C), "stem_bn_relu_pool_fwd_c: C = %d is not a multiple of 64 in 64..1024", C);
+  SL_REQUIRE((long long)B * Hc * Wc * C < (1ll << 31), "stem_bn_relu_pool_fwd_c: more than 2^31 elements");
+  if (dtype == SL_BF16) launch_pool_fwd<bf16_t>(c0, scale, shift, pooled, argmax, B, Hc, Wc, C, (hipStream_t)stream);
+  else if (dtype == SL_F32) launch_pool_fwd<float>(c0, scale, shift, pooled, argmax, B, Hc, Wc, C, (hipStream_t)stream);
+  else SL_REQUIRE(false, "stem_bn_relu_pool_fwd_c: bad dtype");
+  SL_LAUNCH_CHECK("stem_bn_relu_pool_fwd_kernel");
+  return 0;
+}
+
 extern "C" int sl_stem_bn_relu_pool_fwd(int dtype, const void* c0, const float* scale, const float* shift, void* pooled,
                                         uint8_t* argmax, int B, int Hc, int Wc, sl_stream_t stream) {
   SL_REQUIRE(c0 && scale && shift && pooled && B > 0 && Hc % 2 == 0 && Wc % 2 == 0, "stem_bn_relu_pool_fwd: bad args");
-  const long long total = (long long)B * (Hc / 2) * (Wc / 2) * (dtype == SL_BF16 ? 8 : 16);
-  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  if (dtype == SL_BF16) hipLaunchKernelGGL(stem_bn_relu_pool_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)c0, scale, shift, (bf16_t*)pooled, argmax, B, Hc, Wc);
-  else if (dtype == SL_F32) hipLaunchKernelGGL(stem_bn_relu_pool_fwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)c0, scale, shift, (float*)pooled, argmax, B, Hc, Wc);
-  else SL_REQUIRE(false, "stem_bn_relu_pool_fwd: bad dtype");
+  SL_REQUIRE(dtype == SL_BF16 || dtype == SL_F32, "stem_bn_relu_pool_fwd: bad dtype");
+  if (dtype == SL_BF16) launch_pool_fwd<bf16_t>(c0, scale, shift, pooled, argmax, B, Hc, Wc, 64, (hipStream_t)stream);
+  else launch_pool_fwd<float>(c0, scale, shift, pooled, argmax, B, Hc, Wc, 64, (hipStream_t)stream);
   SL_LAUNCH_CHECK("stem_bn_relu_pool_fwd_kernel");
   return 0;
 }
@@ -555,29 +601,39 @@ extern "C" int sl_stem_bn_relu_pool_fwd(int dtype, const void* c0, const float* 
 extern "C" int sl_stem_pool_relu_bwd(int dtype, const void* dpooled, const uint8_t* argmax, const void* c0, const float* scale,
                                      const float* shift, void* g0, int B, int Hc, int Wc, sl_stream_t stream) {
   SL_REQUIRE(dpooled && argmax && c0 && scale && shift && g0 && B > 0 && Hc % 2 == 0 && Wc % 2 == 0, "stem_pool_relu_bwd: bad args");
+  SL_REQUIRE(dtype == SL_BF16 || dtype == SL_F32, "stem_pool_relu_bwd: bad dtype");
   const long long total = (long long)B * Hc * Wc * (dtype == SL_BF16 ? 8 : 16);
   const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  if (dtype == SL_BF16) hipLaunchKernelGGL((stem_pool_relu_bwd_kernel<bf16_t, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dpooled, argmax, (const bf16_t*)c0, scale, shift, (bf16_t*)g0, B, Hc, Wc, nullptr, nullptr, nullptr);
-  else if (dtype == SL_F32) hipLaunchKernelGGL((stem_pool_relu_bwd_kernel<float, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)dpooled, argmax, (const float*)c0, scale, shift, (float*)g0, B, Hc, Wc, nullptr, nullptr, nullptr);
-  else SL_REQUIRE(false, "stem_pool_relu_bwd: bad dtype");
+  if (dtype == SL_BF16) launch_pool_bwd<bf16_t, false>(blocks, 256, dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, 64, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  else launch_pool_bwd<float, false>(blocks, 256, dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, 64, nullptr, nullptr, nullptr, (hipStream_t)stream);
   SL_LAUNCH_CHECK("stem_pool_relu_bwd_kernel");
   return 0;
 }
 
 // The same + the column sums of bn1's backward: stat_partial [sl_stem_pool_relu_bwd_bnstat_rows(B, Hc, Wc)][2][64] (consumed by sl_bn_bwd_finalize like bn_bwd_reduce's)
-extern "C" int sl_stem_pool_relu_bwd_bnstat_rows(int B, int Hc, int Wc) {
-  const long long px = (long long)B * Hc * Wc;
-  if (B <= 0 || Hc <= 0 || Wc <= 0) return 0;
-  const long long blocks = (px * 8 + 255) / 256;           // at least one 16-byte vector per thread in either dtype
-  return (int)(blocks < 2048 ? blocks : 2048);
-}
+extern "C" int sl_stem_pool_relu_bwd_bnstat_rows(int B, int Hc, int Wc) { return pool_bwd_stat_rows(B, Hc, Wc, 64); }
 extern "C" int sl_stem_pool_relu_bwd_bnstat(int dtype, const void* dpooled, const uint8_t* argmax, const void* c0, const float* scale, const float* shift,
                                             const float* mean, const float* invstd, void* g0, float* stat_partial, int B, int Hc, int Wc, sl_stream_t stream) {
   SL_REQUIRE(dpooled && argmax && c0 && scale && shift && mean && invstd && g0 && stat_partial && B > 0 && Hc % 2 == 0 && Wc % 2 == 0, "stem_pool_relu_bwd_bnstat: bad args");
-  const int blocks = sl_stem_pool_relu_bwd_bnstat_rows(B, Hc, Wc);
-  if (dtype == SL_BF16) hipLaunchKernelGGL((stem_pool_relu_bwd_kernel<bf16_t, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dpooled, argmax, (const bf16_t*)c0, scale, shift, (bf16_t*)g0, B, Hc, Wc, mean, invstd, stat_partial);
-  else if (dtype == SL_F32) hipLaunchKernelGGL((stem_pool_relu_bwd_kernel<float, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)dpooled, argmax, (const float*)c0, scale, shift, (float*)g0, B, Hc, Wc, mean, invstd, stat_partial);
-  else SL_REQUIRE(false, "stem_pool_relu_bwd_bnstat: bad dtype");
+  SL_REQUIRE(dtype == SL_BF16 || dtype == SL_F32, "stem_pool_relu_bwd_bnstat: bad dtype");
+  const int blocks = pool_bwd_stat_rows(B, Hc, Wc, 64);
+  if (dtype == SL_BF16) launch_pool_bwd<bf16_t, true>(blocks, 256, dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, 64, mean, invstd, stat_partial, (hipStream_t)stream);
+  else launch_pool_bwd<float, true>(blocks, 256, dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, 64, mean, invstd, stat_partial, (hipStream_t)stream);
+  SL_LAUNCH_CHECK("stem_pool_relu_bwd_kernel");
+  return 0;
+}
+
+// C channels (a multiple of 64, at most 1024): stat_partial [sl_stem_pool_relu_bwd_bnstat_c_rows(B, Hc, Wc, C)][2][C]
+extern "C" int sl_stem_pool_relu_bwd_bnstat_c_rows(int B, int Hc, int Wc, int C) { return pool_bwd_stat_rows(B, Hc, Wc, C); }
+extern "C" int sl_stem_pool_relu_bwd_bnstat_c(int dtype, const void* dpooled, const uint8_t* argmax, const void* c0, const float* scale, const float* shift,
+                                              const float* mean, const float* invstd, void* g0, float* stat_partial, int B, int Hc, int Wc, int C, sl_stream_t stream) {
+  SL_REQUIRE(dpooled && argmax && c0 && scale && shift && mean && invstd && g0 && stat_partial && B > 0 && Hc > 0 && Wc > 0, "stem_pool_relu_bwd_bnstat_c: bad args");
+  SL_REQUIRE(pool_c_ok(C), "stem_pool_relu_bwd_bnstat_c: C = %d is not a multiple of 64 in 64..1024", C);
+  SL_REQUIRE(dtype == SL_BF16 || dtype == SL_F32, "stem_pool_relu_bwd_bnstat_c: bad dtype");
+  SL_REQUIRE((long long)B * Hc * Wc * C < (1ll << 31), "stem_pool_relu_bwd_bnstat_c: more than 2^31 elements");
+  const int blocks = pool_bwd_stat_rows(B, Hc, Wc, C), threads = pool_bwd_threads(dtype, C);
+  if (dtype == SL_BF16) launch_pool_bwd<bf16_t, true>(blocks, threads, dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, C, mean, invstd, stat_partial, (hipStream_t)stream);
+  else launch_pool_bwd<float, true>(blocks, threads, dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, C, mean, invstd, stat_partial, (hipStream_t)stream);
   SL_LAUNCH_CHECK("stem_pool_relu_bwd_kernel");
   return 0;
 }

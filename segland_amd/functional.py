@@ -249,6 +249,7 @@ _STAGE_BN_GROUPED = True   # test hook: the pyramid stages' BatchNorm backward i
 _DS_HALF = True            # test hook: the data gradient of a stride-2 1x1 downsample conv stays on its own grid (conv2d_bwd_data_addend_half)
 _BASE_CHAIN_CACHE = True   # test hook: ft mode, the frozen base classifier's rows are computed once (False: every iteration)
 # The ONE environment switch of the BatchNorm-backward fusions (A/B of the whole feature against stand-alone reduce passes): SEGLAND_BN_FUSE=0 switches all three off.
+# (The deep stem's pool backward is exempt: its kernel exists in the statistics-emitting form only, DeepStemFn.backward always takes bn3's column sums from it.)
 _BN_FUSE = os.environ.get('SEGLAND_BN_FUSE', '1') != '0'        # BN-backward statistics in the data-gradient epilogues (conv_gemm_common.h: conv_epilogue_fast MODE 3)
 _BN_DUAL = _BN_FUSE        # test hook: bn3 + downsample BN backward in one sweep each (bn.hip reduce2 / apply2)
 _BN_CROSS = _BN_FUSE       # test hook: bn3's column sums from the NEXT block's conv1 data-gradient epilogue (pixel-stationary kernel MODE 5)
@@ -333,6 +334,60 @@ class StemFn(torch.autograd.Function):
         dc0, _, dgamma, dbeta = ops.bn_bwd(g0, None, c0, mean, invstd, bn.weight, train=bn.training, sync_world=sync_world(bn), dgamma_out=gg, dbeta_out=gb, pre_partial=pp)
         dw = ops.stem_conv_bwd_weight(img, dc0) if ctx.needs_input_grad[1] else None
         return None, dw, grad_alias(dgamma, gg), grad_alias(dbeta, gb), None, None
+
+
+class DeepStemFn(torch.autograd.Function):
+    """conv1 3x3 s2 -> bn1 -> relu -> conv2 3x3 -> bn2 -> relu -> conv3 3x3 (64 -> 128) -> bn3 -> relu -> maxpool 3x3 s2
+    (networks/backbones/resnet.py:144-153,187-190).  img: NCHW float; the result is NHWC [B, H/4, W/4, 128].
+    conv1 and the pool are the stem kernels (csrc/stem3.hip, csrc/stem.hip); conv2 / conv3 are ordinary layers of the conv dispatch."""
+
+    @staticmethod
+    def forward(ctx, img, net, dtype, *params):
+        bn1, bn2, bn3 = net.bn1, net.bn2, net.bn3
+        w1 = net.conv1.weight.detach()
+        wf3, _ = prepared(net.conv3.weight, dtype)
+        if _frozen(ctx, bn1, bn2, bn3):
+            # frozen statistics, nothing saved: bn1 + relu1 ride in conv1's launch, bn2 + relu2 in conv2's epilogue, bn3 + relu3 in the pool
+            _, _, sc1, sh1 = _bn_eval_coeffs(bn1)
+            a1, _ = ops.stem3_conv_fwd(img, w1, dtype, scale=sc1, shift=sh1)
+            a2 = conv_bn_infer(a1, net.conv2, bn2, relu=True)
+            c3, _ = ops.conv2d_fwd(a2, wf3, spec_of(net.conv3))
+            _, _, sc3, sh3 = _bn_eval_coeffs(bn3)
+            return ops.stem_bn_relu_pool_c(c3, sc3, sh3, want_idx=False)[0]
+        c1, part = ops.stem3_conv_fwd(img, w1, dtype, want_stats=bn1.training)
+        m1, i1, sc1, sh1 = _bn_coeffs(bn1, part, c1.numel() // 64)
+        a1, k1 = ops.bn_act(c1, sc1, sh1, relu=True, want_mask=True)
+        c2, a2, m2, i2, k2 = conv_bn_fwd(a1, net.conv2, bn2, relu=True, want_mask=True)
+        c3, part = ops.conv2d_fwd(a2, wf3, spec_of(net.conv3), want_stats=bn3.training)
+        m3, i3, sc3, sh3 = _bn_coeffs(bn3, part, c3.numel() // c3.shape[-1])
+        pooled, idx = ops.stem_bn_relu_pool_c(c3, sc3, sh3, want_idx=True)        # bn3 + relu3 + maxpool in one pass: relu3's output never exists
+        ctx.net = net
+        ctx.save_for_backward(img, c1, a1, k1, m1, i1, c2, a2, k2, m2, i2, c3, idx, m3, i3, sc3, sh3)
+        return pooled
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dp):
+        img, c1, a1, k1, m1, i1, c2, a2, k2, m2, i2, c3, idx, m3, i3, sc3, sh3 = ctx.saved_tensors
+        net = ctx.net
+        need_w = ctx.needs_input_grad[3]            # the stem's parameters are all-or-nothing frozen, like a bottleneck's
+        # pool + relu3 backward with bn3's column sums in the same sweep over c3; conv3's and conv2's data gradients gate with the ReLU bits below and
+        # emit the next BatchNorm's column sums where their kernel has the staged store phase (conv_bn_bwd: below)
+        g3, p3 = ops.stem_pool_relu_bwd_bnstat_c(dp.contiguous(), idx, c3, sc3, sh3, m3, i3)
+        da2, dw3, dg3, db3, _, p2 = conv_bn_bwd(g3, None, c3, a2, net.conv3, net.bn3, m3, i3, True, need_w, pre_partial=p3,
+                                                below=(k2, c2, m2, i2) if net.bn2.training else None)
+        da1, dw2, dg2, db2, _, p1 = conv_bn_bwd(da2, None, c2, a1, net.conv2, net.bn2, m2, i2, True, need_w, bits=None if p2 is not None else k2, pre_partial=p2,
+                                                below=(k1, c1, m1, i1) if net.bn1.training else None)
+        bn1 = net.bn1
+        gw, gg, gb = (grad_dst(net.conv1.weight), grad_dst(bn1.weight), grad_dst(bn1.bias)) if need_w else (None, None, None)
+        dc1, _, dg1, db1 = ops.bn_bwd(da1, None, c1, m1, i1, bn1.weight, train=bn1.training, mask=None if p1 is not None else k1, sync_world=sync_world(bn1),
+                                      dgamma_out=gg, dbeta_out=gb, pre_partial=p1)
+        dw1 = grad_alias(ops.stem3_conv_bwd_weight(img, dc1, out=gw), gw) if need_w else None        # the image needs no data gradient
+        return (None, None, None, dw1, grad_alias(dg1, gg), grad_alias(db1, gb), dw2, dg2, db2, dw3, dg3, db3)
+
+
+def deep_stem_params(net):
+    return [net.conv1.weight, net.bn1.weight, net.bn1.bias, net.conv2.weight, net.bn2.weight, net.bn2.bias, net.conv3.weight, net.bn3.weight, net.bn3.bias]
 
 
 # ------------------------------------------------------------------------------------------------ bottleneck

@@ -96,7 +96,7 @@ class GFSS_Model(nn.Module):
 
     def late_parameters(self):
         bb = self.backbone
-        early = {id(p) for part in (bb.conv1, bb.bn1, bb.layer1, bb.layer2, bb.layer3) for p in part.parameters()}
+        early = {id(p) for name, part in bb.named_children() if name != 'layer4' for p in part.parameters()}      # the stem (either form) and layer1..3
         return [p for p in self.parameters() if id(p) not in early]
 
     def cut_tensors(self):

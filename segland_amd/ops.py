@@ -692,6 +692,62 @@ def stem_conv_bwd_weight_direct(img, dc0):
     return dw
 
 
+# --------------------------------------------------------------------------------------------- stem (deep)
+def stem3_conv_fwd(img, w, dtype, want_stats=False, scale=None, shift=None):
+    """conv1 of the deep stem (3x3 s2 p1, 3 -> 64) from the NCHW float image -> (y NHWC, statistic partials or None).
+    scale / shift: y = relu(conv * scale + shift) in the same launch (BatchNorm on frozen statistics)."""
+    B, _, H, W = img.shape
+    L = _lib.lib()
+    y = torch.empty((B, (H + 1) // 2, (W + 1) // 2, 64), dtype=dtype, device=img.device)
+    part = _f32((L.sl_stem3_conv_stat_rows(B, H, W), 2, 64), img.device) if want_stats else None
+    need = L.sl_stem3_conv_fwd_workspace(_DT[dtype])
+    ws = torch.empty(need, dtype=torch.uint8, device=img.device) if need else None
+    tok = PROFILER.begin_bytes('stem3_conv_fwd', img.numel() * img.element_size() + y.numel() * y.element_size())
+    check(L.sl_stem3_conv_fwd(_DT[dtype], _p(img), _p(w), _p(scale), _p(shift), _p(y), _p(part), B, H, W, _p(ws), _s()), 'stem3_conv_fwd')
+    PROFILER.end_bytes(tok)
+    return y, part
+
+
+def stem3_conv_bwd_weight(img, dc1, out=None):
+    """Weight gradient of the deep stem's conv1 [64,3,3,3] (float); the im2col view is gathered from the image patch in the LDS, block partials are summed in a fixed order."""
+    B, _, H, W = img.shape
+    L = _lib.lib()
+    ws = workspace(L.sl_stem3_conv_bwd_weight_workspace(B, H, W), img.device)
+    dw = out if out is not None else torch.empty((64, 3, 3, 3), dtype=torch.float32, device=img.device)
+    assert dw.shape == (64, 3, 3, 3) and dw.dtype == torch.float32 and dw.is_contiguous() and dc1.shape == (B, (H + 1) // 2, (W + 1) // 2, 64)
+    tok = PROFILER.begin_bytes('stem3_conv_bwd_weight', img.numel() * img.element_size() + dc1.numel() * dc1.element_size())
+    check(L.sl_stem3_conv_bwd_weight(dt(dc1), _p(img), _p(dc1), _p(dw), _p(ws), ws.numel(), B, H, W, _s()), 'stem3_conv_bwd_weight')
+    PROFILER.end_bytes(tok)
+    return dw
+
+
+def stem_bn_relu_pool_c(c0, scale, shift, want_idx):
+    """stem_bn_relu_pool for any multiple of 64 channels (the deep stem pools 128)."""
+    B, Hc, Wc, Cn = c0.shape
+    shape = (B, (Hc + 1) // 2, (Wc + 1) // 2, Cn)
+    pooled = torch.empty(shape, dtype=c0.dtype, device=c0.device)
+    idx = torch.empty(shape, dtype=torch.uint8, device=c0.device) if want_idx else None
+    tok = PROFILER.begin_bytes('stem_bn_relu_pool_fwd', c0.numel() * c0.element_size() + pooled.numel() * pooled.element_size() + (idx.numel() if idx is not None else 0))
+    check(_lib.lib().sl_stem_bn_relu_pool_fwd_c(dt(c0), _p(c0), _p(scale), _p(shift), _p(pooled), _p(idx), B, Hc, Wc, Cn, _s()), 'stem_bn_relu_pool_fwd_c')
+    PROFILER.end_bytes(tok)
+    return pooled, idx
+
+
+def stem_pool_relu_bwd_bnstat_c(dpooled, idx, c0, scale, shift, mean, invstd):
+    """stem_pool_relu_bwd_bnstat for any multiple of 64 channels -> (g0, partial [rows][2][C])."""
+    B, Hc, Wc, Cn = c0.shape
+    L = _lib.lib()
+    assert dpooled.shape == idx.shape == (B, (Hc + 1) // 2, (Wc + 1) // 2, Cn) and dpooled.dtype == c0.dtype
+    g0 = torch.empty_like(c0)
+    part = _f32((L.sl_stem_pool_relu_bwd_bnstat_c_rows(B, Hc, Wc, Cn), 2, Cn), c0.device)
+    nb = c0.numel() * c0.element_size()
+    tok = PROFILER.begin_bytes('stem_pool_relu_bwd', 2 * nb + nb // 4 + dpooled.numel())
+    check(L.sl_stem_pool_relu_bwd_bnstat_c(dt(c0), _p(dpooled), _p(idx), _p(c0), _p(scale), _p(shift), _p(mean), _p(invstd), _p(g0), _p(part), B, Hc, Wc, Cn, _s()),
+          'stem_pool_relu_bwd_bnstat_c')
+    PROFILER.end_bytes(tok)
+    return g0, part
+
+
 # --------------------------------------------------------------------------------------------- pyramid pooling
 def ppm_desc(x, sizes):
     B, H, W, Cn = x.shape
