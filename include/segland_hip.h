@@ -68,7 +68,8 @@ int sl_conv2d_tile_config(const SlConvDesc* d, int mode);
 #define SL_EPI_GELU 64      /* data gradient behind a GELU (sl_conv2d_bwd_data_gelu) */
 int sl_conv2d_tile_config_ex(const SlConvDesc* d, int mode, int epi);
 /* the same for the weight gradient: 1 = conv_wgrad_c64k3_kernel, 2 = conv_wgrad_c64p_kernel, 3 = conv_wgrad3_kernel (3x3 stride 1, nine taps per block), 10000000 + 1000*BN + BC = conv_wgrad_glds_kernel,
- * 20000000 + ... = conv_wgrad_kernel (+ 500000: rows are pixel pairs); every one is followed by its fixed-order slab reduce. */
+ * 20000000 + ... = conv_wgrad_kernel (+ 500000: rows are pixel pairs); every one is followed by its fixed-order slab reduce.  The answer is for the unclipped call on the layer's own dw
+ * window (sl_conv2d_bwd_weight / _bias): a clipped call (_clip / _defer with fewer channels) takes neither kernel 1 nor 3, a call into a wider dw (_ex) not kernel 1. */
 int sl_conv2d_wgrad_config(const SlConvDesc* d);
 
 /* number of row-blocks of the forward kernel == rows of the BN partial-statistics buffer */

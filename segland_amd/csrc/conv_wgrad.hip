@@ -10,12 +10,9 @@
 // [Cout][tap][Cin] -> OIHW, so results are bit-stable run to run.
 #include <math.h>
 #include <stdlib.h>
+#include <algorithm>
 #include "common.h"
-
-// conv_wgrad3.hip
-bool sl_wgrad3_eligible(const SlConvDesc* d, size_t* ws_bytes);
-int sl_wgrad3_run(const SlConvDesc* d, const void* x, const void* x2, const void* dy, float* dw, int dw_cin_total, int dw_ci_off, void* workspace, size_t workspace_bytes,
-                  hipStream_t st);
+#include "conv_wgrad3.h"
 
 namespace {
 
@@ -867,40 +864,8 @@ int use_tr() { return g_sl_debug.wgrad_tr != 0; }      // bf16 fragments by ds_r
 
 struct WgradPlan { int bnn, bcc, gridN, gridC, taps, splits, rows_per_split; bool glds, pair; size_t ws_bytes; };
 
-WgradPlan plan_shape(const SlConvDesc* d, long long M);
-
-// 64-channel layers (layer1, the stem GEMM): the 128-wide glds tiles do not fit them and the 64-wide register-staged kernel runs at
-// ~75 TFLOP/s.  Reading two consecutive pixels as ONE row doubles both channel counts ([M][64] is bit-identical to [M/2][128]):
-// the paired problem runs on the glds kernel and the true gradient is the sum of the two parity-diagonal blocks of its result
-// (half of the MFMA work is discarded -- still 2-3x faster).  3x3 layers gather the pair per lane, so they need Cin == 64 (one tile).
-// From how many rows a 1x1 layer with a 64-multiple (not 128-multiple) channel count runs as pixel pairs.  64-channel layers: 2^19 (round 1: shorter ones are faster on the
-// 64-wide register-staged kernel; ResNet's layer1 has kernels of its own anyway).  Layers with >= 192 channels on both sides -- Swin stage 2: 192 <-> 576 / 768 on 32 768
-// tokens -- from 16 384 rows (round 4, tools/gemm_time.py: 192 -> 576 66.2 -> 37.4 us, 192 -> 768 53.1 -> 38.3, 768 -> 192 54.3 -> 39.5, 192 -> 192 27.8 -> 24.8;
-// Swin-T POP 717.3 -> 733.7 tiles/s on one box).  The tuning hook sl_debug_wgrad_pair_min (> 0) overrides both.
-static long long pair_min_rows(const SlConvDesc* d) {
-  if (g_sl_debug.wgrad_pair_min_rows > 0) return g_sl_debug.wgrad_pair_min_rows;
-  return (d->Cin >= 192 && d->Cout >= 192) ? 16384 : (1 << 19);
-}
-WgradPlan plan(const SlConvDesc* d) {
-  const int c2 = d->Cin - d->C1;
-  const bool all128 = d->Cout % 128 == 0 && d->C1 % 128 == 0 && c2 % 128 == 0;
-  const bool ident = d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0;
-  const long long M = (long long)d->B * d->Ho * d->Wo;
-  if (!all128 && c2 == 0 && d->dtype == SL_BF16 && M % 2 == 0 && d->Wo % 2 == 0 && d->Cout % 64 == 0 && d->Cin % 64 == 0 &&
-      ((ident && M >= pair_min_rows(d)) || (!ident && d->Cin == 64 && d->stride == 1))) {
-    SlConvDesc d2 = *d;
-    d2.Cout = 2 * d->Cout; d2.Cin = d2.C1 = 2 * d->Cin;
-    WgradPlan pl = plan_shape(&d2, M / 2);
-    pl.pair = true;
-    return pl;
-  }
-  WgradPlan pl = plan_shape(d, M);
-  pl.pair = false;
-  return pl;
-}
-
-WgradPlan plan_shape(const SlConvDesc* d, long long M) {
-  WgradPlan pl;
+WgradPlan plan_shape(const SlConvDesc* d, long long M) {      // (pair stays false: plan())
+  WgradPlan pl{};
   const int c2 = d->Cin - d->C1;
   const bool all128 = d->Cout % 128 == 0 && d->C1 % 128 == 0 && c2 % 128 == 0;
   pl.glds = all128;                               // 128- / 256-wide glds tiles; 64-channel sides run on the register-staged kernel
@@ -941,30 +906,51 @@ WgradPlan plan_shape(const SlConvDesc* d, long long M) {
   return pl;
 }
 
-template <typename T, int BNN, int BCC, int WNN, int WCC, bool TR>
-int launch_wgrad_glds(dim3 grid, WgradParams& p, hipStream_t st) {
+// 64-channel layers (layer1, the stem GEMM): the 128-wide glds tiles do not fit them and the 64-wide register-staged kernel runs at
+// ~75 TFLOP/s.  Reading two consecutive pixels as ONE row doubles both channel counts ([M][64] is bit-identical to [M/2][128]):
+// the paired problem runs on the glds kernel and the true gradient is the sum of the two parity-diagonal blocks of its result
+// (half of the MFMA work is discarded -- still 2-3x faster).  3x3 layers gather the pair per lane, so they need Cin == 64 (one tile).
+// From how many rows a 1x1 layer with a 64-multiple (not 128-multiple) channel count runs as pixel pairs.  64-channel layers: 2^19 (round 1: shorter ones are faster on the
+// 64-wide register-staged kernel; ResNet's layer1 has kernels of its own anyway).  Layers with >= 192 channels on both sides -- Swin stage 2: 192 <-> 576 / 768 on 32 768
+// tokens -- from 16 384 rows (round 4, tools/gemm_time.py: 192 -> 576 66.2 -> 37.4 us, 192 -> 768 53.1 -> 38.3, 768 -> 192 54.3 -> 39.5, 192 -> 192 27.8 -> 24.8;
+// Swin-T POP 717.3 -> 733.7 tiles/s on one box).  The tuning hook sl_debug_wgrad_pair_min (> 0) overrides both.
+static long long pair_min_rows(const SlConvDesc* d) {
+  if (g_sl_debug.wgrad_pair_min_rows > 0) return g_sl_debug.wgrad_pair_min_rows;
+  return (d->Cin >= 192 && d->Cout >= 192) ? 16384 : (1 << 19);
+}
+WgradPlan plan(const SlConvDesc* d) {
+  const int c2 = d->Cin - d->C1;
+  const bool all128 = d->Cout % 128 == 0 && d->C1 % 128 == 0 && c2 % 128 == 0;
+  const bool ident = d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0;
+  const long long M = (long long)d->B * d->Ho * d->Wo;
+  if (!all128 && c2 == 0 && d->dtype == SL_BF16 && M % 2 == 0 && d->Wo % 2 == 0 && d->Cout % 64 == 0 && d->Cin % 64 == 0 &&
+      ((ident && M >= pair_min_rows(d)) || (!ident && d->Cin == 64 && d->stride == 1))) {
+    SlConvDesc d2 = *d;
+    d2.Cout = 2 * d->Cout; d2.Cin = d2.C1 = 2 * d->Cin;
+    WgradPlan pl = plan_shape(&d2, M / 2);
+    pl.pair = true;
+    return pl;
+  }
+  return plan_shape(d, M);
+}
+
+template <typename T, int BNN, int BCC, int WNN, int WCC, bool TR, bool BIAS>
+int launch_wgrad_glds_as(dim3 grid, WgradParams& p, hipStream_t st) {
   const size_t lds = (size_t)wg_ring_depth<T, BNN, BCC>() * 32 * (BNN + BCC) * sizeof(T);        // ring of 32-row stages
   static bool attr_set = false;
   if (!attr_set && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<T, BNN, BCC, WNN, WCC, TR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<T, BNN, BCC, WNN, WCC, TR, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
-  if (p.colsum) {
-    if constexpr (BNN == 256 && BCC == 256) { sl_set_error("conv bwd_weight: no bias instantiation of the 256 x 256 tile"); return SL_EINVAL; }
-    else {
-      static bool attr_set_b = false;
-      if (!attr_set_b && lds > 64 * 1024) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<T, BNN, BCC, WNN, WCC, TR, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set_b = true;
-      }
-      hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, BNN, BCC, WNN, WCC, TR, true>), grid, dim3(64 * WNN * WCC), lds, st, p);
-      SL_LAUNCH_CHECK("conv_wgrad_glds_kernel (bias)");
-      return 0;
-    }
-  }
-  hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, BNN, BCC, WNN, WCC, TR>), grid, dim3(64 * WNN * WCC), lds, st, p);
-  SL_LAUNCH_CHECK("conv_wgrad_glds_kernel");
+  hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, BNN, BCC, WNN, WCC, TR, BIAS>), grid, dim3(64 * WNN * WCC), lds, st, p);
+  SL_LAUNCH_CHECK(BIAS ? "conv_wgrad_glds_kernel (bias)" : "conv_wgrad_glds_kernel");
   return 0;
+}
+template <typename T, int BNN, int BCC, int WNN, int WCC, bool TR>
+int launch_wgrad_glds(dim3 grid, WgradParams& p, hipStream_t st) {
+  if (!p.colsum) return launch_wgrad_glds_as<T, BNN, BCC, WNN, WCC, TR, false>(grid, p, st);
+  if constexpr (BNN == 256 && BCC == 256) { sl_set_error("conv bwd_weight: no bias instantiation of the 256 x 256 tile"); return SL_EINVAL; }
+  else return launch_wgrad_glds_as<T, BNN, BCC, WNN, WCC, TR, true>(grid, p, st);
 }
 
 template <typename T, bool TR>
@@ -990,68 +976,215 @@ int launch_wgrad(const WgradPlan& pl, WgradParams& p, hipStream_t st) {
   return 0;
 }
 
+// The plan of one weight-gradient call.  plan_wgrad is the ONLY statement of the path selection: sl_conv2d_wgrad_config, sl_conv2d_bwd_weight_bias_rows and the launch answer
+// from it; sl_conv2d_bwd_weight_workspace is the maximum over its routes.
+enum WgradRoute { WG_C64K3 = 1, WG_C64P = 2, WG_NINE_TAP = 3, WG_TILES = 4 };       // 1..3 are also the codes sl_conv2d_wgrad_config reports
+enum WgradBias { WB_NONE, WB_KERNEL, WB_REDUCE, WB_PASS };                          // the column sums of dy: not wanted / BIAS instantiation of the tile kernel / blocks of the flat slab-reduce launch / sl_colsum_rows_partial behind the reduce
+// what a call adds to the descriptor: the dw window, the channels that exist (the counts themselves, never 0), whether bias partials are wanted, whether the caller batches the reduce
+struct WgradCall { int dw_cin_total, dw_ci_off, n_valid, c_valid; bool bias, defer; };
+// the launch: route with its tile or nine-tap plan, where the bias partials are made and the rows of colsum_partial that writes, flat slab reduce left to sl_wgrad_reduce_multi, workspace of this route, sl_conv2d_wgrad_config
+struct WgradLaunch { WgradRoute route; WgradPlan tiles; Wg3Plan nine; WgradBias bias; int bias_rows; bool deferred; size_t ws_bytes; int code; };
+struct WgradArgs { const void *x, *x2, *dy; float* dw; void* ws; size_t ws_bytes; float* colsum_partial; SlWgradReduce* defer; hipStream_t st; WgradCall c; };      // the buffers of one call
+inline long long out_rows(const SlConvDesc* d) { return (long long)d->B * d->Ho * d->Wo; }
+inline size_t c64k3_ws_bytes(const SlConvDesc* d) { return (size_t)(c64k3_blocks(d) + 1) * 64 * 64 * 9 * sizeof(float); }      // the blocks' slabs + their sum
+inline size_t c64p_ws_bytes(const SlConvDesc* d) { return (size_t)(c64p_slabs(d) + 1) * d->Cout * d->Cin * sizeof(float); }
+
+WgradLaunch plan_wgrad(const SlConvDesc* d, const WgradCall& c) {
+  WgradLaunch L{};
+  const bool full = c.n_valid == d->Cout && c.c_valid == d->Cin;      // the special kernels' reduces write whole OIHW rows; c64p's flat reduce clips
+  L.bias = c.bias ? WB_PASS : WB_NONE;
+  L.bias_rows = c.bias ? sl_colsum_rows_blocks(out_rows(d), d->Cout, d->dtype) : 0;
+  if (use_tr() && full && c64k3_eligible(d, c.dw_cin_total, c.dw_ci_off)) { L.route = WG_C64K3; L.ws_bytes = c64k3_ws_bytes(d); L.code = 1; return L; }
+  if (use_tr() && c64p_eligible(d)) { L.route = WG_C64P; L.ws_bytes = c64p_ws_bytes(d); L.code = 2; return L; }
+  // 3x3 stride-1 layers with >= 128 x 64 channels: all nine taps from one pass over dy and x (conv_wgrad3.hip; wg3_plan holds the shape rule and the hook sl_debug_wgrad3)
+  if (use_tr() && full && (L.nine = wg3_plan(d)).ok) { L.route = WG_NINE_TAP; L.ws_bytes = L.nine.ws_bytes; L.code = 3; return L; }
+  const WgradPlan& pl = L.tiles = plan(d);
+  L.route = WG_TILES; L.ws_bytes = pl.ws_bytes; L.code = (pl.glds ? 10000000 : 20000000) + (pl.pair ? 500000 : 0) + 1000 * pl.bnn + pl.bcc;
+  const bool flat = !pl.pair && pl.taps == 1;                           // one [Cout][Cin] slab per split: wgrad_reduce_flat_kernel, which can carry column-sum blocks and can be deferred
+  L.deferred = c.defer && flat;
+  if (c.bias && g_sl_debug.wgrad_bias && pl.glds && pl.taps == 1 && !(pl.bnn == 256 && pl.bcc == 256) && use_tr()) {      // (test hook sl_debug_wgrad_bias(0): back in the reduce launch)
+    L.bias = WB_KERNEL; L.bias_rows = pl.splits * (pl.pair ? 2 : 1);    // BIAS instantiation: one row per split, two for pixel pairs
+  } else if (c.bias && flat) L.bias = WB_REDUCE;                        // the same row chunks as the stand-alone pass
+  return L;
+}
+
+// The one place colsum_partial is handed to a kernel: `rows` is what that kernel's grid writes, the caller sized the buffer by the plan (sl_conv2d_bwd_weight_bias_rows)
+int bias_partials(const WgradLaunch& L, const WgradArgs& a, long long rows, float** part) {
+  SL_REQUIRE(rows == L.bias_rows, "conv bwd_weight: the kernel that takes the bias partials writes %lld rows, sl_conv2d_bwd_weight_bias_rows promised %d", rows, L.bias_rows);
+  *part = a.colsum_partial; return 0;
+}
+
+// the fixed-order slab reduces follow their MFMA kernel on the same stream (on a second stream they measured slower inside the captured step:
+// profiles/r3_ab_switches.txt, 27.10 vs 26.53 ms -- every fork / join is a pair of cross-branch dependencies in the graph)
+int run_c64k3(const SlConvDesc* d, const WgradArgs& a) {
+  const int nblk = c64k3_blocks(d), ntiles = d->B * cdiv(d->H, C3_T) * cdiv(d->W, C3_T);
+  const size_t lds = (size_t)(C3_PW * C3_PW + 256) * C3_PITCH;
+  static bool attr_set = false;
+  if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv_wgrad_c64k3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
+  hipLaunchKernelGGL(conv_wgrad_c64k3_kernel, dim3(nblk), dim3(256), lds, a.st, (const bf16_t*)a.x, (const bf16_t*)a.dy, (float*)a.ws, d->B, d->H, d->W, ntiles);
+  SL_LAUNCH_CHECK("conv_wgrad_c64k3_kernel");
+  float* sum = (float*)a.ws + (size_t)nblk * 64 * 64 * 9;
+  if (int e = sl_colsum_finalize((const float*)a.ws, nblk, 64 * 64 * 9, sum, (sl_stream_t)a.st)) return e;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(64), dim3(256), 0, a.st, (const float*)sum, a.dw, 64, 64, 9, 1, 64, 0, 64, 64);      // [n][tap][c] -> OIHW
+  SL_LAUNCH_CHECK("wgrad_reduce_kernel");
+  return 0;
+}
+
+int run_c64p(const SlConvDesc* d, const WgradArgs& a) {
+  const int nblk = c64p_blocks(d), nslab = c64p_slabs(d), ntiles = (int)((long long)d->B * d->H * d->W / CP_T);
+  const size_t lds = (size_t)CP_T * (2 * (d->Cout + d->Cin) + 128);
+#define SL_C64P(CA, CB) do { static bool attr_set = false; \
+    if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv_wgrad_c64p_kernel<CA, CB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; } \
+    hipLaunchKernelGGL((conv_wgrad_c64p_kernel<CA, CB>), dim3(nblk), dim3(256), lds, a.st, (const bf16_t*)a.x, (const bf16_t*)a.dy, (float*)a.ws, ntiles); } while (0)
+  if (d->Cout == 256) SL_C64P(256, 64); else if (d->Cin == 256) SL_C64P(64, 256); else if (d->Cout == 128) SL_C64P(128, 128); else SL_C64P(64, 64);
+#undef SL_C64P
+  SL_LAUNCH_CHECK("conv_wgrad_c64p_kernel");
+  const long long total = (long long)d->Cout * d->Cin;
+  float* sum = (float*)a.ws + (size_t)nslab * total;
+  if (int e = sl_colsum_finalize((const float*)a.ws, nslab, (int)total, sum, (sl_stream_t)a.st)) return e;          // fixed-order column sums over the slabs (one block per 64 numbers)
+  hipLaunchKernelGGL(wgrad_reduce_flat_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, a.st, (const float*)sum, a.dw, total, 1, d->Cin, a.c.dw_cin_total, a.c.dw_ci_off, a.c.n_valid, a.c.c_valid);
+  SL_LAUNCH_CHECK("wgrad_reduce_flat_kernel");
+  return 0;
+}
+
+// the split-K tile kernel; reduce_slabs follows
+int run_tiles(const SlConvDesc* d, const WgradLaunch& L, const WgradArgs& a) {
+  const WgradPlan& pl = L.tiles;
+  SL_REQUIRE(pl.taps <= 49, "conv bwd_weight: kernel window larger than 7x7");
+  WgradParams p{};
+  p.src1 = a.x; p.src2 = a.x2; p.C1 = d->C1; p.C2 = d->Cin - d->C1; p.dy = a.dy; p.ws = (float*)a.ws;
+  p.B = d->B; p.H = d->H; p.W = d->W; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
+  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
+  p.M = d->B * d->Ho * d->Wo; p.rows_per_split = pl.rows_per_split; p.gridN = pl.gridN; p.gridC = pl.gridC; p.taps = pl.taps; p.splits = pl.splits;
+  p.pair = pl.pair ? 1 : 0; p.trace = g_sl_debug.wgrad_trace;
+  if (pl.pair) { p.Cout = 2 * d->Cout; p.C1 = 2 * d->Cin; p.M /= 2; }
+  if (L.bias == WB_KERNEL) {                        // the kernel writes the partials; nothing left for the reduce launch
+    if (int e = bias_partials(L, a, (long long)p.splits * (p.pair ? 2 : 1), &p.colsum)) return e;
+    p.colsum_cout = d->Cout;
+  }
+  return d->dtype == SL_F32 ? launch_wgrad<float, false>(pl, p, a.st) : use_tr() ? launch_wgrad<bf16_t, true>(pl, p, a.st) : launch_wgrad<bf16_t, false>(pl, p, a.st);
+}
+
+// The slab reduce behind the tile kernels: pixel pairs / per tap / flat (1x1), the flat one with the column-sum blocks of the bias gradient in the same launch, or
+// left to the caller's batch (sl_wgrad_reduce_multi) with the same blocks
+int reduce_slabs(const SlConvDesc* d, const WgradLaunch& L, const WgradArgs& a) {
+  const WgradPlan& pl = L.tiles; const WgradCall& c = a.c;
+  const float* ws = (const float*)a.ws;
+  if (pl.pair) {
+    const long long total = (long long)d->Cout * d->Cin * pl.taps;
+    hipLaunchKernelGGL(wgrad_reduce_pair_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, a.st, ws, a.dw, d->Cout, d->Cin, pl.taps, pl.splits, c.dw_cin_total, c.dw_ci_off, c.n_valid, c.c_valid);
+  } else if (pl.taps > 1) {
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(d->Cout * (d->Cin / 64)), dim3(256), 0, a.st, ws, a.dw, d->Cout, d->Cin, pl.taps, pl.splits, c.dw_cin_total, c.dw_ci_off, c.n_valid, c.c_valid);
+  } else {
+    const long long total = (long long)d->Cout * d->Cin;
+    const int nred = (int)((total + 255) / 256);
+    float* part = nullptr;                          // column sums of dy: `ncol` blocks behind the nred reduce blocks, `chunk` rows each
+    long long rows = 0, chunk = 0, ncol = 0;
+    if (L.bias == WB_REDUCE) {
+      rows = out_rows(d); chunk = sl_colsum_rows_chunk(rows, d->Cout, d->dtype == SL_BF16 ? 2 : 4); ncol = (rows + chunk - 1) / chunk;
+      if (int e = bias_partials(L, a, ncol, &part)) return e;
+    }
+    if (L.deferred) {
+      SlWgradReduce& t = *a.defer;
+      t.ws = ws; t.dw = a.dw; t.total = total; t.splits = pl.splits; t.Cin = d->Cin; t.dw_cin_total = c.dw_cin_total; t.dw_ci_off = c.dw_ci_off; t.n_valid = c.n_valid; t.c_valid = c.c_valid;
+      t.dtype = d->dtype; t.Cout = d->Cout; t.dy = part ? a.dy : nullptr; t.rows = rows; t.rows_per_block = chunk; t.colsum_part = part; t.ncol = (int)ncol;
+      return 0;
+    }
+    if (part) {
+#define SL_FLAT_COLSUM(T) hipLaunchKernelGGL(wgrad_reduce_flat_colsum_kernel<T>, dim3(nred + (int)ncol), dim3(256), 0, a.st, ws, a.dw, total, pl.splits, d->Cin, c.dw_cin_total, c.dw_ci_off, \
+                                             nred, (const T*)a.dy, rows, d->Cout, chunk, part, c.n_valid, c.c_valid)
+      if (d->dtype == SL_BF16) SL_FLAT_COLSUM(bf16_t); else SL_FLAT_COLSUM(float);
+#undef SL_FLAT_COLSUM
+      SL_LAUNCH_CHECK("wgrad_reduce_flat_colsum_kernel");
+      return 0;
+    }
+    hipLaunchKernelGGL(wgrad_reduce_flat_kernel, dim3((unsigned)nred), dim3(256), 0, a.st, ws, a.dw, total, pl.splits, d->Cin, c.dw_cin_total, c.dw_ci_off, c.n_valid, c.c_valid);
+  }
+  SL_LAUNCH_CHECK("wgrad_reduce_kernel");
+  return 0;
+}
+
+// dw may be a wider OIHW tensor [Cout][dw_cin_total][KH][KW]; this conv's Cin channels land at input-channel offset dw_ci_off.  a.c.n_valid / c_valid: 0 = all channels
+int bwd_weight(const SlConvDesc* d, WgradArgs a) {
+  SL_REQUIRE(d && a.x && a.dy && a.dw && a.ws, "conv bwd_weight: null buffer");
+  if (a.defer) a.defer->splits = 0;           // 0 = nothing left to do (this path ran its own reduce)
+  WgradCall& c = a.c;
+  if (c.n_valid <= 0) c.n_valid = d->Cout; if (c.c_valid <= 0) c.c_valid = d->Cin;
+  c.bias = a.colsum_partial != nullptr; c.defer = a.defer != nullptr;
+  SL_REQUIRE(c.n_valid <= d->Cout && c.c_valid <= d->Cin, "conv bwd_weight: valid channel counts exceed the (padded) problem");
+  SL_REQUIRE(c.dw_ci_off >= 0 && c.dw_ci_off + c.c_valid <= c.dw_cin_total, "conv bwd_weight: bad dw channel window");
+  const int c2 = d->Cin - d->C1;
+  SL_REQUIRE(d->dtype == SL_BF16 || d->dtype == SL_F32, "conv bwd_weight: bad dtype");
+  SL_REQUIRE(d->Cout % 64 == 0 && d->C1 % 64 == 0 && c2 % 64 == 0, "conv bwd_weight: channels must be multiples of 64 (Cout %d, C1 %d, C2 %d)", d->Cout, d->C1, c2);
+  SL_REQUIRE(c2 == 0 || a.x2, "conv bwd_weight: x2 missing");
+  const WgradLaunch L = plan_wgrad(d, c);
+  if (a.ws_bytes < L.ws_bytes) { sl_set_error("conv bwd_weight: workspace %zu < %zu", a.ws_bytes, L.ws_bytes); return SL_EWORKSPACE; }
+  int e = L.route == WG_C64K3 ? run_c64k3(d, a) : L.route == WG_C64P ? run_c64p(d, a) : L.route == WG_TILES ? run_tiles(d, L, a)
+        : sl_wgrad3_run(d, L.nine, a.x, a.x2, a.dy, a.dw, c.dw_cin_total, c.dw_ci_off, a.ws, a.st);
+  if (!e && L.route == WG_TILES) e = reduce_slabs(d, L, a);
+  if (e || L.bias != WB_PASS) return e;
+  float* part;                                // column sums of dy by the stand-alone kernel: every path that carries them neither in its kernel nor in its reduce launch
+  if ((e = bias_partials(L, a, sl_colsum_rows_blocks(out_rows(d), d->Cout, d->dtype), &part))) return e;
+  return sl_colsum_rows_partial(d->dtype, a.dy, out_rows(d), d->Cout, part, (sl_stream_t)a.st);
+}
+
+inline bool desc_ok(const SlConvDesc* d) { return d && d->Cout % 64 == 0 && d->C1 % 64 == 0 && (d->Cin - d->C1) % 64 == 0; }      // the queries refuse what the launch refuses
+
 }  // namespace
 
-// Which kernel sl_conv2d_bwd_weight runs for a shape (bench.py attributes HIP-event timings to rocprof kernel names with it):
-// 1 conv_wgrad_c64k3_kernel, 2 conv_wgrad_c64p_kernel, 10000000 + 1000*BNN + BCC conv_wgrad_glds_kernel, 20000000 + ... conv_wgrad_kernel;
+// Which kernel sl_conv2d_bwd_weight runs for a shape (bench.py attributes HIP-event timings to rocprof kernel names with it): the plan's code for the unclipped call
+// on the layer's own dw window (a clipped call leaves the 64 -> 64 3x3 and the nine-tap kernel; sl_conv2d_bwd_weight_ex into a wider dw leaves the 64 -> 64 3x3 kernel):
+// 1 conv_wgrad_c64k3_kernel, 2 conv_wgrad_c64p_kernel, 3 conv_wgrad3_kernel, 10000000 + 1000*BNN + BCC conv_wgrad_glds_kernel, 20000000 + ... conv_wgrad_kernel;
 // + 500000 when the rows are pixel pairs.
 extern "C" int sl_conv2d_wgrad_config(const SlConvDesc* d) {
-  if (!d || d->Cout % 64 || d->Cin % 64) return SL_EINVAL;
-  if (c64k3_eligible(d, d->Cin, 0) && use_tr()) return 1;
-  if (c64p_eligible(d) && use_tr()) return 2;
-  if (use_tr() && sl_wgrad3_eligible(d, nullptr)) return 3;
-  const WgradPlan pl = plan(d);
-  return (pl.glds ? 10000000 : 20000000) + (pl.pair ? 500000 : 0) + 1000 * pl.bnn + pl.bcc;
+  if (!desc_ok(d)) return SL_EINVAL;
+  return plan_wgrad(d, WgradCall{d->Cin, 0, d->Cout, d->Cin, false, false}).code;
 }
 
+// the maximum over every route a call on this descriptor may take, whatever its dw window, clip or use_tr()
 extern "C" size_t sl_conv2d_bwd_weight_workspace(const SlConvDesc* d) {
-  if (!d || d->Cout % 64 || d->Cin % 32) return 0;
+  if (!desc_ok(d)) return 0;
   size_t need = plan(d).ws_bytes;
-  { size_t n3 = 0; if (sl_wgrad3_eligible(d, &n3) && n3 > need) need = n3; }
-  if (c64k3_eligible(d, 64, 0)) { const size_t n2 = (size_t)(c64k3_blocks(d) + 1) * 64 * 64 * 9 * sizeof(float); if (n2 > need) need = n2; }
-  if (c64p_eligible(d)) { const size_t n2 = (size_t)(c64p_slabs(d) + 1) * d->Cout * d->Cin * sizeof(float); if (n2 > need) need = n2; }
+  const Wg3Plan nine = wg3_plan(d);
+  if (nine.ok) need = std::max(need, nine.ws_bytes);
+  if (c64k3_eligible(d, d->Cin, 0)) need = std::max(need, c64k3_ws_bytes(d));
+  if (c64p_eligible(d)) need = std::max(need, c64p_ws_bytes(d));
   return need;
 }
-
-extern "C" int sl_colsum_rows_partial(int dtype, const void* x, long long rows, int C, float* partial, sl_stream_t stream);
-extern "C" int sl_conv2d_bwd_weight_ex(const SlConvDesc* d, const void* x, const void* x2, const void* dy, float* dw, int dw_cin_total,
-                                       int dw_ci_off, void* workspace, size_t workspace_bytes, sl_stream_t stream);
+// rows of the colsum_partial buffer sl_conv2d_bwd_weight_bias / _clip / _defer (n_valid, c_valid: 0 = all channels) fill
+extern "C" int sl_conv2d_bwd_weight_bias_rows(const SlConvDesc* d, int n_valid, int c_valid) {
+  if (!desc_ok(d)) { sl_set_error("conv bwd_weight_bias_rows: null descriptor or channel counts that are not multiples of 64"); return SL_EINVAL; }
+  const int nv = n_valid > 0 ? n_valid : d->Cout, cv = c_valid > 0 ? c_valid : d->Cin;
+  return plan_wgrad(d, WgradCall{cv, 0, nv, cv, true, false}).bias_rows;
+}
 
 extern "C" int sl_conv2d_bwd_weight(const SlConvDesc* d, const void* x, const void* x2, const void* dy, float* dw,
                                     void* workspace, size_t workspace_bytes, sl_stream_t stream) {
-  return sl_conv2d_bwd_weight_ex(d, x, x2, dy, dw, d ? d->Cin : 0, 0, workspace, workspace_bytes, stream);
+  return bwd_weight(d, {x, x2, dy, dw, workspace, workspace_bytes, nullptr, nullptr, (hipStream_t)stream, {d ? d->Cin : 0, 0, 0, 0}});
 }
-// dw may be a wider OIHW tensor [Cout][dw_cin_total][KH][KW]; this conv's Cin channels land at input-channel offset dw_ci_off
-static int bwd_weight_impl(const SlConvDesc* d, const void* x, const void* x2, const void* dy, float* dw, int dw_cin_total,
-                           int dw_ci_off, void* workspace, size_t workspace_bytes, sl_stream_t stream, float* colsum_partial, int n_valid = 0, int c_valid = 0,
-                           SlWgradReduce* defer = nullptr);
-
 extern "C" int sl_conv2d_bwd_weight_ex(const SlConvDesc* d, const void* x, const void* x2, const void* dy, float* dw, int dw_cin_total,
                                        int dw_ci_off, void* workspace, size_t workspace_bytes, sl_stream_t stream) {
-  return bwd_weight_impl(d, x, x2, dy, dw, dw_cin_total, dw_ci_off, workspace, workspace_bytes, stream, nullptr);
+  return bwd_weight(d, {x, x2, dy, dw, workspace, workspace_bytes, nullptr, nullptr, (hipStream_t)stream, {dw_cin_total, dw_ci_off, 0, 0}});
 }
-
-// Weight gradient + bias gradient partials of one nn.Linear / biased conv: colsum_partial [sl_colsum_rows_blocks(B*Ho*Wo, Cout, dtype)][Cout] receives the column sums of dy
-// per row chunk (finalize: sl_colsum_finalize / _multi).  1x1 layers on the tile kernels carry them in the slab-reduce launch; other shapes run the separate kernel.
+// Weight gradient + bias gradient partials of one nn.Linear / biased conv: colsum_partial [sl_conv2d_bwd_weight_bias_rows(d, 0, 0)][Cout] receives the column sums of dy
+// per row chunk (finalize: sl_colsum_finalize / _multi).  Where they are made is the plan's WgradBias.
 extern "C" int sl_conv2d_bwd_weight_bias(const SlConvDesc* d, const void* x, const void* x2, const void* dy, float* dw, void* workspace, size_t workspace_bytes,
                                          float* colsum_partial, sl_stream_t stream) {
   SL_REQUIRE(colsum_partial, "conv bwd_weight_bias: null partial buffer");
-  return bwd_weight_impl(d, x, x2, dy, dw, d ? d->Cin : 0, 0, workspace, workspace_bytes, stream, colsum_partial);
+  return bwd_weight(d, {x, x2, dy, dw, workspace, workspace_bytes, colsum_partial, nullptr, (hipStream_t)stream, {d ? d->Cin : 0, 0, 0, 0}});
 }
-
 // The same at zero-padded channel counts: the problem is d->Cout x d->Cin (multiples of 64), dw is the parameter's own [n_valid][c_valid][KH][KW]; colsum_partial may be null.
 extern "C" int sl_conv2d_bwd_weight_clip(const SlConvDesc* d, const void* x, const void* x2, const void* dy, float* dw, int n_valid, int c_valid, void* workspace,
                                          size_t workspace_bytes, float* colsum_partial, sl_stream_t stream) {
   SL_REQUIRE(d && n_valid > 0 && c_valid > 0 && n_valid <= d->Cout && c_valid <= d->Cin, "conv bwd_weight_clip: bad valid channel counts");
-  return bwd_weight_impl(d, x, x2, dy, dw, c_valid, 0, workspace, workspace_bytes, stream, colsum_partial, n_valid, c_valid);
+  return bwd_weight(d, {x, x2, dy, dw, workspace, workspace_bytes, colsum_partial, nullptr, (hipStream_t)stream, {c_valid, 0, n_valid, c_valid}});
 }
-
 // sl_conv2d_bwd_weight_clip with the slab reduce DEFERRED: item receives what is left to do (item->splits == 0: nothing -- this shape's path reduced by itself); the workspace
 // must stay untouched until sl_wgrad_reduce_multi has run (one workspace per deferred layer).
 extern "C" int sl_conv2d_bwd_weight_defer(const SlConvDesc* d, const void* x, const void* x2, const void* dy, float* dw, int n_valid, int c_valid, void* workspace,
                                           size_t workspace_bytes, float* colsum_partial, SlWgradReduce* item, sl_stream_t stream) {
   SL_REQUIRE(d && item && n_valid >= 0 && c_valid >= 0 && n_valid <= d->Cout && c_valid <= d->Cin, "conv bwd_weight_defer: bad arguments");
-  return bwd_weight_impl(d, x, x2, dy, dw, c_valid > 0 ? c_valid : d->Cin, 0, workspace, workspace_bytes, stream, colsum_partial, n_valid, c_valid, item);
+  return bwd_weight(d, {x, x2, dy, dw, workspace, workspace_bytes, colsum_partial, item, (hipStream_t)stream, {c_valid > 0 ? c_valid : d->Cin, 0, n_valid, c_valid}});
 }
 
 extern "C" int sl_wgrad_reduce_multi(const SlWgradReduce* items, int n, sl_stream_t stream) {
@@ -1072,145 +1205,4 @@ extern "C" int sl_wgrad_reduce_multi(const SlWgradReduce* items, int n, sl_strea
   hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b);
   SL_LAUNCH_CHECK("wgrad_reduce_multi_kernel");
   return 0;
-}
-
-// Does the weight-gradient kernel of this shape carry the bias-gradient partials itself (BIAS instantiation: one row per split, two for pixel pairs)?
-static bool wgrad_bias_fused(const SlConvDesc* d, const WgradPlan& pl) {      // test hook sl_debug_wgrad_bias(0): the column sums of dy back in the reduce launch
-  return g_sl_debug.wgrad_bias && pl.glds && pl.taps == 1 && !(pl.bnn == 256 && pl.bcc == 256) && use_tr();
-}
-extern "C" int sl_colsum_rows_blocks(long long rows, int C, int dtype);
-// rows of the colsum_partial buffer sl_conv2d_bwd_weight_bias / _clip (n_valid, c_valid: 0 = all channels) fill: the same path selection as bwd_weight_impl
-extern "C" int sl_conv2d_bwd_weight_bias_rows(const SlConvDesc* d, int n_valid, int c_valid) {
-  if (!d || d->Cout % 64 || d->Cin % 64) { sl_set_error("conv bwd_weight_bias_rows: null descriptor or channel counts that are not multiples of 64"); return SL_EINVAL; }
-  const int generic = sl_colsum_rows_blocks((long long)d->B * d->Ho * d->Wo, d->Cout, d->dtype);
-  const bool full = (n_valid <= 0 || n_valid == d->Cout) && (c_valid <= 0 || c_valid == d->Cin);
-  if (use_tr() && ((full && c64k3_eligible(d, d->Cin, 0)) || c64p_eligible(d) || (full && sl_wgrad3_eligible(d, nullptr)))) return generic;
-  const WgradPlan pl = plan(d);
-  return wgrad_bias_fused(d, pl) ? pl.splits * (pl.pair ? 2 : 1) : generic;
-}
-
-static int bwd_weight_impl(const SlConvDesc* d, const void* x, const void* x2, const void* dy, float* dw, int dw_cin_total,
-                           int dw_ci_off, void* workspace, size_t workspace_bytes, sl_stream_t stream, float* colsum_partial, int n_valid, int c_valid, SlWgradReduce* defer) {
-  SL_REQUIRE(d && x && dy && dw && workspace, "conv bwd_weight: null buffer");
-  if (defer) defer->splits = 0;           // 0 = nothing left to do (this path ran its own reduce)
-  const int nv = n_valid > 0 ? n_valid : d->Cout, cv = c_valid > 0 ? c_valid : d->Cin;
-  SL_REQUIRE(nv <= d->Cout && cv <= d->Cin, "conv bwd_weight: valid channel counts exceed the (padded) problem");
-  // column sums of dy by the stand-alone kernel: every path below that does not carry them in its reduce launch
-  // the caller sized colsum_partial by sl_conv2d_bwd_weight_bias_rows, a second statement of the path selection below: every path checks that the rows it is about to
-  // write are the rows that query promised (round-5 advisor: the two must not drift apart silently)
-  const int promised_rows = colsum_partial ? sl_conv2d_bwd_weight_bias_rows(d, n_valid, c_valid) : 0;
-  auto colsum_separately = [&]() -> int {
-    if (!colsum_partial) return 0;
-    SL_REQUIRE(sl_colsum_rows_blocks((long long)d->B * d->Ho * d->Wo, d->Cout, d->dtype) == promised_rows, "conv bwd_weight: bias partial rows (stand-alone pass) != sl_conv2d_bwd_weight_bias_rows (%d)", promised_rows);
-    return sl_colsum_rows_partial(d->dtype, dy, (long long)d->B * d->Ho * d->Wo, d->Cout, colsum_partial, stream);
-  };
-  // the fixed-order slab reduces follow their MFMA kernel on the same stream (on a second stream they measured slower inside the captured step:
-  // profiles/r3_ab_switches.txt, 27.10 vs 26.53 ms -- every fork / join is a pair of cross-branch dependencies in the graph)
-  SL_REQUIRE(dw_ci_off >= 0 && dw_ci_off + cv <= dw_cin_total, "conv bwd_weight: bad dw channel window");
-  const int bke = d->dtype == SL_BF16 ? 64 : 32;
-  const int c2 = d->Cin - d->C1;
-  SL_REQUIRE(d->dtype == SL_BF16 || d->dtype == SL_F32, "conv bwd_weight: bad dtype");
-  SL_REQUIRE(d->Cout % 64 == 0 && d->C1 % 64 == 0 && c2 % 64 == 0, "conv bwd_weight: channels must be multiples of 64 (Cout %d, C1 %d, C2 %d)", d->Cout, d->C1, c2);
-  (void)bke;
-  SL_REQUIRE(c2 == 0 || x2, "conv bwd_weight: x2 missing");
-  if (c64k3_eligible(d, dw_cin_total, dw_ci_off) && use_tr() && nv == d->Cout && cv == d->Cin) {
-    const int nblk = c64k3_blocks(d), ntiles = d->B * cdiv(d->H, C3_T) * cdiv(d->W, C3_T);
-    const size_t need = (size_t)(nblk + 1) * 64 * 64 * 9 * sizeof(float);         // nblk slabs + their sum
-    if (workspace_bytes < need) { sl_set_error("conv bwd_weight: workspace %zu < %zu", workspace_bytes, need); return SL_EWORKSPACE; }
-    const size_t lds = (size_t)(C3_PW * C3_PW + 256) * C3_PITCH;
-    static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv_wgrad_c64k3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
-    hipLaunchKernelGGL(conv_wgrad_c64k3_kernel, dim3(nblk), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)dy, (float*)workspace, d->B, d->H, d->W, ntiles);
-    SL_LAUNCH_CHECK("conv_wgrad_c64k3_kernel");
-    float* sum = (float*)workspace + (size_t)nblk * 64 * 64 * 9;
-    hipStream_t rs = (hipStream_t)stream;
-    if (int e = sl_colsum_finalize((const float*)workspace, nblk, 64 * 64 * 9, sum, (sl_stream_t)rs)) return e;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(64), dim3(256), 0, rs, (const float*)sum, dw, 64, 64, 9, 1, 64, 0, 64, 64);      // [n][tap][c] -> OIHW
-    SL_LAUNCH_CHECK("wgrad_reduce_kernel");
-    return colsum_separately();
-  }
-  if (c64p_eligible(d) && use_tr()) {
-    const int nblk = c64p_blocks(d), nslab = c64p_slabs(d), ntiles = (int)((long long)d->B * d->H * d->W / CP_T);
-    const size_t need = (size_t)(nslab + 1) * d->Cout * d->Cin * sizeof(float);       // the slabs + their sum
-    if (workspace_bytes < need) { sl_set_error("conv bwd_weight: workspace %zu < %zu", workspace_bytes, need); return SL_EWORKSPACE; }
-    const size_t lds = (size_t)CP_T * (2 * (d->Cout + d->Cin) + 128);
-    hipStream_t st = (hipStream_t)stream;
-#define SL_C64P(CA, CB) do { static bool attr_set = false; \
-      if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv_wgrad_c64p_kernel<CA, CB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; } \
-      hipLaunchKernelGGL((conv_wgrad_c64p_kernel<CA, CB>), dim3(nblk), dim3(256), lds, st, (const bf16_t*)x, (const bf16_t*)dy, (float*)workspace, ntiles); } while (0)
-    if (d->Cout == 256) SL_C64P(256, 64); else if (d->Cin == 256) SL_C64P(64, 256); else if (d->Cout == 128) SL_C64P(128, 128); else SL_C64P(64, 64);
-#undef SL_C64P
-    SL_LAUNCH_CHECK("conv_wgrad_c64p_kernel");
-    const long long total = (long long)d->Cout * d->Cin;
-    float* sum = (float*)workspace + (size_t)nslab * total;
-    hipStream_t rs = (hipStream_t)stream;
-    if (int e = sl_colsum_finalize((const float*)workspace, nslab, (int)total, sum, (sl_stream_t)rs)) return e;          // fixed-order column sums over the slabs (one block per 64 numbers)
-    hipLaunchKernelGGL(wgrad_reduce_flat_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, rs, (const float*)sum, dw, total, 1, d->Cin, dw_cin_total, dw_ci_off, nv, cv);
-    SL_LAUNCH_CHECK("wgrad_reduce_flat_kernel");
-    return colsum_separately();
-  }
-  // 3x3 stride-1 layers with >= 128 x 64 channels: all nine taps from one pass over dy and x (conv_wgrad3.hip)
-  if (use_tr() && nv == d->Cout && cv == d->Cin && sl_wgrad3_eligible(d, nullptr)) {
-    if (int e = sl_wgrad3_run(d, x, x2, dy, dw, dw_cin_total, dw_ci_off, workspace, workspace_bytes, (hipStream_t)stream)) return e;
-    return colsum_separately();
-  }
-  const WgradPlan pl = plan(d);
-  if (workspace_bytes < pl.ws_bytes) { sl_set_error("conv bwd_weight: workspace %zu < %zu", workspace_bytes, pl.ws_bytes); return SL_EWORKSPACE; }
-  WgradParams p{};
-  p.src1 = x; p.src2 = x2; p.C1 = d->C1; p.C2 = c2; p.dy = dy; p.ws = (float*)workspace;
-  p.B = d->B; p.H = d->H; p.W = d->W; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-  p.M = d->B * d->Ho * d->Wo; p.rows_per_split = pl.rows_per_split;
-  p.gridN = pl.gridN; p.gridC = pl.gridC; p.taps = pl.taps; p.splits = pl.splits;
-  p.pair = pl.pair ? 1 : 0;
-  p.trace = g_sl_debug.wgrad_trace;
-  if (pl.pair) { p.Cout = 2 * d->Cout; p.C1 = 2 * d->Cin; p.M /= 2; }
-  const bool bias_fused = colsum_partial && wgrad_bias_fused(d, pl);
-  if (bias_fused) SL_REQUIRE(pl.splits * (pl.pair ? 2 : 1) == promised_rows, "conv bwd_weight: bias partial rows (in-kernel) != sl_conv2d_bwd_weight_bias_rows (%d)", promised_rows);
-  if (bias_fused) { p.colsum = colsum_partial; p.colsum_cout = d->Cout; colsum_partial = nullptr; }      // the kernel writes the partials; nothing left for the reduce launch
-  hipStream_t st = (hipStream_t)stream;
-  int e;
-  if (d->dtype == SL_F32) e = launch_wgrad<float, false>(pl, p, st);
-  else if (use_tr()) e = launch_wgrad<bf16_t, true>(pl, p, st);
-  else e = launch_wgrad<bf16_t, false>(pl, p, st);
-  if (e) return e;
-  SL_REQUIRE(pl.taps <= 49, "conv bwd_weight: kernel window larger than 7x7");
-  if (pl.pair) {
-    const long long total = (long long)d->Cout * d->Cin * pl.taps;
-    hipLaunchKernelGGL(wgrad_reduce_pair_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float*)workspace, dw, d->Cout, d->Cin, pl.taps, pl.splits, dw_cin_total, dw_ci_off, nv, cv);
-  } else if (pl.taps == 1) {
-    const long long total = (long long)d->Cout * d->Cin;
-    const int nred = (int)((total + 255) / 256);
-    if (defer) {
-      // the flat slab reduce (and the column sums of dy that would ride in it) joins the caller's batch: sl_wgrad_reduce_multi runs it with the other layers' reduces
-      defer->ws = (const float*)workspace; defer->dw = dw; defer->total = total; defer->splits = pl.splits; defer->Cin = d->Cin; defer->dw_cin_total = dw_cin_total;
-      defer->dw_ci_off = dw_ci_off; defer->n_valid = nv; defer->c_valid = cv; defer->dtype = d->dtype; defer->dy = nullptr; defer->colsum_part = nullptr; defer->ncol = 0;
-      defer->rows = 0; defer->Cout = d->Cout; defer->rows_per_block = 0;
-      if (colsum_partial) {
-        const long long rows = (long long)d->B * d->Ho * d->Wo, ch = sl_colsum_rows_chunk(rows, d->Cout, d->dtype == SL_BF16 ? 2 : 4);
-        const int ncol = (int)((rows + ch - 1) / ch);
-        SL_REQUIRE(ncol == promised_rows, "conv bwd_weight: bias partial rows (deferred reduce) != sl_conv2d_bwd_weight_bias_rows (%d)", promised_rows);
-        defer->dy = dy; defer->rows = rows; defer->rows_per_block = ch; defer->colsum_part = colsum_partial; defer->ncol = ncol;
-      }
-      return 0;
-    }
-    if (colsum_partial) {
-      const long long rows = (long long)d->B * d->Ho * d->Wo, ch = sl_colsum_rows_chunk(rows, d->Cout, d->dtype == SL_BF16 ? 2 : 4);
-      const int ncol = (int)((rows + ch - 1) / ch);
-      SL_REQUIRE(ncol == promised_rows, "conv bwd_weight: bias partial rows (reduce launch) != sl_conv2d_bwd_weight_bias_rows (%d)", promised_rows);
-      if (d->dtype == SL_BF16)
-        hipLaunchKernelGGL(wgrad_reduce_flat_colsum_kernel<bf16_t>, dim3(nred + ncol), dim3(256), 0, st, (const float*)workspace, dw, total, pl.splits, d->Cin, dw_cin_total, dw_ci_off,
-                           nred, (const bf16_t*)dy, rows, d->Cout, ch, colsum_partial, nv, cv);
-      else
-        hipLaunchKernelGGL(wgrad_reduce_flat_colsum_kernel<float>, dim3(nred + ncol), dim3(256), 0, st, (const float*)workspace, dw, total, pl.splits, d->Cin, dw_cin_total, dw_ci_off,
-                           nred, (const float*)dy, rows, d->Cout, ch, colsum_partial, nv, cv);
-      SL_LAUNCH_CHECK("wgrad_reduce_flat_colsum_kernel");
-        return 0;
-    }
-    hipLaunchKernelGGL(wgrad_reduce_flat_kernel, dim3((unsigned)nred), dim3(256), 0, st, (const float*)workspace, dw, total, pl.splits, d->Cin, dw_cin_total, dw_ci_off, nv, cv);
-  } else {
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(d->Cout * (d->Cin / 64)), dim3(256), 0, st, (const float*)workspace, dw, d->Cout, d->Cin, pl.taps, pl.splits, dw_cin_total, dw_ci_off, nv, cv);
-  }
-  SL_LAUNCH_CHECK("wgrad_reduce_kernel");
-  return colsum_separately();
 }

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
+#include "conv_wgrad3.h"
 
 namespace {
 
@@ -275,7 +276,7 @@ __global__ __launch_bounds__(576) void wgrad3_reduce_kernel(const float* __restr
   *(f32x4_t*)o = *(const f32x4_t*)(tilebuf + row * 288 + k4 * 4);
 }
 
-struct Wg3Plan { int ok, d, Hs, Ws, nstrips, L, SP, ppu, pieces, ppb, splits, tilesN, tilesC; size_t ws_bytes; };
+}  // namespace
 
 Wg3Plan wg3_plan(const SlConvDesc* d) {
   Wg3Plan pl{};
@@ -315,8 +316,6 @@ Wg3Plan wg3_plan(const SlConvDesc* d) {
   return pl;
 }
 
-}  // namespace
-
 // test hook (include/segland_hip_debug.h): the plan of a shape: out[0..7] = {served, pieces per strip, rows per piece, steps per piece, pieces per block, splits, tiles, blocks}
 extern "C" int sl_debug_wgrad3_plan(const SlConvDesc* d, int* out) {
   const Wg3Plan pl = wg3_plan(d);
@@ -324,18 +323,8 @@ extern "C" int sl_debug_wgrad3_plan(const SlConvDesc* d, int* out) {
   return pl.ok;
 }
 
-// internal (conv_wgrad.hip): does the nine-tap kernel take this layer, and with how much workspace
-bool sl_wgrad3_eligible(const SlConvDesc* d, size_t* ws_bytes) {
-  const Wg3Plan pl = wg3_plan(d);
-  if (ws_bytes) *ws_bytes = pl.ok ? pl.ws_bytes : 0;
-  return pl.ok != 0;
-}
-
-int sl_wgrad3_run(const SlConvDesc* d, const void* x, const void* x2, const void* dy, float* dw, int dw_cin_total, int dw_ci_off, void* workspace, size_t workspace_bytes,
-                  hipStream_t st) {
-  const Wg3Plan pl = wg3_plan(d);
+int sl_wgrad3_run(const SlConvDesc* d, const Wg3Plan& pl, const void* x, const void* x2, const void* dy, float* dw, int dw_cin_total, int dw_ci_off, void* workspace, hipStream_t st) {
   SL_REQUIRE(pl.ok, "conv bwd_weight (nine-tap kernel): shape not served");
-  if (workspace_bytes < pl.ws_bytes) { sl_set_error("conv bwd_weight: workspace %zu < %zu", workspace_bytes, pl.ws_bytes); return SL_EWORKSPACE; }
   SL_REQUIRE(dw_cin_total % 4 == 0 && dw_ci_off % 4 == 0, "conv bwd_weight: dw channel window must be 4-aligned");
   Wg3Params p{};
   p.x1 = (const bf16_t*)x; p.x2 = (const bf16_t*)x2; p.C1 = d->C1; p.C2 = d->Cin - d->C1; p.dy = (const bf16_t*)dy; p.Cout = d->Cout; p.ws = (float*)workspace;

@@ -50,6 +50,14 @@ def _f32(n, dev, zero=False):
 EPI_STATS, EPI_AFFINE, EPI_ADDEND, EPI_ADDEND_BITS, EPI_GATE, EPI_SPLITK, EPI_GELU = 1, 2, 4, 8, 16, 32, 64      # SL_EPI_* of include/segland_hip.h
 
 
+def wgrad_config(cfg):
+    """A code of sl_conv2d_wgrad_config (include/segland_hip.h) -> (kernel name, tile rows, tile columns, rows are pixel pairs); the three special kernels have no tile."""
+    special = {1: 'conv_wgrad_c64k3_kernel', 2: 'conv_wgrad_c64p_kernel', 3: 'conv_wgrad3_kernel'}
+    if cfg in special:
+        return special[cfg], 0, 0, False
+    return 'conv_wgrad_glds_kernel' if cfg // 10000000 == 1 else 'conv_wgrad_kernel', (cfg % 500000) // 1000, cfg % 1000, bool((cfg // 500000) % 2)
+
+
 # --------------------------------------------------------------------------------------------- live kernel timing
 class _Profiler:
     """HIP-event timing of the conv launches on the launch stream (bench.py: roofline of the dominant kernel).
@@ -70,16 +78,8 @@ class _Profiler:
     def family(self, kind, d, epi=0):
         if kind == 'conv_wgrad':
             # the kernel rocprofv3 names.  Its deterministic slab reduce (a separate small launch behind it on the same stream) is inside the span
-            cfg = _lib.lib().sl_conv2d_wgrad_config(C.byref(d))
-            dts = 'bf16' if d.dtype == SL_BF16 else 'f32'
-            if cfg == 1:
-                return 'conv_wgrad_c64k3_kernel'
-            if cfg == 2:
-                return 'conv_wgrad_c64p_kernel'
-            if cfg == 3:
-                return 'conv_wgrad3_kernel'
-            name = 'conv_wgrad_glds_kernel' if cfg // 10000000 == 1 else 'conv_wgrad_kernel'
-            return '%s<%s, %d, %d>%s' % (name, dts, (cfg % 500000) // 1000, cfg % 1000, ' pixel pairs' if (cfg // 500000) % 2 else '')
+            name, bn, bc, pair = wgrad_config(_lib.lib().sl_conv2d_wgrad_config(C.byref(d)))
+            return name if not bn else '%s<%s, %d, %d>%s' % (name, 'bf16' if d.dtype == SL_BF16 else 'f32', bn, bc, ' pixel pairs' if pair else '')
         # epi: the SL_EPI_* bits of the launch (the dispatch depends on the epilogue, include/segland_hip.h)
         cfg = _lib.lib().sl_conv2d_tile_config_ex(C.byref(d), 0 if kind == 'conv_fwd' else 1, epi)
         return '%s<%s, %d, %d>%s' % (self.FAMILY.get((cfg // 1000000) % 10, '?'), 'bf16' if d.dtype == SL_BF16 else 'f32', (cfg // 1000) % 1000, cfg % 1000,

@@ -159,3 +159,41 @@ def test_parity_plane_statistic_rows_come_from_the_launch_plan(lib):
     d = _desc(_lib.SL_BF16, 1, 128, 128, 128, 128, 3, 2, 1, 1)
     assert lib.sl_conv2d_tile_config_ex(C.byref(d), 1, GATE) == 4128128
     assert lib.sl_conv2d_bwd_data_bnstat_rows(C.byref(d)) == 128 * 128 // 128
+
+
+WGRAD_PLAN = [
+    # dtype, (B, H, W), Cin, Cout, k, hook set to 0      config code, bias rows at (0, 0), bias rows clipped to (Cout - 32, Cin - 32), workspace bytes
+    (_lib.SL_BF16, (4, 128, 128), 64, 64, 3, None, (1, 128, 128, 37896192)),                          # 64 -> 64 3x3 kernel; bias by the stand-alone pass
+    (_lib.SL_BF16, (4, 128, 128), 64, 256, 1, None, (2, 512, 512, 16842752)),                         # 64-channel 1x1 kernel; stand-alone pass
+    (_lib.SL_BF16, (2, 64, 64), 128, 128, 3, None, (3, 32, 32, 18874368)),                            # nine-tap kernel; stand-alone pass
+    (_lib.SL_BF16, (1, 32, 32), 128, 384, 1, None, (10128128, 8, 8, 1572864)),                        # 128 x 128 tiles, bias inside the kernel: one row per split
+    (_lib.SL_BF16, (1, 32, 32), 128, 384, 1, 'sl_debug_wgrad_bias', (10128128, 13, 13, 1572864)),     # the same with the bias in the slab-reduce launch
+    (_lib.SL_BF16, (1, 32, 32), 512, 768, 1, None, (10256256, 32, 32, 9437184)),                      # 256 x 256 tiles have no bias instantiation: reduce launch
+    (_lib.SL_BF16, (1, 128, 128), 192, 192, 1, None, (10628128, 32, 32, 9437184)),                    # pixel pairs: two rows per split
+    (_lib.SL_BF16, (1, 32, 32), 64, 64, 1, None, (20064064, 2, 2, 131072)),                           # register-staged kernel
+    (_lib.SL_F32, (1, 32, 32), 64, 64, 1, None, (20064064, 4, 4, 131072)),
+]
+
+
+def test_weight_gradient_plan_by_shape(lib):
+    """One shape per route and per bias placement of the weight-gradient plan (csrc/conv_wgrad.hip plan_wgrad: host logic, no launch): what sl_conv2d_wgrad_config,
+    sl_conv2d_bwd_weight_bias_rows and sl_conv2d_bwd_weight_workspace answer.  The literals are those of the build before the queries and the launch shared one plan."""
+    for dtype, (B, H, W), cin, cout, k, hook, want in WGRAD_PLAN:
+        d = _desc(dtype, B, H, W, cin, cout, k, 1, k // 2, 1)
+        r = C.byref(d)
+        if hook:
+            getattr(lib, hook)(0)
+        try:
+            got = (lib.sl_conv2d_wgrad_config(r), lib.sl_conv2d_bwd_weight_bias_rows(r, 0, 0), lib.sl_conv2d_bwd_weight_bias_rows(r, cout - 32, cin - 32),
+                   lib.sl_conv2d_bwd_weight_workspace(r))
+        finally:
+            lib.sl_debug_reset()
+        assert got == want, ((B, H, W), cin, cout, k, hook, got)
+    # a clipped call leaves the nine-tap route: the launch (refused here for its workspace, before anything runs) asks for the slabs of the route it takes
+    d = _desc(_lib.SL_BF16, 2, 64, 64, 128, 128, 3, 1, 1, 1)
+    dummy = C.c_void_p(16)
+    assert lib.sl_conv2d_bwd_weight_bias(C.byref(d), dummy, None, dummy, dummy, dummy, 0, dummy, None) == -2
+    assert lib.sl_last_error_string() == b'conv bwd_weight: workspace 0 < 18874368'
+    assert lib.sl_conv2d_bwd_weight_clip(C.byref(d), dummy, None, dummy, dummy, 96, 96, dummy, 0, dummy, None) == -2
+    assert lib.sl_last_error_string() == b'conv bwd_weight: workspace 0 < 9437184'                  # the 128 x 128 tile kernels' slabs
+    assert lib.sl_conv2d_bwd_weight_bias_rows(C.byref(d), 96, 96) == 32

@@ -26,9 +26,10 @@ gf = 2.0 * a.B * a.hw * a.hw * a.cin * a.cout * a.k * a.k / 1e9
 def run(nine):
     L.sl_debug_wgrad3(1 if nine else 0)
     cfg = L.sl_conv2d_wgrad_config(ctypes.byref(d))
-    if nine and cfg != 3:
+    kernel = ops.wgrad_config(cfg)[0]
+    if nine and kernel != 'conv_wgrad3_kernel':
         print('shape not served by the nine-tap kernel (config %d)' % cfg); return
-    if not nine and cfg < 10000000:
+    if not nine and kernel != 'conv_wgrad_glds_kernel':
         print('shape not on conv_wgrad_glds_kernel (config %d)' % cfg); return
     fn = lambda: ops.conv2d_bwd_weight(x, dy, spec)
     for _ in range(3): fn()
