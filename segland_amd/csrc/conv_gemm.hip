@@ -48,6 +48,17 @@ static bool parity_shape(const ConvGemmParams& p) {
 }
 static long long plane_rows(const ConvGemmParams& p) { return (long long)p.B * (p.Hd / 2) * (p.Wd / 2); }
 
+// Store phases of the pixel-stationary kernel (conv_gemm_sk.hip: launch_sk): plain (+ statistics), + addend (+ its gate bits), gate + addend + BN-backward column sums.
+// The two that stage a block's gate bytes in LDS take N % 128 == 0, N <= 1024.  It is the ONLY kernel that reads addend_half, bn_x2 / stat_partial2, or a gate next to an
+// addend (launch_gemm requires it for those blocks), so the served-queries of the fused data gradients below ask choose_kernel for family 6.
+static bool sk_store_phase(const ConvGemmParams& p) {
+  const bool bits_fit = p.N % 128 == 0 && p.N <= 1024;
+  if (p.gate) return p.addend && !p.addend_mask && p.stat_partial && bits_fit;
+  if (p.addend) return !p.stat_partial && (!p.addend_mask || bits_fit);
+  return !p.addend_mask;
+}
+static bool sk_only_fields(const ConvGemmParams& p) { return p.addend_half || p.bn_x2 || p.stat_partial2 || (p.gate && p.addend); }
+
 // How a launch runs: kernel code cfg = 1000000 * family + 1000 * BM + BN (family 8 = 3x3 patch (+ 10000000: split-K), 7 = 64 -> 64 patch, 6 = pixel-stationary K <= 256,
 // 5 = half-tile, 4 = ring, 3 = <= 32 rows, 2 = two-stage glds); parity: cfg runs as four launches, one per parity plane (parity_shape), instead of one.
 struct Plan {
@@ -55,8 +66,8 @@ struct Plan {
   bool parity;
   Plan(int c, bool par = false) : cfg(c), parity(par) {}
 };
-// The ONE predicate chain: launch_gemm runs its plan, sl_conv2d_tile_config(_ex) reports its cfg, and sl_conv2d_stat_rows / sl_conv2d_bwd_data_bnstat_rows count the
-// partial rows of its launches (stat_rows) -- round 4 found the query drifted from the dispatch.  A parity-plane plan reports the ring code of its planes.
+// The ONE predicate chain: launch_gemm runs its plan, sl_conv2d_tile_config(_ex) reports its cfg, and sl_conv2d_stat_rows and the sl_conv2d_bwd_data_*_rows / _ok
+// served-queries count the partial rows of its launches (stat_rows) -- round 4 found the query drifted from the dispatch.  A parity-plane plan reports the ring code of its planes.
 static Plan choose_kernel(const ConvGemmParams& p, int dtype) {
   const bool n128 = (p.N % 128 == 0), n256 = (p.N % 256 == 0);
   const bool big = block_rows(p.M) == 256;           // tiny problems (PPM stages, prototype rows) stay on 128-row tiles
@@ -71,8 +82,7 @@ static Plan choose_kernel(const ConvGemmParams& p, int dtype) {
         !(p.bias || p.scale || p.relu || p.addend || p.mask_src || p.pre_addend || p.row_scale || p.out2) && (!p.gate || (p.stat_partial && p.bn_x)))
       return 7016016;                                                                  // (round 6: also the gated data gradient with BN-backward column sums)
     if (sk_shape(SL_BF16, p.KH, p.KW, p.stride, p.pad, p.C1 + p.C2, p.C1, p.N, p.M) && p.Hs == p.Hd && p.Ws == p.Wd &&
-        !(p.bias || p.scale || p.relu || p.mask_src || p.pre_addend || p.row_scale || p.out2) && (p.gate || !(p.addend && p.stat_partial)) && (p.addend || !p.addend_mask) &&
-        (!p.gate || (p.addend && !p.addend_mask && p.stat_partial)) && (!(p.addend_mask || p.gate) || (p.N % 128 == 0 && p.N <= 1024)))
+        !(p.bias || p.scale || p.relu || p.mask_src || p.pre_addend || p.row_scale || p.out2) && sk_store_phase(p))
       return 6256064;
     if (p9_shape(p) && !(p.flags & 4)) return 8256256;
     // half-tile kernel: needs the affine row -> pixel map (forward, or data gradient of a stride-1 conv) and <= 32 taps in the mask
@@ -121,6 +131,15 @@ static long long stat_rows(const Plan& pl, const ConvGemmParams& p) {
   return pl.parity ? 4LL * cdiv(plane_rows(p), bm) : cdiv(p.M, bm);
 }
 
+// Does the plan have the gated-statistics store phase (a data gradient gated with the ReLU bits of its own positions + BN-backward column sums)?  The 64 -> 64 3x3
+// kernel, and the tile kernels with the LDS-staged store phase (half-tile, 3x3 patch, ring, two-stage) when every row block is full.  Not the 128 x 192 ring tile: no
+// BatchNorm model exercises it there (192-multiple widths are Swin's LayerNorm layers), so it is not offered.
+static bool gated_stat_phase(const Plan& pl, const ConvGemmParams& p) {
+  if (pl.cfg == 7016016) return true;
+  const int fam = pl.cfg / 1000000, bm = (pl.cfg / 1000) % 1000;
+  return (fam == 5 || fam == 8 || fam == 4 || fam == 2) && bm > 0 && (pl.parity ? plane_rows(p) : p.M) % bm == 0 && pl.cfg % 1000 != 192;
+}
+
 static int launch_parity_planes(const Plan& pl, int dtype, const ConvGemmParams& p, hipStream_t st) {
   const long long Ms = plane_rows(p);
   const int bm = (pl.cfg / 1000) % 1000;
@@ -138,6 +157,7 @@ static int launch_parity_planes(const Plan& pl, int dtype, const ConvGemmParams&
 
 int launch_gemm(int dtype, ConvGemmParams& p, hipStream_t st) {
   const Plan pl = choose_kernel(p, dtype);
+  SL_REQUIRE(!sk_only_fields(p) || pl.cfg == 6256064, "conv: a half-resolution addend, dual statistics or a gate next to an addend need the pixel-stationary kernel, this shape runs on %d", pl.cfg);
   if (pl.parity) return launch_parity_planes(pl, dtype, p, st);
   if (dtype == SL_BF16) {
     switch (pl.cfg) {
@@ -180,24 +200,37 @@ int check_desc(const SlConvDesc* d) {
 // SL_EPI_AFFINE (bias / folded BN / ReLU / residual: the inference forms), SL_EPI_ADDEND (data gradient + shortcut gradient), SL_EPI_ADDEND_BITS (gated by ReLU bits),
 // SL_EPI_GATE (gated result + BN-backward column sums, sl_conv2d_bwd_data_bnstat), SL_EPI_SPLITK (the split-K plan of sl_conv2d_affine_fwd_ex applies).
 // sl_conv2d_tile_config(d, mode) = the training forms: forward with statistics, plain data gradient.
-// The parameter block the entry points would build for this descriptor (mode 0: forward, 1: data gradient; epi: SL_EPI_* as above), dummy buffers where they pass some
-static unsigned char g_cfg_dummy[16];
-static ConvGemmParams query_params(const SlConvDesc* d, int mode, int epi) {
+// The parameter block of a launch for this descriptor -- geometry, mode and M: every entry point and query_params start from one of the two and set only their own fields.
+static ConvGemmParams fwd_params(const SlConvDesc* d) {
   ConvGemmParams p{};
+  p.C1 = d->C1; p.C2 = d->Cin - d->C1; p.B = d->B; p.Hs = d->H; p.Ws = d->W; p.Hd = d->Ho; p.Wd = d->Wo; p.N = d->Cout; p.M = d->B * d->Ho * d->Wo;
+  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.mode = 0;
+  return p;
+}
+static ConvGemmParams dgrad_params(const SlConvDesc* d) {
+  ConvGemmParams p{};
+  p.C1 = d->Cout; p.C2 = 0; p.B = d->B; p.Hs = d->Ho; p.Ws = d->Wo; p.Hd = d->H; p.Wd = d->W; p.N = d->Cin; p.M = d->B * d->H * d->W;
+  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.mode = 1;
+  return p;
+}
+static void gated_stats(ConvGemmParams& p, const uint8_t* gate, const void* bn_x, const float* bn_mean, const float* bn_invstd, float* stat_partial) {
+  p.gate = gate; p.bn_x = bn_x; p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.stat_partial = stat_partial;
+}
+
+// The parameter block the entry points would build for this descriptor (mode 0: forward, 1: data gradient; epi: SL_EPI_* as above; addend_half: the addend is the
+// half-resolution one of sl_conv2d_bwd_data_addend_half), dummy buffers where they pass some
+static unsigned char g_cfg_dummy[16];
+static ConvGemmParams query_params(const SlConvDesc* d, int mode, int epi, int addend_half = 0) {
+  ConvGemmParams p = mode == 0 ? fwd_params(d) : dgrad_params(d);
   void* dm = (void*)g_cfg_dummy;
   p.src1 = dm; p.wt = dm; p.out = dm;
-  if (mode == 0) {
-    p.C1 = d->C1; p.C2 = d->Cin - d->C1; p.B = d->B; p.Hs = d->H; p.Ws = d->W; p.Hd = d->Ho; p.Wd = d->Wo; p.N = d->Cout; p.M = d->B * d->Ho * d->Wo;
-  } else {
-    p.C1 = d->Cout; p.C2 = 0; p.B = d->B; p.Hs = d->Ho; p.Ws = d->Wo; p.Hd = d->H; p.Wd = d->W; p.N = d->Cin; p.M = d->B * d->H * d->W;
-  }
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.mode = mode;
   if (epi & SL_EPI_STATS) p.stat_partial = (float*)dm;
   if (epi & SL_EPI_AFFINE) { p.scale = (const float*)dm; p.bias = (const float*)dm; p.relu = 1; }
   if (epi & (SL_EPI_ADDEND | SL_EPI_ADDEND_BITS)) p.addend = dm;
   if (epi & SL_EPI_ADDEND_BITS) p.addend_mask = (const unsigned char*)dm;
-  if (epi & SL_EPI_GATE) { p.gate = (const unsigned char*)dm; p.bn_x = dm; p.bn_mean = (const float*)dm; p.bn_invstd = (const float*)dm; p.stat_partial = (float*)dm; }
+  if (epi & SL_EPI_GATE) gated_stats(p, (const uint8_t*)dm, dm, (const float*)dm, (const float*)dm, (float*)dm);
   if (epi & SL_EPI_GELU) { p.mask_src = dm; p.flags = 4; }
+  p.addend_half = addend_half;
   p.ksplit = (epi & SL_EPI_SPLITK) ? splitk_parts(p, d->dtype) : 1;
   return p;
 }
@@ -216,26 +249,20 @@ extern "C" int sl_conv2d_stat_rows(const SlConvDesc* d) {
 }
 
 extern "C" int sl_conv2d_fwd_ex(const SlConvDesc* d, const void* x, const void* x2, const void* w, const void* pre_addend,
-                                const float* bias, int relu, void* y, float* stat_partial, sl_stream_t stream);
-
-extern "C" int sl_conv2d_fwd(const SlConvDesc* d, const void* x, const void* x2, const void* w, const float* bias,
-                             int relu, void* y, float* stat_partial, sl_stream_t stream) {
-  return sl_conv2d_fwd_ex(d, x, x2, w, nullptr, bias, relu, y, stat_partial, stream);
-}
-
-extern "C" int sl_conv2d_fwd_ex(const SlConvDesc* d, const void* x, const void* x2, const void* w, const void* pre_addend,
                                 const float* bias, int relu, void* y, float* stat_partial, sl_stream_t stream) {
   if (int e = check_desc(d)) return e;
   SL_REQUIRE(x && w && y, "conv fwd: null buffer");
   SL_REQUIRE(d->C1 == d->Cin || x2, "conv fwd: x2 missing for a concat input");
   SL_REQUIRE(!(stat_partial && (bias || relu)), "conv fwd: statistics are defined on the raw conv output");
-  ConvGemmParams p{};
-  p.src1 = x; p.src2 = x2; p.C1 = d->C1; p.C2 = d->Cin - d->C1; p.wt = w; p.out = y;
-  p.B = d->B; p.Hs = d->H; p.Ws = d->W; p.Hd = d->Ho; p.Wd = d->Wo;
-  p.N = d->Cout; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.mode = 0;
+  ConvGemmParams p = fwd_params(d);
+  p.src1 = x; p.src2 = x2; p.wt = w; p.out = y;
   p.bias = bias; p.relu = relu; p.stat_partial = stat_partial; p.pre_addend = pre_addend;
-  p.M = d->B * d->Ho * d->Wo;
   return run_gemm(d->dtype, p, (hipStream_t)stream);
+}
+
+extern "C" int sl_conv2d_fwd(const SlConvDesc* d, const void* x, const void* x2, const void* w, const float* bias,
+                             int relu, void* y, float* stat_partial, sl_stream_t stream) {
+  return sl_conv2d_fwd_ex(d, x, x2, w, nullptr, bias, relu, y, stat_partial, stream);
 }
 
 // nn.Linear as a 1x1 conv with the elementwise tail of a transformer block in the epilogue:
@@ -246,37 +273,16 @@ extern "C" int sl_linear_fwd(const SlConvDesc* d, const void* x, const void* w, 
   if (int e = check_desc(d)) return e;
   SL_REQUIRE(x && w && y, "linear fwd: null buffer");
   SL_REQUIRE(d->C1 == d->Cin, "linear fwd: single input tensor");
-  ConvGemmParams p{};
-  p.src1 = x; p.src2 = nullptr; p.C1 = d->C1; p.C2 = 0; p.wt = w; p.out = y;
-  p.B = d->B; p.Hs = d->H; p.Ws = d->W; p.Hd = d->Ho; p.Wd = d->Wo;
-  p.N = d->Cout; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.mode = 0;
+  ConvGemmParams p = fwd_params(d);
+  p.src1 = x; p.wt = w; p.out = y;
   p.bias = bias; p.row_scale = row_scale; p.addend = residual; p.out2 = gelu_out;
-  p.M = d->B * d->Ho * d->Wo;
   return run_gemm(d->dtype, p, (hipStream_t)stream);
-}
-
-static void affine_params(ConvGemmParams& p, const SlConvDesc* d, const void* x, const void* x2, const void* w, const void* pre_addend, const float* scale,
-                          const float* shift, const void* residual, int relu, void* y) {
-  p.src1 = x; p.src2 = x2; p.C1 = d->C1; p.C2 = d->Cin - d->C1; p.wt = w; p.out = y;
-  p.B = d->B; p.Hs = d->H; p.Ws = d->W; p.Hd = d->Ho; p.Wd = d->Wo;
-  p.N = d->Cout; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.mode = 0;
-  p.scale = scale; p.bias = shift; p.relu = relu; p.addend = residual; p.pre_addend = pre_addend;
-  p.M = d->B * d->Ho * d->Wo;
-}
-
-extern "C" int sl_conv2d_affine_fwd_ex(const SlConvDesc* d, const void* x, const void* x2, const void* w, const void* pre_addend, const float* scale,
-                                       const float* shift, const void* residual, int relu, void* y, void* workspace, size_t workspace_bytes, sl_stream_t stream);
-
-extern "C" int sl_conv2d_affine_fwd(const SlConvDesc* d, const void* x, const void* x2, const void* w, const float* scale,
-                                    const float* shift, const void* residual, int relu, void* y, sl_stream_t stream) {
-  return sl_conv2d_affine_fwd_ex(d, x, x2, w, nullptr, scale, shift, residual, relu, y, nullptr, 0, stream);
 }
 
 // bytes of split-K workspace sl_conv2d_affine_fwd_ex can use for this layer (0: the layer is not split)
 extern "C" size_t sl_conv2d_affine_fwd_workspace(const SlConvDesc* d) {
   if (!d || check_desc(d)) return 0;
-  ConvGemmParams p{};
-  affine_params(p, d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+  const ConvGemmParams p = fwd_params(d);
   const int parts = splitk_parts(p, d->dtype);
   return parts > 1 ? (size_t)parts * p.M * p.N * sizeof(float) : 0;
 }
@@ -286,23 +292,26 @@ extern "C" int sl_conv2d_affine_fwd_ex(const SlConvDesc* d, const void* x, const
   if (int e = check_desc(d)) return e;
   SL_REQUIRE(x && w && y && scale && shift, "conv affine fwd: null buffer");
   SL_REQUIRE(d->C1 == d->Cin || x2, "conv affine fwd: x2 missing for a concat input");
-  ConvGemmParams p{};
-  affine_params(p, d, x, x2, w, pre_addend, scale, shift, residual, relu, y);
+  ConvGemmParams p = fwd_params(d);
+  p.src1 = x; p.src2 = x2; p.wt = w; p.out = y;
+  p.scale = scale; p.bias = shift; p.relu = relu; p.addend = residual; p.pre_addend = pre_addend;
   const int parts = workspace ? splitk_parts(p, d->dtype) : 1;
   if (parts > 1 && workspace_bytes >= (size_t)parts * p.M * p.N * sizeof(float) && ((size_t)workspace & 15) == 0) { p.ws = (float*)workspace; p.ksplit = parts; }
   return run_gemm(d->dtype, p, (hipStream_t)stream);
+}
+
+extern "C" int sl_conv2d_affine_fwd(const SlConvDesc* d, const void* x, const void* x2, const void* w, const float* scale,
+                                    const float* shift, const void* residual, int relu, void* y, sl_stream_t stream) {
+  return sl_conv2d_affine_fwd_ex(d, x, x2, w, nullptr, scale, shift, residual, relu, y, nullptr, 0, stream);
 }
 
 extern "C" int sl_conv2d_bwd_data(const SlConvDesc* d, const void* dy, const void* wt, const void* addend, const uint8_t* addend_mask,
                                   const void* mask_src, void* dx, sl_stream_t stream) {
   if (int e = check_desc(d)) return e;
   SL_REQUIRE(dy && wt && dx, "conv bwd_data: null buffer");
-  ConvGemmParams p{};
-  p.src1 = dy; p.src2 = nullptr; p.C1 = d->Cout; p.C2 = 0; p.wt = wt; p.out = dx;
-  p.B = d->B; p.Hs = d->Ho; p.Ws = d->Wo; p.Hd = d->H; p.Wd = d->W;
-  p.N = d->Cin; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.mode = 1;
+  ConvGemmParams p = dgrad_params(d);
+  p.src1 = dy; p.wt = wt; p.out = dx;
   p.addend = addend; p.mask_src = mask_src; p.addend_mask = addend ? addend_mask : nullptr;
-  p.M = d->B * d->H * d->W;
   return run_gemm(d->dtype, p, (hipStream_t)stream);
 }
 
@@ -311,27 +320,20 @@ extern "C" int sl_conv2d_bwd_data(const SlConvDesc* d, const void* dy, const voi
 extern "C" int sl_conv2d_bwd_data_gelu(const SlConvDesc* d, const void* dy, const void* wt, const void* h, void* dx, sl_stream_t stream) {
   if (int e = check_desc(d)) return e;
   SL_REQUIRE(dy && wt && h && dx, "conv bwd_data_gelu: null buffer");
-  ConvGemmParams p{};
-  p.src1 = dy; p.src2 = nullptr; p.C1 = d->Cout; p.C2 = 0; p.wt = wt; p.out = dx;
-  p.B = d->B; p.Hs = d->Ho; p.Ws = d->Wo; p.Hd = d->H; p.Wd = d->W;
-  p.N = d->Cin; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.mode = 1;
+  ConvGemmParams p = dgrad_params(d);
+  p.src1 = dy; p.wt = wt; p.out = dx;
   p.mask_src = h; p.flags = 4;
-  p.M = d->B * d->H * d->W;
   return run_gemm(d->dtype, p, (hipStream_t)stream);
 }
 
 // Data gradient whose result is gated with the ReLU bits of its own positions and reduced for the BatchNorm backward of the layer below (see ConvGemmParams::gate).
 // rows of stat_partial: sl_conv2d_bwd_data_bnstat_rows(d), 0 = this shape is not served (the caller runs sl_conv2d_bwd_data + sl_bn_bwd_reduce instead): served are the
-// shapes that the tile kernels with the LDS-staged store phase take (half-tile, 3x3 patch, ring, two-stage) when every row block is full.
+// plans with the gated-statistics store phase (gated_stat_phase).
 extern "C" int sl_conv2d_bwd_data_bnstat_rows(const SlConvDesc* d) {
   if (!d) return 0;
   const ConvGemmParams p = query_params(d, 1, SL_EPI_GATE);
   const Plan pl = choose_kernel(p, d->dtype);
-  const int fam = pl.cfg / 1000000, bm = (pl.cfg / 1000) % 1000;
-  if (pl.cfg == 7016016) return (int)stat_rows(pl, p);                  // conv_c64k3_kernel: one row per 16 x 16 tile (as the forward's statistics)
-  if (!(fam == 5 || fam == 8 || fam == 4 || fam == 2) || bm <= 0 || (pl.parity ? plane_rows(p) : p.M) % bm != 0) return 0;
-  if (pl.cfg % 1000 == 192) return 0;      // the 128 x 192 ring tile's gated-statistics store phase is not exercised by any BatchNorm model (192-multiple widths are Swin's LayerNorm layers): not offered
-  return (int)stat_rows(pl, p);
+  return gated_stat_phase(pl, p) ? (int)stat_rows(pl, p) : 0;
 }
 
 extern "C" int sl_conv2d_bwd_data_bnstat(const SlConvDesc* d, const void* dy, const void* wt, const uint8_t* gate, const void* bn_x, const float* bn_mean,
@@ -339,24 +341,24 @@ extern "C" int sl_conv2d_bwd_data_bnstat(const SlConvDesc* d, const void* dy, co
   if (int e = check_desc(d)) return e;
   SL_REQUIRE(dy && wt && dx && gate && bn_x && bn_mean && bn_invstd && stat_partial, "conv bwd_data_bnstat: null buffer");
   SL_REQUIRE(sl_conv2d_bwd_data_bnstat_rows(d) > 0, "conv bwd_data_bnstat: shape not served (sl_conv2d_bwd_data_bnstat_rows == 0)");
-  ConvGemmParams p{};
-  p.src1 = dy; p.src2 = nullptr; p.C1 = d->Cout; p.C2 = 0; p.wt = wt; p.out = dx;
-  p.B = d->B; p.Hs = d->Ho; p.Ws = d->Wo; p.Hd = d->H; p.Wd = d->W;
-  p.N = d->Cin; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.mode = 1;
-  p.gate = gate; p.bn_x = bn_x; p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.stat_partial = stat_partial;
-  p.M = d->B * d->H * d->W;
+  ConvGemmParams p = dgrad_params(d);
+  p.src1 = dy; p.wt = wt; p.out = dx;
+  gated_stats(p, gate, bn_x, bn_mean, bn_invstd, stat_partial);
   return run_gemm(d->dtype, p, (hipStream_t)stream);
+}
+
+// Partial rows of the pixel-stationary kernel's launch for this block, 0 when the plan is another kernel: what the fused forms below are served by.
+static int sk_rows(const SlConvDesc* d, const ConvGemmParams& p) {
+  const Plan pl = choose_kernel(p, d->dtype);
+  return pl.cfg == 6256064 ? (int)stat_rows(pl, p) : 0;
 }
 
 // The same across a block boundary (resnet.py:71-78 backward): the data gradient of conv1 plus the shortcut gradient `addend` IS the gradient wrt the previous block's
 // output relu(bn3(c3) + res); gated with that ReLU's bits and reduced against c3 it hands the previous block its bn3 backward column sums -- its reduce pass over
-// (dout, c3) disappears, and dout arrives gated.  Served: the shapes of the pixel-stationary kernel (1x1, K = 64 / 128 / 256, N % 128 == 0, N <= 1024, M % 256 == 0).
+// (dout, c3) disappears, and dout arrives gated.  Served: where this block's plan is the pixel-stationary kernel (choose_kernel: 1x1, K = 64 / 128 / 256, N % 128 == 0,
+// N <= 1024, M % 256 == 0).
 extern "C" int sl_conv2d_bwd_data_addend_bnstat_rows(const SlConvDesc* d) {
-  if (!d) return 0;
-  const long long M = (long long)d->B * d->H * d->W;
-  if (d->dtype != SL_BF16 || d->H != d->Ho || d->W != d->Wo) return 0;
-  if (!sk_shape(d->dtype, d->KH, d->KW, d->stride, d->pad, d->Cout, d->Cout, d->Cin, M) || d->Cin % 128 != 0 || d->Cin > 1024) return 0;
-  return (int)(M / 256);
+  return d ? sk_rows(d, query_params(d, 1, SL_EPI_GATE | SL_EPI_ADDEND)) : 0;
 }
 
 extern "C" int sl_conv2d_bwd_data_addend_bnstat(const SlConvDesc* d, const void* dy, const void* wt, const void* addend, const uint8_t* gate, const void* bn_x,
@@ -364,23 +366,19 @@ extern "C" int sl_conv2d_bwd_data_addend_bnstat(const SlConvDesc* d, const void*
   if (int e = check_desc(d)) return e;
   SL_REQUIRE(dy && wt && dx && addend && gate && bn_x && bn_mean && bn_invstd && stat_partial, "conv bwd_data_addend_bnstat: null buffer");
   SL_REQUIRE(sl_conv2d_bwd_data_addend_bnstat_rows(d) > 0, "conv bwd_data_addend_bnstat: shape not served (sl_conv2d_bwd_data_addend_bnstat_rows == 0)");
-  ConvGemmParams p{};
-  p.src1 = dy; p.src2 = nullptr; p.C1 = d->Cout; p.C2 = 0; p.wt = wt; p.out = dx;
-  p.B = d->B; p.Hs = d->Ho; p.Ws = d->Wo; p.Hd = d->H; p.Wd = d->W;
-  p.N = d->Cin; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.mode = 1;
-  p.addend = addend; p.gate = gate; p.bn_x = bn_x; p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.stat_partial = stat_partial;
-  p.M = d->B * d->H * d->W;
+  ConvGemmParams p = dgrad_params(d);
+  p.src1 = dy; p.wt = wt; p.out = dx; p.addend = addend;
+  gated_stats(p, gate, bn_x, bn_mean, bn_invstd, stat_partial);
   return run_gemm(d->dtype, p, (hipStream_t)stream);
 }
 
 // Data gradient + a HALF-RESOLUTION addend at the even positions (resnet.py:109-110, 71-76 backward of a stride-2 stage entry: the downsample branch is a 1x1 stride-2
 // conv, whose data gradient is non-zero at the even positions only): addend_half [B][H/2][W/2][Cin] is the DENSE data gradient of that conv on its own output grid
 // (sl_conv2d_bwd_data of the stride-1 form), added where (y, x) are both even -- the zero-filled full-resolution tensor (3/4 zeros, written and read back as an addend)
-// never exists.  Served: the pixel-stationary kernel's shapes with even H, W (sl_conv2d_bwd_data_addend_half_ok); optional cross-block statistics as in
+// never exists.  Served: where this block's plan is the pixel-stationary kernel, with even H, W (sl_conv2d_bwd_data_addend_half_ok); optional cross-block statistics as in
 // sl_conv2d_bwd_data_addend_bnstat (gate / bn_x / bn_mean / bn_invstd / stat_partial all NULL: plain).
 extern "C" int sl_conv2d_bwd_data_addend_half_ok(const SlConvDesc* d) {
-  if (!d || d->dtype != SL_BF16 || d->H != d->Ho || d->W != d->Wo || (d->H & 1) || (d->W & 1)) return 0;
-  return sk_shape(d->dtype, d->KH, d->KW, d->stride, d->pad, d->Cout, d->Cout, d->Cin, (long long)d->B * d->H * d->W) ? 1 : 0;
+  return d && !(d->H & 1) && !(d->W & 1) && sk_rows(d, query_params(d, 1, SL_EPI_ADDEND, 1)) > 0;
 }
 extern "C" int sl_conv2d_bwd_data_addend_half(const SlConvDesc* d, const void* dy, const void* wt, const void* addend_half, const uint8_t* gate, const void* bn_x,
                                               const float* bn_mean, const float* bn_invstd, void* dx, float* stat_partial, sl_stream_t stream) {
@@ -388,13 +386,9 @@ extern "C" int sl_conv2d_bwd_data_addend_half(const SlConvDesc* d, const void* d
   SL_REQUIRE(dy && wt && dx && addend_half, "conv bwd_data_addend_half: null buffer");
   SL_REQUIRE(sl_conv2d_bwd_data_addend_half_ok(d), "conv bwd_data_addend_half: shape not served (sl_conv2d_bwd_data_addend_half_ok == 0)");
   SL_REQUIRE(!gate || (bn_x && bn_mean && bn_invstd && stat_partial && sl_conv2d_bwd_data_addend_bnstat_rows(d) > 0), "conv bwd_data_addend_half: statistics not served for this shape");
-  ConvGemmParams p{};
-  p.src1 = dy; p.src2 = nullptr; p.C1 = d->Cout; p.C2 = 0; p.wt = wt; p.out = dx;
-  p.B = d->B; p.Hs = d->Ho; p.Ws = d->Wo; p.Hd = d->H; p.Wd = d->W;
-  p.N = d->Cin; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.mode = 1;
-  p.addend = addend_half; p.addend_half = 1;
-  if (gate) { p.gate = gate; p.bn_x = bn_x; p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.stat_partial = stat_partial; }
-  p.M = d->B * d->H * d->W;
+  ConvGemmParams p = dgrad_params(d);
+  p.src1 = dy; p.wt = wt; p.out = dx; p.addend = addend_half; p.addend_half = 1;
+  if (gate) gated_stats(p, gate, bn_x, bn_mean, bn_invstd, stat_partial);
   return run_gemm(d->dtype, p, (hipStream_t)stream);
 }
 
@@ -407,13 +401,9 @@ extern "C" int sl_conv2d_bwd_data_addend_bnstat2(const SlConvDesc* d, const void
   if (int e = check_desc(d)) return e;
   SL_REQUIRE(dy && wt && dx && addend && gate && bn_x && bn_mean && bn_invstd && bn_x2 && bn_mean2 && bn_invstd2 && stat_partial && stat_partial2, "conv bwd_data_addend_bnstat2: null buffer");
   SL_REQUIRE(sl_conv2d_bwd_data_addend_bnstat_rows(d) > 0, "conv bwd_data_addend_bnstat2: shape not served (sl_conv2d_bwd_data_addend_bnstat_rows == 0)");
-  ConvGemmParams p{};
-  p.src1 = dy; p.src2 = nullptr; p.C1 = d->Cout; p.C2 = 0; p.wt = wt; p.out = dx;
-  p.B = d->B; p.Hs = d->Ho; p.Ws = d->Wo; p.Hd = d->H; p.Wd = d->W;
-  p.N = d->Cin; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.mode = 1;
-  p.addend = addend; p.gate = gate; p.bn_x = bn_x; p.bn_mean = bn_mean; p.bn_invstd = bn_invstd; p.stat_partial = stat_partial;
+  ConvGemmParams p = dgrad_params(d);
+  p.src1 = dy; p.wt = wt; p.out = dx; p.addend = addend;
+  gated_stats(p, gate, bn_x, bn_mean, bn_invstd, stat_partial);
   p.bn_x2 = bn_x2; p.bn_mean2 = bn_mean2; p.bn_invstd2 = bn_invstd2; p.stat_partial2 = stat_partial2;
-  p.M = d->B * d->H * d->W;
   return run_gemm(d->dtype, p, (hipStream_t)stream);
 }
-

@@ -255,6 +255,31 @@ _BN_DUAL = _BN_FUSE        # test hook: bn3 + downsample BN backward in one swee
 _BN_CROSS = _BN_FUSE       # test hook: bn3's column sums from the NEXT block's conv1 data-gradient epilogue (pixel-stationary kernel MODE 5)
 
 
+def _conv_dgrad(dc, x, wb, spec, addend, x2, dx_out, addend_bits, below, prev3, prevd, dx_half, addend_half):
+    """The data gradient of conv_bn_bwd behind its BatchNorm part (dc: the gradient at the conv output, wb: the weight in the data-gradient layout): ONE launch, chosen by the first route that applies.
+    -> (dx, partial_below).  The fused routes write a fresh dx from a single source; where the library does not serve the shape they return None and the plain form runs."""
+    hw = x.shape[1:3]
+    fresh = x2 is None and dx_out is None
+    cross = prev3 is not None and addend is not None and addend_bits is None and fresh
+    r = None
+    if dx_half:
+        # a 1x1 stride-2 conv (a stage entry's downsample branch): its data gradient is non-zero at the even positions only -- return the DENSE gradient on the conv's own
+        # output grid; the consumer adds it at the even positions (ops.conv2d_bwd_data_addend_half), the zero-filled tensor is never written
+        r = ops.conv2d_bwd_data(dc, wb, ConvSpec(spec.cin, spec.cout, 1, 1, 0, 1), dc.shape[1:3]), None
+    elif addend_half:
+        r = ops.conv2d_bwd_data_addend_half(dc, wb, spec, hw, addend, prev3)
+    elif below is not None and _BN_FUSE and addend is None and fresh:
+        r = ops.conv2d_bwd_data_bnstat(dc, wb, spec, hw, *below)
+    elif cross and prevd is not None:     # the block in front is a stage's first one: bn3 + downsample BatchNorm behind its ReLU, both reduced here (partial_below is a pair)
+        r = ops.conv2d_bwd_data_addend_bnstat2(dc, wb, spec, hw, addend, *prev3, *prevd)
+        r = r and (r[0], (r[1], r[2]))
+    elif cross:
+        r = ops.conv2d_bwd_data_addend_bnstat(dc, wb, spec, hw, addend, *prev3)
+    if r is None:
+        r = ops.conv2d_bwd_data(dc, wb, spec, hw, addend=addend, addend_mask=addend_bits, C1=(x.shape[3] if x2 is not None else None), out=dx_out), None
+    return r
+
+
 def conv_bn_bwd(dy, y_mask, c, x, conv, bn, mean, invstd, need_dx, need_dw, want_dres=False, addend=None, x2=None, dx_out=None,
                 bits=None, addend_bits=None, pre_partial=None, below=None, bn_done=None, prev3=None, prevd=None, dx_half=False, addend_half=False):
     """Backward of y = act(bn(conv(x))).  Returns (dx, dw, dgamma, dbeta, dres, partial_below).
@@ -278,32 +303,8 @@ def conv_bn_bwd(dy, y_mask, c, x, conv, bn, mean, invstd, need_dx, need_dw, want
     dx = dw = part_below = None
     if need_dw:
         dw = grad_alias(ops.conv2d_bwd_weight(x, dc, spec, x2=x2, out=gw), gw)
-    if need_dx and dx_half:
-        # a 1x1 stride-2 conv (a stage entry's downsample branch): its data gradient is non-zero at the even positions only -- return the DENSE gradient on the conv's own
-        # output grid; the consumer adds it at the even positions (ops.conv2d_bwd_data_addend_half), the zero-filled tensor is never written
-        _, wb = prepared(conv.weight, c.dtype)
-        dx = ops.conv2d_bwd_data(dc, wb, ConvSpec(spec.cin, spec.cout, 1, 1, 0, 1), dc.shape[1:3])
-    elif need_dx and addend_half:
-        _, wb = prepared(conv.weight, c.dtype)
-        dx, part_below = ops.conv2d_bwd_data_addend_half(dc, wb, spec, x.shape[1:3], addend, prev3)
-    elif need_dx:
-        _, wb = prepared(conv.weight, c.dtype)
-        if below is not None and _BN_FUSE and addend is None and x2 is None and dx_out is None:
-            r = ops.conv2d_bwd_data_bnstat(dc, wb, spec, x.shape[1:3], *below)
-            if r is not None:
-                dx, part_below = r
-        if prev3 is not None and addend is not None and addend_bits is None and x2 is None and dx_out is None:
-            if prevd is not None:       # the block in front is a stage's first one: bn3 + downsample BatchNorm behind its ReLU, both reduced here (partial_below is a pair)
-                r = ops.conv2d_bwd_data_addend_bnstat2(dc, wb, spec, x.shape[1:3], addend, *prev3, *prevd)
-                if r is not None:
-                    dx, part_below = r[0], (r[1], r[2])
-            else:
-                r = ops.conv2d_bwd_data_addend_bnstat(dc, wb, spec, x.shape[1:3], addend, *prev3)
-                if r is not None:
-                    dx, part_below = r
-        if dx is None:
-            dx = ops.conv2d_bwd_data(dc, wb, spec, x.shape[1:3], addend=addend, addend_mask=addend_bits,
-                                     C1=(x.shape[3] if x2 is not None else None), out=dx_out)
+    if need_dx:
+        dx, part_below = _conv_dgrad(dc, x, prepared(conv.weight, c.dtype)[1], spec, addend, x2, dx_out, addend_bits, below, prev3, prevd, dx_half, addend_half)
     return dx, dw, dgamma, dbeta, dres, part_below
 
 

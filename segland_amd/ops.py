@@ -252,129 +252,101 @@ def conv2d_affine_fwd(x, wf, spec, scale, shift, x2=None, residual=None, relu=Tr
     return y
 
 
-def conv2d_bwd_data(dy, wb, spec, in_hw, addend=None, mask_src=None, C1=None, out=None, addend_mask=None):
+def _dgrad_query(query, dtype, B, H, W, spec):
+    """A served-query of the pixel-stationary kernel's fused data gradients (include/segland_hip.h: sl_conv2d_bwd_data_addend_bnstat_rows / _addend_half_ok) for conv
+    `spec` on a [B,H,W,Cin] input: partial rows / 1, 0 = not served.  THE bf16 guard of these forms: the wrappers below all ask here."""
+    if dtype != torch.bfloat16:
+        return 0
+    return getattr(_lib.lib(), query)(C.byref(conv_desc(dtype, B, H, W, spec, None)))
+
+
+def _dgrad(name, launch, dy, spec, in_hw, epi, reads, C1=None, out=None):
+    """One data-gradient launch: descriptor, dx, profiler bracket.  launch(L, d, dx, stream) is the library call; epi: its SL_EPI_* bits; reads: the tensors it
+    reads beyond dy and the weight (None entries skipped), for the profiler's byte count.  -> dx [B,H,W,Cin]."""
     B = dy.shape[0]
     H, W = in_hw
     d = conv_desc(dy.dtype, B, H, W, spec, C1)
     dx = out if out is not None else torch.empty((B, H, W, spec.cin), dtype=dy.dtype, device=dy.device)
     assert dx.numel() == B * H * W * spec.cin and dx.dtype == dy.dtype
-    tok = PROFILER.begin('conv_dgrad', d, (EPI_ADDEND if addend is not None else 0) | (EPI_ADDEND_BITS if addend_mask is not None else 0))
-    check(_lib.lib().sl_conv2d_bwd_data(C.byref(d), _p(dy), _p(wb), _p(addend), _p(addend_mask), _p(mask_src), _p(dx), _s()), 'conv2d_bwd_data')
+    tok = PROFILER.begin('conv_dgrad', d, epi)
+    check(launch(_lib.lib(), C.byref(d), _p(dx), _s()), name)
     if tok is not None:
-        PROFILER.end(tok, sum(t.numel() * t.element_size() for t in (addend, addend_mask, mask_src) if t is not None))
+        PROFILER.end(tok, sum(t.numel() * t.element_size() for t in reads if t is not None))
     return dx
+
+
+def conv2d_bwd_data(dy, wb, spec, in_hw, addend=None, mask_src=None, C1=None, out=None, addend_mask=None):
+    return _dgrad('conv2d_bwd_data', lambda L, d, dx, s: L.sl_conv2d_bwd_data(d, _p(dy), _p(wb), _p(addend), _p(addend_mask), _p(mask_src), dx, s),
+                  dy, spec, in_hw, (EPI_ADDEND if addend is not None else 0) | (EPI_ADDEND_BITS if addend_mask is not None else 0), (addend, addend_mask, mask_src), C1, out)
 
 
 def conv2d_bwd_data_gelu(dy, wb, spec, in_hw, h):
     """conv2d_bwd_data(dy) * GELU'(h) in one launch (h: the stored pre-activation, the data gradient's shape): sl_conv2d_bwd_data_gelu."""
-    B = dy.shape[0]
-    H, W = in_hw
-    d = conv_desc(dy.dtype, B, H, W, spec, None)
-    assert (d.Ho, d.Wo) == tuple(dy.shape[1:3]) and tuple(h.shape) == (B, H, W, spec.cin) and h.dtype == dy.dtype and h.is_contiguous()
-    dx = torch.empty((B, H, W, spec.cin), dtype=dy.dtype, device=dy.device)
-    tok = PROFILER.begin('conv_dgrad', d, EPI_GELU)
-    check(_lib.lib().sl_conv2d_bwd_data_gelu(C.byref(d), _p(dy), _p(wb), _p(h), _p(dx), _s()), 'conv2d_bwd_data_gelu')
-    PROFILER.end(tok, extra_bytes=h.numel() * h.element_size())
-    return dx
+    assert spec.out_hw(*in_hw) == tuple(dy.shape[1:3]) and tuple(h.shape) == (dy.shape[0], *in_hw, spec.cin) and h.dtype == dy.dtype and h.is_contiguous()
+    return _dgrad('conv2d_bwd_data_gelu', lambda L, d, dx, s: L.sl_conv2d_bwd_data_gelu(d, _p(dy), _p(wb), _p(h), dx, s), dy, spec, in_hw, EPI_GELU, (h,))
 
 
 def conv2d_bwd_data_bnstat(dy, wb, spec, in_hw, gate, bn_x, mean, invstd):
     """Data gradient gated with the ReLU bits `gate` of its own positions + the reduce pass of the BatchNorm backward below it in the epilogue
     (csrc/conv_gemm_common.h: conv_epilogue_fast MODE 3).  -> (g, partial [rows][2][Cin]) or None when the shape is not served (caller: conv2d_bwd_data + bn_bwd)."""
-    B = dy.shape[0]
-    H, W = in_hw
-    d = conv_desc(dy.dtype, B, H, W, spec, None)
-    L = _lib.lib()
-    rows = L.sl_conv2d_bwd_data_bnstat_rows(C.byref(d))
+    rows = _lib.lib().sl_conv2d_bwd_data_bnstat_rows(C.byref(conv_desc(dy.dtype, dy.shape[0], *in_hw, spec, None)))      # the tile kernels serve fp32 too
     if rows <= 0:
         return None
-    dx = torch.empty((B, H, W, spec.cin), dtype=dy.dtype, device=dy.device)
     part = _f32((rows, 2, spec.cin), dy.device)
-    tok = PROFILER.begin('conv_dgrad', d, EPI_GATE)
-    check(L.sl_conv2d_bwd_data_bnstat(C.byref(d), _p(dy), _p(wb), _p(gate), _p(bn_x), _p(mean), _p(invstd), _p(dx), _p(part), _s()), 'conv2d_bwd_data_bnstat')
-    if tok is not None:
-        PROFILER.end(tok, bn_x.numel() * bn_x.element_size() + gate.numel())
+    dx = _dgrad('conv2d_bwd_data_bnstat', lambda L, d, dx, s: L.sl_conv2d_bwd_data_bnstat(d, _p(dy), _p(wb), _p(gate), _p(bn_x), _p(mean), _p(invstd), dx, _p(part), s),
+                dy, spec, in_hw, EPI_GATE, (bn_x, gate))
     return dx, part
 
 
 def conv2d_bwd_data_addend_bnstat_ok(x, spec):
     """Would conv2d_bwd_data_addend_bnstat serve the data gradient of conv `spec` on input x [B,H,W,Cin]?"""
-    if x.dtype != torch.bfloat16:
-        return False
-    B, H, W, _ = x.shape
-    return _lib.lib().sl_conv2d_bwd_data_addend_bnstat_rows(C.byref(conv_desc(x.dtype, B, H, W, spec, None))) > 0
+    return _dgrad_query('sl_conv2d_bwd_data_addend_bnstat_rows', x.dtype, *x.shape[:3], spec) > 0
 
 
 def conv2d_bwd_data_addend_bnstat(dy, wb, spec, in_hw, addend, gate, bn_x, mean, invstd):
     """dx = data gradient + addend, gated with the ReLU bits `gate` of the block output it is the gradient of, + that block's bn3 backward column
     sums (csrc/conv_gemm_sk.hip: pixel-stationary kernel MODE 5).  -> (g, partial [rows][2][Cin]) or None when the shape is not served."""
-    B = dy.shape[0]
-    H, W = in_hw
-    d = conv_desc(dy.dtype, B, H, W, spec, None)
-    L = _lib.lib()
-    rows = L.sl_conv2d_bwd_data_addend_bnstat_rows(C.byref(d)) if dy.dtype == torch.bfloat16 else 0
+    rows = _dgrad_query('sl_conv2d_bwd_data_addend_bnstat_rows', dy.dtype, dy.shape[0], *in_hw, spec)
     if rows <= 0:
         return None
-    dx = torch.empty((B, H, W, spec.cin), dtype=dy.dtype, device=dy.device)
     part = _f32((rows, 2, spec.cin), dy.device)
-    tok = PROFILER.begin('conv_dgrad', d, EPI_GATE | EPI_ADDEND)
-    check(L.sl_conv2d_bwd_data_addend_bnstat(C.byref(d), _p(dy), _p(wb), _p(addend), _p(gate), _p(bn_x), _p(mean), _p(invstd), _p(dx), _p(part), _s()),
-          'conv2d_bwd_data_addend_bnstat')
-    if tok is not None:
-        PROFILER.end(tok, addend.numel() * addend.element_size() + bn_x.numel() * bn_x.element_size() + gate.numel())
+    dx = _dgrad('conv2d_bwd_data_addend_bnstat',
+                lambda L, d, dx, s: L.sl_conv2d_bwd_data_addend_bnstat(d, _p(dy), _p(wb), _p(addend), _p(gate), _p(bn_x), _p(mean), _p(invstd), dx, _p(part), s),
+                dy, spec, in_hw, EPI_GATE | EPI_ADDEND, (addend, bn_x, gate))
     return dx, part
 
 
 def conv2d_bwd_data_addend_half_ok(x, spec):
     """Would conv2d_bwd_data_addend_half serve the data gradient of conv `spec` on input x [B,H,W,Cin]?"""
-    if x.dtype != torch.bfloat16:
-        return False
-    B, H, W, _ = x.shape
-    return _lib.lib().sl_conv2d_bwd_data_addend_half_ok(C.byref(conv_desc(x.dtype, B, H, W, spec, None))) > 0
+    return _dgrad_query('sl_conv2d_bwd_data_addend_half_ok', x.dtype, *x.shape[:3], spec) > 0
 
 
 def conv2d_bwd_data_addend_half(dy, wb, spec, in_hw, addend_half, prev3=None):
     """dx = data gradient + addend_half [B,H/2,W/2,Cin] at the even positions (the dense data gradient of a 1x1 stride-2 conv on its own grid; its zero-filled
     full-resolution form never exists).  prev3 = (gate bits, bn_x, mean, invstd): also the cross-block statistics of conv2d_bwd_data_addend_bnstat.
     -> (dx, partial or None)."""
-    B = dy.shape[0]
-    H, W = in_hw
-    d = conv_desc(dy.dtype, B, H, W, spec, None)
-    L = _lib.lib()
+    B, (H, W) = dy.shape[0], in_hw
     assert addend_half.shape == (B, H // 2, W // 2, spec.cin) and addend_half.is_contiguous()
-    dx = torch.empty((B, H, W, spec.cin), dtype=dy.dtype, device=dy.device)
-    part = None
-    gate = bn_x = mean = invstd = None
-    if prev3 is not None:
-        rows = L.sl_conv2d_bwd_data_addend_bnstat_rows(C.byref(d))
-        if rows > 0:
-            gate, bn_x, mean, invstd = prev3
-            part = _f32((rows, 2, spec.cin), dy.device)
-    tok = PROFILER.begin('conv_dgrad', d, EPI_ADDEND | (EPI_GATE if part is not None else 0))
-    check(L.sl_conv2d_bwd_data_addend_half(C.byref(d), _p(dy), _p(wb), _p(addend_half), _p(gate), _p(bn_x), _p(mean), _p(invstd), _p(dx), _p(part), _s()),
-          'conv2d_bwd_data_addend_half')
-    if tok is not None:
-        PROFILER.end(tok, addend_half.numel() * addend_half.element_size() + (bn_x.numel() * bn_x.element_size() + gate.numel() if part is not None else 0))
+    rows = _dgrad_query('sl_conv2d_bwd_data_addend_bnstat_rows', dy.dtype, B, H, W, spec) if prev3 is not None else 0
+    gate, bn_x, mean, invstd = prev3 if rows > 0 else (None,) * 4
+    part = _f32((rows, 2, spec.cin), dy.device) if rows > 0 else None
+    dx = _dgrad('conv2d_bwd_data_addend_half',
+                lambda L, d, dx, s: L.sl_conv2d_bwd_data_addend_half(d, _p(dy), _p(wb), _p(addend_half), _p(gate), _p(bn_x), _p(mean), _p(invstd), dx, _p(part), s),
+                dy, spec, in_hw, EPI_ADDEND | (EPI_GATE if rows > 0 else 0), (addend_half, bn_x, gate))
     return dx, part
 
 
 def conv2d_bwd_data_addend_bnstat2(dy, wb, spec, in_hw, addend, gate, bn_x, mean, invstd, bn_x2, mean2, invstd2):
     """The dual form of conv2d_bwd_data_addend_bnstat: the gated result is reduced against the inputs of TWO BatchNorms behind the same ReLU (bn3 + the downsample
     BatchNorm of a stage's first bottleneck).  -> (g, partial, partial2) or None when the shape is not served."""
-    B = dy.shape[0]
-    H, W = in_hw
-    d = conv_desc(dy.dtype, B, H, W, spec, None)
-    L = _lib.lib()
-    rows = L.sl_conv2d_bwd_data_addend_bnstat_rows(C.byref(d)) if dy.dtype == torch.bfloat16 else 0
+    rows = _dgrad_query('sl_conv2d_bwd_data_addend_bnstat_rows', dy.dtype, dy.shape[0], *in_hw, spec)
     if rows <= 0:
         return None
-    dx = torch.empty((B, H, W, spec.cin), dtype=dy.dtype, device=dy.device)
     part = _f32((2, rows, 2, spec.cin), dy.device)
-    tok = PROFILER.begin('conv_dgrad', d, EPI_GATE | EPI_ADDEND)
-    check(L.sl_conv2d_bwd_data_addend_bnstat2(C.byref(d), _p(dy), _p(wb), _p(addend), _p(gate), _p(bn_x), _p(mean), _p(invstd), _p(bn_x2), _p(mean2), _p(invstd2), _p(dx),
-                                              _p(part[0]), _p(part[1]), _s()), 'conv2d_bwd_data_addend_bnstat2')
-    if tok is not None:
-        PROFILER.end(tok, addend.numel() * addend.element_size() + 2 * bn_x.numel() * bn_x.element_size() + gate.numel())
+    dx = _dgrad('conv2d_bwd_data_addend_bnstat2',
+                lambda L, d, dx, s: L.sl_conv2d_bwd_data_addend_bnstat2(d, _p(dy), _p(wb), _p(addend), _p(gate), _p(bn_x), _p(mean), _p(invstd), _p(bn_x2), _p(mean2),
+                                                                        _p(invstd2), dx, _p(part[0]), _p(part[1]), s),
+                dy, spec, in_hw, EPI_GATE | EPI_ADDEND, (addend, bn_x, bn_x2, gate))
     return dx, part[0], part[1]
 
 

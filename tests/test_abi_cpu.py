@@ -197,3 +197,64 @@ def test_weight_gradient_plan_by_shape(lib):
     assert lib.sl_conv2d_bwd_weight_clip(C.byref(d), dummy, None, dummy, dummy, 96, 96, dummy, 0, dummy, None) == -2
     assert lib.sl_last_error_string() == b'conv bwd_weight: workspace 0 < 9437184'                  # the 128 x 128 tile kernels' slabs
     assert lib.sl_conv2d_bwd_weight_bias_rows(C.byref(d), 96, 96) == 32
+
+
+DGRAD_PLAN = [
+    # (B, H, W), Cin, Cout, k, stride      the data gradient reduces over Cout and writes Cin columns
+    ((1, 256, 256), 128, 64, 1, 1),        # K = 64 at 65 536 rows, 128 columns: every fused form of the pixel-stationary kernel
+    ((1, 128, 128), 128, 64, 1, 1),        # the same layer below 65 536 rows: tile kernels, no fused form with an addend
+    ((1, 256, 256), 192, 64, 1, 1),        # 192 columns: the half-resolution addend is served, its gate bytes do not fit (N % 128)
+    ((256, 17, 17), 128, 64, 1, 1),        # a pixel-stationary shape with odd H, W: no half-resolution addend
+    ((16, 64, 64), 2048, 512, 1, 1),       # K = 512: half-tile kernel, gated statistics only
+    ((1, 160, 160), 256, 512, 1, 1),       # half-tile kernel from 256 x 96 rows
+    ((1, 100, 100), 256, 512, 1, 1),       # ragged last row block: no gated statistics
+    ((8, 64, 64), 192, 256, 1, 1),         # 128 x 192 ring tile: gated statistics not offered
+    ((6, 128, 128), 128, 128, 3, 2),       # parity planes
+    ((4, 128, 128), 64, 64, 3, 1),         # 64 -> 64 3x3 kernel
+    ((3, 128, 128), 64, 64, 3, 1),         # below its 65 536 rows: two-stage kernel
+]
+
+
+def test_fused_data_gradient_queries_answer_from_the_plan(lib):
+    """The served-queries of the fused data gradients are the dispatch's own answer (csrc/conv_gemm.hip choose_kernel; host logic, no launch): the forms with an addend
+    are served exactly where the launch with their epilogue bits is planned on the pixel-stationary kernel (family 6; the half-resolution addend also needs even H, W), the
+    gated statistics exactly where the plan is a family with the gated store phase (5, 8, 4, 2 with full row blocks and not 192 columns wide, or 7).  The entry points
+    refuse an unserved shape before anything is launched."""
+    ADDEND, GATE = 4, 16
+    served = {'bnstat': 0, 'addend_bnstat': 0, 'half': 0}
+    for (B, H, W), cin, cout, k, stride in DGRAD_PLAN:
+        for dtype in (_lib.SL_BF16, _lib.SL_F32):
+            d = _desc(dtype, B, H, W, cin, cout, k, stride, k // 2, 1)
+            r = C.byref(d)
+            cfg = lambda epi: lib.sl_conv2d_tile_config_ex(r, 1, epi)
+            rows = lib.sl_conv2d_bwd_data_addend_bnstat_rows(r)
+            assert (rows > 0) == (cfg(GATE | ADDEND) // 1000000 == 6), (d.dtype, B, H, W, cin, cout, rows)
+            assert rows == (B * H * W // 256 if rows else 0)
+            half = lib.sl_conv2d_bwd_data_addend_half_ok(r)
+            assert half == int(cfg(ADDEND) // 1000000 == 6 and H % 2 == 0 and W % 2 == 0), (d.dtype, B, H, W, cin, cout, half)
+            c = cfg(GATE)
+            fam, bm, bn = c // 1000000, (c // 1000) % 1000, c % 1000
+            plane = B * H * W // 4 if (stride == 2 and bm == 256) else B * H * W        # a stride-2 3x3 plan on 256-row tiles is the four parity planes
+            gated = fam == 7 or (fam in (5, 8, 4, 2) and plane % bm == 0 and bn != 192)
+            g = lib.sl_conv2d_bwd_data_bnstat_rows(r)
+            assert (g > 0) == gated, (d.dtype, B, H, W, cin, cout, c, g)
+            served['bnstat'] += g > 0; served['addend_bnstat'] += rows > 0; served['half'] += half
+    assert all(0 < n < 2 * len(DGRAD_PLAN) for n in served.values()), served                  # the table holds served and unserved descriptors of each form
+    dummy = C.c_void_p(16)
+    err = lambda: lib.sl_last_error_string()
+    d = _desc(_lib.SL_BF16, 1, 128, 128, 128, 64, 1, 1, 0, 1)
+    assert lib.sl_conv2d_bwd_data_addend_half(C.byref(d), dummy, dummy, dummy, None, None, None, None, dummy, None, None) == -1
+    assert err() == b'conv bwd_data_addend_half: shape not served (sl_conv2d_bwd_data_addend_half_ok == 0)'
+    assert lib.sl_conv2d_bwd_data_addend_bnstat(C.byref(d), dummy, dummy, dummy, dummy, dummy, dummy, dummy, dummy, dummy, None) == -1
+    assert err() == b'conv bwd_data_addend_bnstat: shape not served (sl_conv2d_bwd_data_addend_bnstat_rows == 0)'
+    assert lib.sl_conv2d_bwd_data_addend_bnstat2(C.byref(d), dummy, dummy, dummy, dummy, dummy, dummy, dummy, dummy, dummy, dummy, dummy, dummy, dummy, None) == -1
+    assert err() == b'conv bwd_data_addend_bnstat2: shape not served (sl_conv2d_bwd_data_addend_bnstat_rows == 0)'
+    d = _desc(_lib.SL_BF16, 256, 17, 17, 128, 64, 1, 1, 0, 1)                               # pixel-stationary plan, odd map
+    assert lib.sl_conv2d_bwd_data_addend_half(C.byref(d), dummy, dummy, dummy, None, None, None, None, dummy, None, None) == -1
+    assert err() == b'conv bwd_data_addend_half: shape not served (sl_conv2d_bwd_data_addend_half_ok == 0)'
+    d = _desc(_lib.SL_BF16, 1, 256, 256, 192, 64, 1, 1, 0, 1)                               # served without the statistics only
+    assert lib.sl_conv2d_bwd_data_addend_half(C.byref(d), dummy, dummy, dummy, dummy, dummy, dummy, dummy, dummy, dummy, None) == -1
+    assert err() == b'conv bwd_data_addend_half: statistics not served for this shape'
+    d = _desc(_lib.SL_BF16, 8, 64, 64, 192, 256, 1, 1, 0, 1)
+    assert lib.sl_conv2d_bwd_data_bnstat(C.byref(d), dummy, dummy, dummy, dummy, dummy, dummy, dummy, dummy, None) == -1
+    assert err() == b'conv bwd_data_bnstat: shape not served (sl_conv2d_bwd_data_bnstat_rows == 0)'
