@@ -17,6 +17,7 @@ void sl_debug_reset(void);                 /* every override back to its default
 /* dispatch overrides (1 = default route, 0 = the route it replaced) */
 void sl_debug_conv_affine(int on);         /* branch-free affine store phase of biased / folded-BN epilogues vs the generic store phase */
 void sl_debug_conv_p9(int on);             /* 3x3 patch kernel (conv_gemm_p9_kernel) vs the half-tile / ring kernels */
+void sl_debug_conv_p9_lean(int on);        /* lean (dilation / window as template constants, taps unrolled) vs generic K-tile loop of conv_gemm_p9_kernel (bit-identical) */
 void sl_debug_conv_p8_k1(int on);          /* 1x1 form of conv_gemm_p8_kernel's K-tile body vs the generic form on 1x1 launches (bit-identical) */
 void sl_debug_conv_ring192(int on);        /* 128 x 192 ring tiles for 192-multiple output widths vs the two-stage 256 x 64 kernel */
 void sl_debug_conv_ringn64(int on);        /* 128 x 64 ring tiles for 64-column inference layers vs the two-stage kernel */

@@ -24,6 +24,7 @@ SlDebugState g_sl_debug;
 extern "C" void sl_debug_reset(void) { g_sl_debug = SlDebugState(); }
 extern "C" void sl_debug_conv_affine(int v) { g_sl_debug.conv_affine = v ? 1 : 0; }
 extern "C" void sl_debug_conv_p9(int v) { g_sl_debug.conv_p9 = (v & 1) ? 1 : 0; }
+extern "C" void sl_debug_conv_p9_lean(int v) { g_sl_debug.conv_p9_lean = v ? 1 : 0; }
 extern "C" void sl_debug_conv_p8_k1(int v) { g_sl_debug.conv_p8_k1 = v ? 1 : 0; }
 extern "C" void sl_debug_conv_ring192(int v) { g_sl_debug.conv_ring192 = v ? 1 : 0; }
 extern "C" void sl_debug_conv_ringn64(int v) { g_sl_debug.conv_ringn64 = v ? 1 : 0; }

@@ -91,6 +91,7 @@ void sl_set_error(const char* fmt, ...);
 struct SlDebugState {
   int conv_affine = 1;             // branch-free affine store phase for biased / folded-BN epilogues (0: the generic one everywhere -- the bit-identity test)
   int conv_p9 = 1;                 // 3x3 patch kernel (0: the half-tile / ring kernels take the 3x3 layers)
+  int conv_p9_lean = 1;            // lean form of the patch kernel's K-tile loop (0: the generic loop takes every launch; bit-identical)
   int conv_p8_k1 = 1;              // 1x1 form of the half-tile kernel's K-tile body (0: the generic form takes the 1x1 launches too; bit-identical)
   int conv_ring192 = 1;            // 128 x 192 ring tile for 192-multiple output widths
   int conv_ringn64 = 1;            // 128 x 64 ring tile for 64-column inference layers

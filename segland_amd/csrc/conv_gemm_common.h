@@ -732,6 +732,21 @@ __device__ __forceinline__ void glds16x2_sbase_asm(const void* sbase, unsigned o
                "global_load_lds_dwordx4 %3, %1\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "s"(sbase), "v"(off0), "v"(off1), "s"(lds_addr) : "memory", "scc");
 }
+// Both halves of one weight K-tile (patch kernel): rows dst, dst + 1 KiB of half 0 and the same two of half 1, one 16 KiB slot further on.  Four loads for the caller's vmcnt.
+__device__ __forceinline__ void glds16x4_sbase_asm(const void* sbase, unsigned off0, unsigned off1, unsigned off2, unsigned off3, unsigned lds_addr) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %1\n\ts_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
+               "global_load_lds_dwordx4 %3, %1\n\ts_add_u32 m0, m0, 0x3c00\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %1\n\ts_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
+               "global_load_lds_dwordx4 %5, %1\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "s"(sbase), "v"(off0), "v"(off1), "v"(off2), "v"(off3), "s"(lds_addr) : "memory", "scc");
+}
+// glds16x2_asm with the second piece STEP bytes further on in the LDS (patch rows of two consecutive wave-instructions: 8 KiB apart)
+template <int STEP> __device__ __forceinline__ void glds16x2_step_asm(const void* g0, const void* g1, unsigned lds_addr) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_add_u32 m0, m0, %4\n\ts_nop 0\n\t"
+               "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(g0), "v"(g1), "s"(lds_addr), "n"(STEP) : "memory", "scc");
+}
 __device__ __forceinline__ unsigned lds_addr_of(const unsigned char* p) {
   return (unsigned)(size_t)((const __attribute__((address_space(3))) unsigned char*)p);
 }

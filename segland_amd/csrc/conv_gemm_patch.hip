@@ -403,7 +403,21 @@ constexpr int P9_PATCH = 576 * 128;                                     // large
 constexpr int P9_LDS = P9_PATCH + 4 * P8_SLOT;                          // + B0 / B1 of two K-tiles = 136 KiB
 constexpr int P9_PATCH1 = 42 * 1024;                                    // d = 1: 324 rows -> two patch buffers (the next chunk's patch lands under the current chunk's taps)
 constexpr int P9_LDS1 = 2 * P9_PATCH1 + 4 * P8_SLOT;                    // 148 KiB
-template <int EPI>       // 0 / 1 / 2 as in conv_gemm_p8_kernel; split-K parts are ranges of 64-channel chunks (all nine taps of a chunk stay together: one patch per chunk)
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+// one fragment from an LDS byte address: with a compile-time addend the compiler folds it into the 16-bit offset field of the ds_read_b128
+__device__ __forceinline__ uint4 lds_read16(unsigned addr) {
+  const u32x4_t v = *(const __attribute__((address_space(3))) u32x4_t*)(size_t)addr;
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+template <int I> using p9_int = std::integral_constant<int, I>;
+
+// D = 0: the generic loop (dilation, window direction and patch-buffer choice at run time).  D = 1 / 2 / 4: the LEAN form of the same loop for that dilation, FLIP = the data
+// gradient's flipped window.  Same LDS-DMA issue order, LDS slots, waits, barriers and MFMA order -- results are bit-identical -- with everything a K-tile does not need taken
+// out of it: the nine taps are unrolled inside a loop over chunks, so a tap's patch offset, the (half, row block) offset and the weight slot are ds_read immediates on top of
+// 12 + 8 lane addresses (swizzle of column shift kx x k-step; two weight slot pairs, swapped per chunk because nine taps are odd); the weight rows are a wave-uniform base
+// advanced in scalar registers plus four lane offsets, all four pieces from one statement; the patch pieces are per-lane pointers that advance by 128 or 0 bytes per chunk
+// (padding lanes stay on the zero page), two pieces per statement; the last chunk is peeled, so no issue site of the steady chunk asks whether there is a next one.
+template <int EPI, int D, bool FLIP>       // EPI 0 / 1 / 2 as in conv_gemm_p8_kernel; split-K parts are ranges of 64-channel chunks (all nine taps of a chunk stay together: one patch per chunk)
 __global__ __launch_bounds__(512) void conv_gemm_p9_kernel(ConvGemmParams p) {
   using T = bf16_t;
   constexpr int BM = 256, BN = 256;
@@ -424,7 +438,7 @@ __global__ __launch_bounds__(512) void conv_gemm_p9_kernel(ConvGemmParams p) {
   const int GN = p.gridN > 2 && p.gridN % 2 == 0 && !(p.flags & 16) ? 2 : p.gridN;
   const int grp = bid / (p.gridM * GN), rem = bid - grp * (p.gridM * GN);
   const int bm = rem / GN, bn = grp * GN + rem % GN;
-  const int d = p.dil, PW = 16 + 2 * d, PP = PW * PW;
+  const int d = D ? D : p.dil, PW = 16 + 2 * d, PP = PW * PW;
   const int CT = p.C1;
   const int cbeg = SPLITK ? (CT / 64) * part / KS : 0, nchunk = SPLITK ? (CT / 64) * (part + 1) / KS : CT / 64;      // chunks [cbeg, nchunk)
   const int tx = p.Ws >> 4, ty = p.Hs >> 4;
@@ -433,6 +447,8 @@ __global__ __launch_bounds__(512) void conv_gemm_p9_kernel(ConvGemmParams p) {
   const unsigned lds_base = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
   const int lr = lane >> 3, lpos = lane & 7;
   const unsigned char* zsrc = g_zero_page + lpos * 16;
+  f32x16_t acc[4][2];
+  if constexpr (D == 0) {      // the generic loop, text unchanged (and not re-indented)
 
   // ---- patch fill: wave-instruction g = j * 8 + wave covers patch rows g * 8 .. + 7 (lane -> row lr, 16-byte position lpos; the swizzle is applied to the source piece)
   constexpr int NPI = 9;                                                  // instructions per wave: 9 x 8 waves x 8 rows = 576 rows (rows >= PP are skipped)
@@ -497,7 +513,6 @@ __global__ __launch_bounds__(512) void conv_gemm_p9_kernel(ConvGemmParams p) {
     return *(const uint4*)(smem + pbase + pr * 128 + (((2 * ks + fh) ^ ((px >> 1) & 7)) << 4));
   };
 
-  f32x16_t acc[4][2];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -566,6 +581,147 @@ __global__ __launch_bounds__(512) void conv_gemm_p9_kernel(ConvGemmParams p) {
       }
     } else ++tap;
   }
+
+  } else {
+    // ---- the lean form (see above).  Names as in the generic form.
+    constexpr int LPW = 16 + 2 * D, LPP = LPW * LPW;
+    constexpr int NPI = 9;
+    constexpr bool DBUF = D == 1;                                          // launch_p9 sends a launch with flags bit 3 to the generic form
+    constexpr int BOFF = DBUF ? 2 * P9_PATCH1 : P9_PATCH;
+    static_assert(((10 * LPW + (2 * LPW + 2) * D) * 128) < 65536, "ds_read immediates");
+    // patch pieces: pptr[j] = this lane's source piece of the NEXT chunk to be requested; bit j of okm: the piece is inside the image and advances by 128 bytes per chunk
+    const unsigned char* pptr[10]; unsigned okm = 0;
+#pragma unroll
+    for (int j = 0; j < NPI; ++j) {
+      const int pr = (j * 8 + wave) * 8 + lr;
+      const int py = pr / LPW, px = pr - py * LPW;
+      const int iy = y0 + py, ix = x0 + px;
+      const bool ok = pr < LPP && (unsigned)iy < (unsigned)p.Hs && (unsigned)ix < (unsigned)p.Ws;
+      pptr[j] = ok ? (const unsigned char*)p.src1 + (((size_t)(bb * p.Hs + iy) * p.Ws + ix) * CT + (size_t)cbeg * 64) * sizeof(T) + ((lpos ^ ((px >> 1) & 7)) << 4) : zsrc;
+      okm |= ok ? 1u << j : 0u;
+    }
+    pptr[9] = zsrc;
+    auto issue_patch = [&](unsigned buf) {                                 // piece j of wave w -> rows (j * 8 + w) * 8 .. + 7; the pieces every wave has go out in pairs
+      const unsigned dst = lds_base + buf + wave * 1024;
+#pragma unroll
+      for (int j = 0; j < 10; j += 2) {
+        const bool all0 = (j * 8 + 7) * 8 < LPP, all1 = ((j + 1) * 8 + 7) * 8 < LPP;
+        if (all0 && all1) glds16x2_step_asm<8192>(pptr[j], pptr[j + 1], dst + j * 8192);
+        else {
+          if (all0 || (j * 64 < LPP && (j * 8 + wave) * 8 < LPP)) glds16_asm(pptr[j], dst + j * 8192);
+          if (all1 || ((j + 1) * 64 < LPP && ((j + 1) * 8 + wave) * 8 < LPP)) glds16_asm(pptr[j + 1], dst + (j + 1) * 8192);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < NPI; ++j)
+        if (j * 64 < LPP) pptr[j] += ((okm >> j) & 1u) << 7;
+    };
+    // weight rows: wave-uniform base (the next K-tile to be requested) + lane offset of (half, piece); a tap is CT elements further on, the next chunk's tap 0 follows tap 8
+    const unsigned wpitch = 9u * CT * (unsigned)sizeof(T);
+    unsigned woff[4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) woff[h * 2 + j] = (unsigned)(h * 128 + j * 8 + lr) * wpitch + ((lpos ^ (((j * 8 + lr) >> 1) & 7)) * 16);
+    const unsigned char* wcur = (const unsigned char*)p.wt + (size_t)(bn * BN + wave * 16) * wpitch + (size_t)cbeg * 128;
+    const long long tapstep = (long long)CT * (long long)sizeof(T), wrapstep = 128 - 8 * tapstep;
+    unsigned bd[2];                                                        // LDS-DMA destination of slot pair (chunk parity) ^ (tap & 1): swapped per chunk
+    bd[0] = lds_base + BOFF + wave * 2048; bd[1] = bd[0] + 2 * P8_SLOT;
+    // fragment addresses
+    const int l31 = lane & 31, fh = lane >> 5;
+    unsigned pcur = DBUF && (cbeg & 1) ? P9_PATCH1 : 0;                    // patch buffer of the current chunk
+    unsigned ab[3][4], fbs[2][4];                                          // A: [column shift kx][k-step], row block and tap as immediates.  B: [slot pair as bd][k-step]
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+        ab[kx][ks] = lds_base + pcur + ((wm * 4 + (l31 >> 4)) * LPW + (l31 & 15)) * 128 + (((2 * ks + fh) ^ ((((l31 & 15) + kx * D) >> 1) & 7)) << 4);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      fbs[0][ks] = lds_base + BOFF + wn * (32 * 128) + l31 * 128 + (((2 * ks + fh) ^ ((l31 >> 1) & 7)) << 4);
+      fbs[1][ks] = fbs[0][ks] + 2 * P8_SLOT;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    issue_patch(pcur);
+    glds16x4_sbase_asm(wcur, woff[0], woff[1], woff[2], woff[3], bd[0]); wcur += tapstep;
+    glds16x4_sbase_asm(wcur, woff[0], woff[1], woff[2], woff[3], bd[1]); wcur += tapstep;
+    wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();
+    constexpr int T0 = FLIP ? 8 : 0, KX0 = T0 % 3, OFF0 = ((T0 / 3) * LPW + KX0) * D * 128;      // tap 0 of a chunk
+    uint4 a[4][2], b0k[4], b1k[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) { a[ks][0] = lds_read16(ab[KX0][ks] + OFF0); a[ks][1] = lds_read16(ab[KX0][ks] + OFF0 + 2 * LPW * 128); b0k[ks] = lds_read16(fbs[0][ks]); }
+
+    // K-tile (chunk, tap t); LAST: the range's last chunk (no next patch, and nothing to request in its taps 7 and 8)
+    auto ktile = [&](auto tc, auto lc) {
+      constexpr int t = decltype(tc)::value; constexpr bool LAST = decltype(lc)::value;
+      constexpr int sp = t & 1;
+      constexpr int tw = FLIP ? 8 - t : t, tn = t == 8 ? 0 : t + 1, twn = FLIP ? 8 - tn : tn;
+      constexpr int kx = tw % 3, kxn = twn % 3;
+      constexpr int off = ((tw / 3) * LPW + kx) * D * 128, offn = ((twn / 3) * LPW + kxn) * D * 128;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int ph = q >> 2, ks = q & 3;
+        const int ih = ph >> 1, jh = (ph == 1 || ph == 2) ? 1 : 0;
+        if (ph == 0) b1k[ks] = lds_read16(fbs[sp][ks] + P8_SLOT);
+        const uint4 bq = (ph == 0 || ph == 3) ? b0k[ks] : b1k[ks];
+        Mma<T>::run(bq, a[ks][0], acc[ih * 2 + 0][jh]);
+        Mma<T>::run(bq, a[ks][1], acc[ih * 2 + 1][jh]);
+        if (ph == 1) { a[ks][0] = lds_read16(ab[kx][ks] + off + 8 * LPW * 128); a[ks][1] = lds_read16(ab[kx][ks] + off + 10 * LPW * 128); }   // image rows 8-15 of the tile
+        if (ph == 2 && ks == 3) {
+          wait_vmcnt<0>();
+          __builtin_amdgcn_s_barrier();
+          if (DBUF && t == 0 && !LAST) issue_patch(P9_PATCH1 - pcur);      // the other buffer: every wave is past the previous chunk
+          if (!(LAST && t >= 7)) { glds16x4_sbase_asm(wcur, woff[0], woff[1], woff[2], woff[3], bd[sp]); wcur += t == 6 ? wrapstep : tapstep; }
+          if (DBUF && t == 8 && !LAST) {                                   // P3 reads the next chunk's first fragments: the lane addresses move to the other buffer
+            const unsigned nxt = P9_PATCH1 - pcur, delta = nxt - pcur;
+#pragma unroll
+            for (int x = 0; x < 3; ++x)
+#pragma unroll
+              for (int y = 0; y < 4; ++y) ab[x][y] += delta;
+            pcur = nxt;
+          }
+        }
+        if (ph == 3 && !(LAST && t == 8)) {
+          b0k[ks] = lds_read16(fbs[sp ^ 1][ks]);                           // B0 of the next K-tile
+          if (t < 8 || DBUF) { a[ks][0] = lds_read16(ab[kxn][ks] + offn); a[ks][1] = lds_read16(ab[kxn][ks] + offn + 2 * LPW * 128); }
+        }
+      }
+    };
+    auto chunk_body = [&](auto lc) {
+      constexpr bool LAST = decltype(lc)::value;
+      // an empty statement per lane address: a value the compiler cannot follow from chunk to chunk, so it does not hoist `address + immediate` of every fragment read out
+      // of the chunk loop into registers of their own (72 of them: spills) but folds the immediate into the read
+#pragma unroll
+      for (int x = 0; x < 3; ++x)
+#pragma unroll
+        for (int y = 0; y < 4; ++y) asm volatile("" : "+v"(ab[x][y]));
+      ktile(p9_int<0>(), lc); ktile(p9_int<1>(), lc); ktile(p9_int<2>(), lc); ktile(p9_int<3>(), lc); ktile(p9_int<4>(), lc);
+      ktile(p9_int<5>(), lc); ktile(p9_int<6>(), lc); ktile(p9_int<7>(), lc); ktile(p9_int<8>(), lc);
+      if constexpr (!LAST) {
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) { const unsigned x = fbs[0][ks]; fbs[0][ks] = fbs[1][ks]; fbs[1][ks] = x; }      // nine taps: the slot pairs change roles
+        { const unsigned x = bd[0]; bd[0] = bd[1]; bd[1] = x; }
+        if constexpr (!DBUF) {
+          __builtin_amdgcn_s_barrier();                                   // every wave is past its last read of the patch
+          issue_patch(0);
+          wait_vmcnt<0>();
+          __builtin_amdgcn_s_barrier();
+#pragma unroll
+          for (int ks = 0; ks < 4; ++ks) { a[ks][0] = lds_read16(ab[KX0][ks] + OFF0); a[ks][1] = lds_read16(ab[KX0][ks] + OFF0 + 2 * LPW * 128); }
+        }
+      }
+    };
+#pragma unroll 1
+    for (int chunk = cbeg; chunk + 1 < nchunk; ++chunk) chunk_body(std::false_type());
+    chunk_body(std::true_type());
+  }
   if constexpr (SPLITK) { conv_store_partial(p, acc, part, bm, bn, wm, wn, lane); return; }
   lds_barrier();
   conv_epilogue_lds<T, BM, BN, 2, 4, true, GATE>(p, acc, bm, bn, wm, wn, lane, tid, smem);
@@ -581,20 +737,29 @@ bool slconv::p9_shape(const ConvGemmParams& p) {
 }
 int slconv::launch_p9(ConvGemmParams& p, hipStream_t st) {
   p.gridM = p.M / 256; p.gridN = p.N / 256; p.tile16 = 1;
+  typedef void (*kern_t)(ConvGemmParams);
+#define P9_ROW(E, F) {{conv_gemm_p9_kernel<E, 0, false>, conv_gemm_p9_kernel<E, 0, false>}, {conv_gemm_p9_kernel<E, 1, false>, conv_gemm_p9_kernel<E, 1, F>}, \
+                      {conv_gemm_p9_kernel<E, 2, false>, conv_gemm_p9_kernel<E, 2, F>}, {conv_gemm_p9_kernel<E, 4, false>, conv_gemm_p9_kernel<E, 4, F>}}
+  // [EPI][0: generic, 1 / 2 / 3: lean d = 1 / 2 / 4][flipped window]; split-K is planned for forward convs only (splitk_parts), so <2, D, true> is not instantiated
+  static const kern_t kern[3][4][2] = {P9_ROW(0, true), P9_ROW(1, true), P9_ROW(2, false)};
+#undef P9_ROW
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_gemm_p9_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(P9_LDS1 > P9_LDS ? P9_LDS1 : P9_LDS));
-    (void)hipFuncSetAttribute((const void*)conv_gemm_p9_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(P9_LDS1 > P9_LDS ? P9_LDS1 : P9_LDS));
-    (void)hipFuncSetAttribute((const void*)conv_gemm_p9_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(P9_LDS1 > P9_LDS ? P9_LDS1 : P9_LDS));
+    for (int e = 0; e < 3; ++e)
+      for (int v = 0; v < 4; ++v)
+        for (int f = 0; f < 2; ++f) (void)hipFuncSetAttribute((const void*)kern[e][v][f], hipFuncAttributeMaxDynamicSharedMemorySize, (int)(P9_LDS1 > P9_LDS ? P9_LDS1 : P9_LDS));
     attr_set = true;
   }
+  // the lean form of the K-tile loop (test hook sl_debug_conv_p9_lean: 0 sends every launch through the generic loop, which gives the same bits); a split-K part holds at least one chunk
+  const bool lean = g_sl_debug.conv_p9_lean && !(p.flags & 8) && (p.ksplit <= 1 || (p.mode == 0 && p.ksplit <= p.C1 / 64));
+  const int v = !lean ? 0 : p.dil == 1 ? 1 : p.dil == 2 ? 2 : 3, f = lean && p.mode != 0;
+  const size_t lds = p.dil == 1 ? P9_LDS1 : P9_LDS;
   if (p.ksplit > 1) {
-    hipLaunchKernelGGL(conv_gemm_p9_kernel<2>, dim3(p.gridM * p.gridN * p.ksplit), dim3(512), p.dil == 1 ? P9_LDS1 : P9_LDS, st, p);
+    hipLaunchKernelGGL(kern[2][v][f], dim3(p.gridM * p.gridN * p.ksplit), dim3(512), lds, st, p);
     SL_LAUNCH_CHECK("conv_gemm_p9_kernel (split-K)");
     return launch_splitk_finish(p, st);
   }
-  if (p.gate) hipLaunchKernelGGL(conv_gemm_p9_kernel<1>, dim3(p.gridM * p.gridN), dim3(512), p.dil == 1 ? P9_LDS1 : P9_LDS, st, p);
-  else        hipLaunchKernelGGL(conv_gemm_p9_kernel<0>, dim3(p.gridM * p.gridN), dim3(512), p.dil == 1 ? P9_LDS1 : P9_LDS, st, p);
+  hipLaunchKernelGGL(kern[p.gate ? 1 : 0][v][f], dim3(p.gridM * p.gridN), dim3(512), lds, st, p);
   SL_LAUNCH_CHECK("conv_gemm_p9_kernel");
   return 0;
 }
