@@ -6,6 +6,7 @@ nn.Conv2d / nn.BatchNorm2d modules are used purely as parameter holders (state_d
 reference); their own forward is never called.
 """
 import os
+from collections import namedtuple
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -209,15 +210,43 @@ def sync_world(bn):
     return w if (w > 1 or _SYNC_BN == 'force') else 0
 
 
+# What the forward of one BatchNorm(+ReLU) layer keeps for its backward: the conv output c the BatchNorm read, its batch (or running) mean / invstd and the ReLU bits
+# of its output (None: no ReLU, or the mask was not asked for).
+BNLayer = namedtuple('BNLayer', 'c mean invstd bits')
+
+
+class Grad:
+    """A gradient on its way down the backward chain: the tensor t, its ReLU gate still to be applied -- `bits` (the bit mask of the forward) or `act` (the activation
+    itself: y > 0) or neither (no ReLU, or gated already) -- and the BatchNorm-backward column sums that came with it from the epilogue that wrote it (part; part2: those
+    of a second BatchNorm behind the same ReLU).  A gradient that arrives with column sums is already gated."""
+    __slots__ = ('t', 'bits', 'act', 'part', 'part2')
+
+    def __init__(self, t, part=None, part2=None, bits=None, act=None):
+        assert (part is None or (bits is None and act is None)) and (bits is None or act is None) and (part2 is None or part is not None)
+        self.t, self.bits, self.act, self.part, self.part2 = t, bits, act, part, part2
+
+
+def _save(ctx, *items):
+    """ctx.save_for_backward of tensors, None, BNLayer records and lists of tensors; _saved(ctx) gives the same sequence back."""
+    groups = [it if isinstance(it, (list, BNLayer)) else [it] for it in items]
+    ctx.saved_form = [(type(it), len(g)) for it, g in zip(items, groups)]
+    ctx.save_for_backward(*[t for g in groups for t in g])
+
+
+def _saved(ctx):
+    sv = iter(ctx.saved_tensors)
+    groups = [(kind, [next(sv) for _ in range(n)]) for kind, n in ctx.saved_form]
+    return [BNLayer(*ts) if kind is BNLayer else ts if kind is list else ts[0] for kind, ts in groups]
+
+
 def conv_bn_fwd(x, conv, bn, relu, residual=None, x2=None, out=None, want_mask=False):
+    """y = act(bn(conv(x)) (+ residual)) -> (y, BNLayer); want_mask: the record carries the ReLU bits."""
     wf, _ = prepared(conv.weight, x.dtype)
     c, part = ops.conv2d_fwd(x, wf, spec_of(conv), x2=x2, want_stats=bn.training)
     mean, invstd, scale, shift = _bn_coeffs(bn, part, c.numel() // c.shape[-1])
-    if want_mask:
-        y, mask = ops.bn_act(c, scale, shift, residual=residual, relu=relu, out=out, want_mask=True)
-        return c, y, mean, invstd, mask
-    y = ops.bn_act(c, scale, shift, residual=residual, relu=relu, out=out)
-    return c, y, mean, invstd
+    r = ops.bn_act(c, scale, shift, residual=residual, relu=relu, out=out, want_mask=want_mask)
+    y, mask = r if want_mask else (r, None)
+    return y, BNLayer(c, mean, invstd, mask)
 
 
 def conv_bn_infer(x, conv, bn, relu, residual=None, x2=None, out=None):
@@ -255,57 +284,59 @@ _BN_DUAL = _BN_FUSE        # test hook: bn3 + downsample BN backward in one swee
 _BN_CROSS = _BN_FUSE       # test hook: bn3's column sums from the NEXT block's conv1 data-gradient epilogue (pixel-stationary kernel MODE 5)
 
 
-def _conv_dgrad(dc, x, wb, spec, addend, x2, dx_out, addend_bits, below, prev3, prevd, dx_half, addend_half):
-    """The data gradient of conv_bn_bwd behind its BatchNorm part (dc: the gradient at the conv output, wb: the weight in the data-gradient layout): ONE launch, chosen by the first route that applies.
-    -> (dx, partial_below).  The fused routes write a fresh dx from a single source; where the library does not serve the shape they return None and the plain form runs."""
-    hw = x.shape[1:3]
-    fresh = x2 is None and dx_out is None
-    cross = prev3 is not None and addend is not None and addend_bits is None and fresh
-    r = None
+def _bn_bwd(g, layer, bn, need_w, want_dres=False, out=None):
+    """BatchNorm(+ReLU) backward of the Grad g through `layer` (the BNLayer of module bn), without a reduce pass when g brought its column sums -> (dc, dgamma, dbeta, dres):
+    the gradient at the conv output (in `out` if given), the parameter gradients (in their bucket views where there are any), with want_dres the gated g as a tensor."""
+    gg, gb = (grad_dst(bn.weight), grad_dst(bn.bias)) if need_w else (None, None)
+    dc, dres, dgamma, dbeta = ops.bn_bwd(g.t, g.act, layer.c, layer.mean, layer.invstd, bn.weight, train=bn.training, want_dres=want_dres, mask=g.bits, out=out,
+                                         sync_world=sync_world(bn), dgamma_out=gg, dbeta_out=gb, pre_partial=g.part)
+    return dc, grad_alias(dgamma, gg), grad_alias(dbeta, gb), dres
+
+
+def _bn_bwd2(g, layer1, bn1, layer2, bn2, need_w):
+    """_bn_bwd for two BatchNorms whose outputs were added before one ReLU, in one sweep over g per pass (ops.bn_bwd2) -> (dc1, dgamma1, dbeta1), (dc2, dgamma2, dbeta2)."""
+    o1, o2 = [(grad_dst(bn.weight), grad_dst(bn.bias)) if need_w else (None, None) for bn in (bn1, bn2)]
+    dc1, dg1, db1, dc2, dg2, db2 = ops.bn_bwd2(g.t, g.bits, layer1.c, layer1.mean, layer1.invstd, bn1.weight, layer2.c, layer2.mean, layer2.invstd, bn2.weight, o1, o2,
+                                               pre_partials=None if g.part is None else (g.part, g.part2))
+    return (dc1, grad_alias(dg1, o1[0]), grad_alias(db1, o1[1])), (dc2, grad_alias(dg2, o2[0]), grad_alias(db2, o2[1]))
+
+
+def _conv_wgrad(conv, x, dc, x2=None):
+    """Weight gradient of conv on input x (x2: the second half of a virtual concat) from dc, the gradient at its output, written to its bucket view where there is one."""
+    gw = grad_dst(conv.weight)
+    return grad_alias(ops.conv2d_bwd_weight(x, dc, spec_of(conv), x2=x2, out=gw), gw)
+
+
+def _conv_dgrad(dc, conv, x, below=None, addend=None, x2=None, prev=None, dx_half=False, addend_half=False):
+    """Data gradient of conv on input x from dc, the gradient at its output: ONE launch, chosen by the first route that applies.  -> Grad.  The fused routes write a
+    fresh dx from a single source; where the library does not serve the shape they return None and the plain form runs.
+    below: (BNLayer, module) of the BatchNorm + ReLU that produced x.  In train mode, where the kernel has the staged store phase, its epilogue gates dx with those
+    bits and emits that layer's column sums; otherwise the result carries the bits as its gate.
+    addend: a Grad (tensor + optional bits gate) accumulated into dx by the epilogue.
+    prev: the _BlockLink of the PREVIOUS bottleneck (bn3: its bn3 + output ReLU; bnd: its downsample BatchNorm behind the same ReLU, or None): dx, with its addend,
+    which must be gated already, is that block's incoming gradient; where the pixel-stationary kernel serves the shape it is gated there and reduced against c3
+    (and cd): the result carries that block's column sums."""
+    spec, hw = spec_of(conv), x.shape[1:3]
+    wb = prepared(conv.weight, dc.dtype)[1]
+    add, add_bits = (addend.t, addend.bits) if addend is not None else (None, None)
     if dx_half:
         # a 1x1 stride-2 conv (a stage entry's downsample branch): its data gradient is non-zero at the even positions only -- return the DENSE gradient on the conv's own
         # output grid; the consumer adds it at the even positions (ops.conv2d_bwd_data_addend_half), the zero-filled tensor is never written
-        r = ops.conv2d_bwd_data(dc, wb, ConvSpec(spec.cin, spec.cout, 1, 1, 0, 1), dc.shape[1:3]), None
-    elif addend_half:
-        r = ops.conv2d_bwd_data_addend_half(dc, wb, spec, hw, addend, prev3)
-    elif below is not None and _BN_FUSE and addend is None and fresh:
-        r = ops.conv2d_bwd_data_bnstat(dc, wb, spec, hw, *below)
-    elif cross and prevd is not None:     # the block in front is a stage's first one: bn3 + downsample BatchNorm behind its ReLU, both reduced here (partial_below is a pair)
-        r = ops.conv2d_bwd_data_addend_bnstat2(dc, wb, spec, hw, addend, *prev3, *prevd)
-        r = r and (r[0], (r[1], r[2]))
+        return Grad(ops.conv2d_bwd_data(dc, wb, ConvSpec(spec.cin, spec.cout, 1, 1, 0, 1), dc.shape[1:3]))
+    (lb, bnb), (l3, ld) = below or (None, None), (prev.bn3, prev.bnd) if prev is not None else (None, None)
+    cross = l3 is not None and add is not None and add_bits is None and x2 is None
+    r = None
+    if addend_half:
+        r = ops.conv2d_bwd_data_addend_half(dc, wb, spec, hw, add, None if l3 is None else (l3.bits, l3.c, l3.mean, l3.invstd))
+    elif lb is not None and bnb.training and _BN_FUSE and add is None and x2 is None:
+        r = ops.conv2d_bwd_data_bnstat(dc, wb, spec, hw, lb.bits, lb.c, lb.mean, lb.invstd)
+    elif cross and ld is not None:        # the block in front is a stage's first one: bn3 + downsample BatchNorm behind its ReLU, both reduced here (the result has part2)
+        r = ops.conv2d_bwd_data_addend_bnstat2(dc, wb, spec, hw, add, l3.bits, l3.c, l3.mean, l3.invstd, ld.c, ld.mean, ld.invstd)
     elif cross:
-        r = ops.conv2d_bwd_data_addend_bnstat(dc, wb, spec, hw, addend, *prev3)
+        r = ops.conv2d_bwd_data_addend_bnstat(dc, wb, spec, hw, add, l3.bits, l3.c, l3.mean, l3.invstd)
     if r is None:
-        r = ops.conv2d_bwd_data(dc, wb, spec, hw, addend=addend, addend_mask=addend_bits, C1=(x.shape[3] if x2 is not None else None), out=dx_out), None
-    return r
-
-
-def conv_bn_bwd(dy, y_mask, c, x, conv, bn, mean, invstd, need_dx, need_dw, want_dres=False, addend=None, x2=None, dx_out=None,
-                bits=None, addend_bits=None, pre_partial=None, below=None, bn_done=None, prev3=None, prevd=None, dx_half=False, addend_half=False):
-    """Backward of y = act(bn(conv(x))).  Returns (dx, dw, dgamma, dbeta, dres, partial_below).
-    ReLU gate of dy: `bits` (bit mask from the forward) or `y_mask` (the activation itself).  `addend` (+ optional
-    `addend_bits` gate) is accumulated into dx by the dgrad epilogue.
-    pre_partial: dy is ALREADY gated and the BN-backward column sums of this layer were produced by the epilogue that wrote it (no reduce pass).
-    below = (bits, c, mean, invstd) of the BatchNorm + ReLU that produced x: when the data gradient of this conv runs on a kernel with the staged
-    store phase, its epilogue gates dx with those bits and emits that layer's column sums (partial_below is then not None and dx is gated).
-    bn_done = (dc, dgamma, dbeta): the BatchNorm part was already done by the caller (ops.bn_bwd2: two BatchNorms behind one ReLU in one sweep).
-    prev3 = (bits, c3, mean, invstd) of the PREVIOUS bottleneck's bn3 + output ReLU: dx (with its addend, which must be gated already) is that block's incoming
-    gradient; where the pixel-stationary kernel serves the shape it is gated there and reduced against c3 (partial_below = that block's bn3 column sums)."""
-    gw, gg, gb = (grad_dst(conv.weight), grad_dst(bn.weight), grad_dst(bn.bias)) if need_dw else (None, None, None)
-    if bn_done is not None:
-        (dc, dgamma, dbeta), dres = bn_done, None
-    else:
-        dc, dres, dgamma, dbeta = ops.bn_bwd(dy, None if (bits is not None or pre_partial is not None) else y_mask, c, mean, invstd, bn.weight, train=bn.training,
-                                             want_dres=want_dres, mask=None if pre_partial is not None else bits, sync_world=sync_world(bn), dgamma_out=gg, dbeta_out=gb,
-                                             pre_partial=pre_partial)
-        dgamma, dbeta = grad_alias(dgamma, gg), grad_alias(dbeta, gb)
-    spec = spec_of(conv)
-    dx = dw = part_below = None
-    if need_dw:
-        dw = grad_alias(ops.conv2d_bwd_weight(x, dc, spec, x2=x2, out=gw), gw)
-    if need_dx:
-        dx, part_below = _conv_dgrad(dc, x, prepared(conv.weight, c.dtype)[1], spec, addend, x2, dx_out, addend_bits, below, prev3, prevd, dx_half, addend_half)
-    return dx, dw, dgamma, dbeta, dres, part_below
+        r = (ops.conv2d_bwd_data(dc, wb, spec, hw, addend=add, addend_mask=add_bits, C1=(x.shape[3] if x2 is not None else None)), None)
+    return Grad(*r, bits=lb.bits if (lb is not None and r[1] is None) else None)            # the epilogue did not gate: the layer below's bits go with the result
 
 
 # ------------------------------------------------------------------------------------------------ stem
@@ -319,22 +350,20 @@ class StemFn(torch.autograd.Function):
         mean, invstd, scale, shift = _bn_coeffs(bn, part, c0.numel() // 64)
         pooled, idx = ops.stem_bn_relu_pool(c0, scale, shift, want_idx=True)
         ctx.net = net
-        ctx.save_for_backward(img, c0, idx, mean, invstd, scale, shift)
+        _save(ctx, img, BNLayer(c0, mean, invstd, None), idx, scale, shift)
         return pooled
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dp):
-        img, c0, idx, mean, invstd, scale, shift = ctx.saved_tensors
-        bn = ctx.net.bn1
-        gg, gb = grad_dst(bn.weight), grad_dst(bn.bias)
+        img, l0, idx, scale, shift = _saved(ctx)
         if _BN_FUSE:          # bn1's reduce pass rides in the pool / ReLU backward, which reads c0 anyway (round 5)
-            g0, pp = ops.stem_pool_relu_bwd_bnstat(dp.contiguous(), idx, c0, scale, shift, mean, invstd)
+            g0, pp = ops.stem_pool_relu_bwd_bnstat(dp.contiguous(), idx, l0.c, scale, shift, l0.mean, l0.invstd)
         else:
-            g0, pp = ops.stem_pool_relu_bwd(dp.contiguous(), idx, c0, scale, shift), None
-        dc0, _, dgamma, dbeta = ops.bn_bwd(g0, None, c0, mean, invstd, bn.weight, train=bn.training, sync_world=sync_world(bn), dgamma_out=gg, dbeta_out=gb, pre_partial=pp)
+            g0, pp = ops.stem_pool_relu_bwd(dp.contiguous(), idx, l0.c, scale, shift), None
+        dc0, dgamma, dbeta, _ = _bn_bwd(Grad(g0, part=pp), l0, ctx.net.bn1, need_w=True)     # bn1's gradients are produced whether or not conv1's weight takes one
         dw = ops.stem_conv_bwd_weight(img, dc0) if ctx.needs_input_grad[1] else None
-        return None, dw, grad_alias(dgamma, gg), grad_alias(dbeta, gb), None, None
+        return None, dw, dgamma, dbeta, None, None
 
 
 class DeepStemFn(torch.autograd.Function):
@@ -358,33 +387,33 @@ class DeepStemFn(torch.autograd.Function):
         c1, part = ops.stem3_conv_fwd(img, w1, dtype, want_stats=bn1.training)
         m1, i1, sc1, sh1 = _bn_coeffs(bn1, part, c1.numel() // 64)
         a1, k1 = ops.bn_act(c1, sc1, sh1, relu=True, want_mask=True)
-        c2, a2, m2, i2, k2 = conv_bn_fwd(a1, net.conv2, bn2, relu=True, want_mask=True)
+        a2, l2 = conv_bn_fwd(a1, net.conv2, bn2, relu=True, want_mask=True)
         c3, part = ops.conv2d_fwd(a2, wf3, spec_of(net.conv3), want_stats=bn3.training)
         m3, i3, sc3, sh3 = _bn_coeffs(bn3, part, c3.numel() // c3.shape[-1])
         pooled, idx = ops.stem_bn_relu_pool_c(c3, sc3, sh3, want_idx=True)        # bn3 + relu3 + maxpool in one pass: relu3's output never exists
         ctx.net = net
-        ctx.save_for_backward(img, c1, a1, k1, m1, i1, c2, a2, k2, m2, i2, c3, idx, m3, i3, sc3, sh3)
+        _save(ctx, img, BNLayer(c1, m1, i1, k1), a1, l2, a2, BNLayer(c3, m3, i3, None), idx, sc3, sh3)
         return pooled
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dp):
-        img, c1, a1, k1, m1, i1, c2, a2, k2, m2, i2, c3, idx, m3, i3, sc3, sh3 = ctx.saved_tensors
+        img, l1, a1, l2, a2, l3, idx, sc3, sh3 = _saved(ctx)
         net = ctx.net
         need_w = ctx.needs_input_grad[3]            # the stem's parameters are all-or-nothing frozen, like a bottleneck's
         # pool + relu3 backward with bn3's column sums in the same sweep over c3; conv3's and conv2's data gradients gate with the ReLU bits below and
-        # emit the next BatchNorm's column sums where their kernel has the staged store phase (conv_bn_bwd: below)
-        g3, p3 = ops.stem_pool_relu_bwd_bnstat_c(dp.contiguous(), idx, c3, sc3, sh3, m3, i3)
-        da2, dw3, dg3, db3, _, p2 = conv_bn_bwd(g3, None, c3, a2, net.conv3, net.bn3, m3, i3, True, need_w, pre_partial=p3,
-                                                below=(k2, c2, m2, i2) if net.bn2.training else None)
-        da1, dw2, dg2, db2, _, p1 = conv_bn_bwd(da2, None, c2, a1, net.conv2, net.bn2, m2, i2, True, need_w, bits=None if p2 is not None else k2, pre_partial=p2,
-                                                below=(k1, c1, m1, i1) if net.bn1.training else None)
-        bn1 = net.bn1
-        gw, gg, gb = (grad_dst(net.conv1.weight), grad_dst(bn1.weight), grad_dst(bn1.bias)) if need_w else (None, None, None)
-        dc1, _, dg1, db1 = ops.bn_bwd(da1, None, c1, m1, i1, bn1.weight, train=bn1.training, mask=None if p1 is not None else k1, sync_world=sync_world(bn1),
-                                      dgamma_out=gg, dbeta_out=gb, pre_partial=p1)
+        # emit the next BatchNorm's column sums where their kernel has the staged store phase (_conv_dgrad: below)
+        g3, p3 = ops.stem_pool_relu_bwd_bnstat_c(dp.contiguous(), idx, l3.c, sc3, sh3, l3.mean, l3.invstd)
+        dc3, dg3, db3, _ = _bn_bwd(Grad(g3, part=p3), l3, net.bn3, need_w)
+        dw3 = _conv_wgrad(net.conv3, a2, dc3) if need_w else None
+        da2 = _conv_dgrad(dc3, net.conv3, a2, below=(l2, net.bn2))
+        dc2, dg2, db2, _ = _bn_bwd(da2, l2, net.bn2, need_w)
+        dw2 = _conv_wgrad(net.conv2, a1, dc2) if need_w else None
+        da1 = _conv_dgrad(dc2, net.conv2, a1, below=(l1, net.bn1))
+        dc1, dg1, db1, _ = _bn_bwd(da1, l1, net.bn1, need_w)
+        gw = grad_dst(net.conv1.weight) if need_w else None
         dw1 = grad_alias(ops.stem3_conv_bwd_weight(img, dc1, out=gw), gw) if need_w else None        # the image needs no data gradient
-        return (None, None, None, dw1, grad_alias(dg1, gg), grad_alias(db1, gb), dw2, dg2, db2, dw3, dg3, db3)
+        return (None, None, None, dw1, dg1, db1, dw2, dg2, db2, dw3, dg3, db3)
 
 
 def deep_stem_params(net):
@@ -394,14 +423,15 @@ def deep_stem_params(net):
 # ------------------------------------------------------------------------------------------------ bottleneck
 class _BlockLink:
     """What two consecutive bottlenecks of ONE forward pass hand each other for the cross-block bn3 fusion (_BN_CROSS).  The producer's forward makes it
-    (bn3: ReLU bits, c3, mean, invstd of its output BatchNorm; out_ptr / out_shape: the tensor it returned), the consumer's forward picks it up from the
-    producer module -- checked against its own input -- and keeps it in its ctx; the consumer's backward leaves the column sums its conv1 data-gradient
-    epilogue produced in pre3 (with the address of the gradient tensor they belong to), the producer's backward takes them.  Nothing is read from module
-    state at backward time."""
+    (bn3: the BNLayer of its output BatchNorm + ReLU; bnd: that of the downsample BatchNorm behind the same ReLU, a stage's first block; out_ptr / out_shape: the
+    tensor it returned), the consumer's forward picks it up from the producer module -- checked against its own input -- and keeps it in its ctx; the consumer's
+    backward leaves the Grad its conv1 data-gradient epilogue produced (the gradient tensor with the column sums that belong to it) in pre3, the producer's
+    backward takes it.  Nothing is read from module state at backward time.  pre3 holds the gradient tensor itself, not its address (an address can be reused):
+    where the producer's backward never runs, the tensor lives until the producer module's next forward drops the link."""
     __slots__ = ('bn3', 'bnd', 'pre3', 'out_ptr', 'out_shape')
 
     def __init__(self):
-        self.bn3 = self.bnd = self.pre3 = self.out_ptr = self.out_shape = None      # bnd: (cd, mean, invstd) of the downsample BatchNorm behind the same ReLU (a stage's first block)
+        self.bn3 = self.bnd = self.pre3 = self.out_ptr = self.out_shape = None
 
 
 class BottleneckFn(torch.autograd.Function):
@@ -421,95 +451,83 @@ class BottleneckFn(torch.autograd.Function):
             a2 = conv_bn_infer(a1, blk.conv2, blk.bn2, relu=True)
             res = x if blk.downsample is None else conv_bn_infer(x, blk.downsample[0], blk.downsample[1], relu=False)
             return conv_bn_infer(a2, blk.conv3, blk.bn3, relu=blk.last_relu, residual=res)
-        c1, a1, m1, i1, k1 = conv_bn_fwd(x, blk.conv1, blk.bn1, relu=True, want_mask=True)
-        c2, a2, m2, i2, k2 = conv_bn_fwd(a1, blk.conv2, blk.bn2, relu=True, want_mask=True)
+        a1, l1 = conv_bn_fwd(x, blk.conv1, blk.bn1, relu=True, want_mask=True)
+        a2, l2 = conv_bn_fwd(a1, blk.conv2, blk.bn2, relu=True, want_mask=True)
         if blk.downsample is not None:
-            cd, res, md, idd = conv_bn_fwd(x, blk.downsample[0], blk.downsample[1], relu=False)
+            res, ld = conv_bn_fwd(x, blk.downsample[0], blk.downsample[1], relu=False)
         else:
-            cd, res, md, idd = None, x, None, None
-        c3, out, m3, i3, k3 = conv_bn_fwd(a2, blk.conv3, blk.bn3, relu=blk.last_relu, residual=res, want_mask=True)
+            res, ld = x, None
+        out, l3 = conv_bn_fwd(a2, blk.conv3, blk.bn3, relu=blk.last_relu, residual=res, want_mask=True)
         ctx.blk = blk
         ctx.has_ds = blk.downsample is not None
         # the next bottleneck's backward produces this block's incoming gradient: it may gate it and reduce it against c3 right there (_BN_CROSS)
         link = ctx.link = blk.__dict__['_sl_link'] = _BlockLink()
         dual_ok = ctx.has_ds and _BN_DUAL and blk.downsample[1].training and not sync_world(blk.bn3)      # the consumer's one-sweep dual backward (ops.bn_bwd2) must apply
-        link.bn3 = (k3, c3, m3, i3) if (_BN_CROSS and k3 is not None and blk.bn3.training and (not ctx.has_ds or dual_ok) and any(ctx.needs_input_grad)) else None
-        link.bnd = (cd, md, idd) if (link.bn3 is not None and ctx.has_ds) else None
+        link.bn3 = l3 if (_BN_CROSS and l3.bits is not None and blk.bn3.training and (not ctx.has_ds or dual_ok) and any(ctx.needs_input_grad)) else None
+        link.bnd = ld if (link.bn3 is not None and ctx.has_ds) else None
         link.out_ptr, link.out_shape = out.data_ptr(), tuple(out.shape)
-        saved = [x, c1, a1, m1, i1, k1, c2, a2, m2, i2, k2, c3, m3, i3]
-        if ctx.has_ds:
-            saved += [cd, md, idd]
-        if k3 is not None:
-            saved.append(k3)
-        ctx.save_for_backward(*saved)
+        _save(ctx, x, l1, a1, l2, a2, l3, ld)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
         blk = ctx.blk
-        sv = ctx.saved_tensors
-        x, c1, a1, m1, i1, k1, c2, a2, m2, i2, k2, c3, m3, i3 = sv[:14]
-        k3 = sv[-1] if blk.last_relu else None        # ReLU bits of the block output (gates BOTH the bn3 and the shortcut gradient)
+        x, l1, a1, l2, a2, l3, ld = _saved(ctx)       # l3.bits: ReLU bits of the block output (they gate BOTH the bn3 and the shortcut gradient)
         dout = dout.contiguous()
         need_w = ctx.needs_input_grad[2]            # params are all-or-nothing frozen in this model family
         need_x = ctx.needs_input_grad[0]
-        # the data gradients of conv3 and conv2 gate their result with the ReLU bits of the layer below and emit its BN-backward column sums in the epilogue
-        # (where the kernel has the staged store phase: layer3 / layer4 at the bench shapes): that layer's reduce pass over (g, c) disappears
+        # bn3 and the downsample BN sit behind the same ReLU: one sweep over dout and its bits for both reduces, one for both applies (ops.bn_bwd2)
+        dual = ctx.has_ds and _BN_DUAL and l3.bits is not None and blk.bn3.training and blk.downsample[1].training and not sync_world(blk.bn3)
         # this block's incoming gradient may have been gated and reduced against c3 by the block behind it (its conv1 data gradient epilogue): the tensor
         # autograd hands over must be exactly the one that epilogue wrote (a second consumer of this block's output would have made autograd sum into a new one)
         link = ctx.link
         pre3, link.pre3, link.bn3, link.bnd = link.pre3, None, None, None
-        p3 = pdual = None
-        if pre3 is not None and pre3[0] == dout.data_ptr() and pre3[1] == tuple(dout.shape):
-            if not ctx.has_ds and not isinstance(pre3[2], tuple):
-                p3, k3 = pre3[2], None               # dout is gated already: no bits for bn3, none for the identity shortcut
-            elif ctx.has_ds and isinstance(pre3[2], tuple):
-                pdual = pre3[2]                      # ... and reduced against c3 AND the downsample BatchNorm's input (round 5: the dual store loop of the block behind)
-        done3 = doned = None
-        if ctx.has_ds and _BN_DUAL and k3 is not None and blk.bn3.training and blk.downsample[1].training and not sync_world(blk.bn3):
-            # bn3 and the downsample BN sit behind the same ReLU: one sweep over dout and its bits for both reduces, one for both applies (ops.bn_bwd2)
-            cd, md, idd = sv[14:17]
-            bnd = blk.downsample[1]
-            g3, b3, gd_, bd_ = (grad_dst(blk.bn3.weight), grad_dst(blk.bn3.bias), grad_dst(bnd.weight), grad_dst(bnd.bias)) if need_w else (None,) * 4
-            dc3, dg3_, db3_, dcd, dgd_, dbd_ = ops.bn_bwd2(dout, None if pdual is not None else k3, c3, m3, i3, blk.bn3.weight, cd, md, idd, bnd.weight, (g3, b3), (gd_, bd_),
-                                                           pre_partials=pdual)
-            done3 = (dc3, grad_alias(dg3_, g3), grad_alias(db3_, b3))
-            doned = (dcd, grad_alias(dgd_, gd_), grad_alias(dbd_, bd_))
+        g3 = Grad(dout, bits=l3.bits)
+        # (one set of column sums serves a block with an identity shortcut; a pair, from the dual store loop of the block behind, bn3 AND the downsample BatchNorm)
+        if pre3 is not None and pre3.t.data_ptr() == dout.data_ptr() and pre3.t.shape == dout.shape and (dual if pre3.part2 is not None else not ctx.has_ds):
+            g3 = pre3                                # dout is gated already: no bits for bn3, none for the identity shortcut
+        dres = None
+        if dual:
+            (dc3, dg3, db3), (dcd, dgd, dbd) = _bn_bwd2(g3, l3, blk.bn3, ld, blk.downsample[1], need_w)
         # the block in front of this one can take its bn3 column sums from this block's conv1 data gradient only if the shortcut gradient enters that epilogue
-        # gated already: either dout arrived gated (p3), or the shortcut is a downsample branch, or -- the start of a chain inside a stage -- bn3's apply pass
+        # gated already: either dout arrived gated (g3.part), or the shortcut is a downsample branch, or -- the start of a chain inside a stage -- bn3's apply pass
         # also writes the gated gradient (one extra write of dout's size, repaid by every block further up the stage)
-        plink = ctx.prev_link
-        prev3 = plink.bn3 if (plink is not None and need_x and _BN_CROSS) else None
-        if prev3 is not None and (prev3[1].shape != x.shape or prev3[1].dtype != x.dtype or not ops.conv2d_bwd_data_addend_bnstat_ok(x, spec_of(blk.conv1))):
-            prev3 = None
-        prevd = plink.bnd if prev3 is not None else None
-        want_dres = prev3 is not None and not ctx.has_ds and k3 is not None and p3 is None and done3 is None
-        da2, dw3, dg3, db3, dres, p2 = conv_bn_bwd(dout, None, c3, a2, blk.conv3, blk.bn3, m3, i3, True, need_w, bits=k3, pre_partial=p3,
-                                                   below=(k2, c2, m2, i2) if blk.bn2.training else None, bn_done=done3, want_dres=want_dres)
-        da1, dw2, dg2, db2, _, p1 = conv_bn_bwd(da2, None, c2, a1, blk.conv2, blk.bn2, m2, i2, True, need_w, bits=None if p2 is not None else k2, pre_partial=p2,
-                                                below=(k1, c1, m1, i1) if blk.bn1.training else None)
-        grads_ds = ()
+        prev = ctx.prev_link if (need_x and _BN_CROSS) else None
+        if prev is not None and (prev.bn3 is None or prev.bn3.c.shape != x.shape or prev.bn3.c.dtype != x.dtype
+                                 or not ops.conv2d_bwd_data_addend_bnstat_ok(x, spec_of(blk.conv1))):
+            prev = None
+        if not dual:
+            dc3, dg3, db3, dres = _bn_bwd(g3, l3, blk.bn3, need_w, want_dres=prev is not None and not ctx.has_ds and g3.bits is not None)
+        # the data gradients of conv3 and conv2 gate their result with the ReLU bits of the layer below and emit its BN-backward column sums in the epilogue
+        # (where the kernel has the staged store phase: layer3 / layer4 at the bench shapes): that layer's reduce pass over (g, c) disappears
+        dw3 = _conv_wgrad(blk.conv3, a2, dc3) if need_w else None
+        da2 = _conv_dgrad(dc3, blk.conv3, a2, below=(l2, blk.bn2))
+        dc2, dg2, db2, _ = _bn_bwd(da2, l2, blk.bn2, need_w)
+        dw2 = _conv_wgrad(blk.conv2, a1, dc2) if need_w else None
+        da1 = _conv_dgrad(dc2, blk.conv2, a1, below=(l1, blk.bn1))
+        grads_ds, half = (), False
         if ctx.has_ds:
-            cd, md, idd = sv[14:17]
             dsc = blk.downsample[0]
             half = (_DS_HALF and need_x and dsc.kernel_size == (1, 1) and dsc.stride == (2, 2) and dsc.padding == (0, 0) and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0
                     and ops.conv2d_bwd_data_addend_half_ok(x, spec_of(blk.conv1)))
-            dxd, dwd, dgd, dbd, _, _ = conv_bn_bwd(dout, None, cd, x, dsc, blk.downsample[1], md, idd, need_x, need_w, bits=k3, bn_done=doned, dx_half=half)
+            if not dual:
+                dcd, dgd, dbd, _ = _bn_bwd(g3, ld, blk.downsample[1], need_w)
+            dwd = _conv_wgrad(dsc, x, dcd) if need_w else None
+            shortcut = _conv_dgrad(dcd, dsc, x, dx_half=half) if need_x else None
             grads_ds = (dwd, dgd, dbd)
-            addend, abits = dxd, None
         elif dres is not None:
-            addend, abits = dres, None              # identity shortcut, gated by bn3's apply pass (chain start, see above)
+            shortcut = Grad(dres)                   # identity shortcut, gated by bn3's apply pass (chain start, see above)
         else:
-            addend, abits = dout, k3                # identity shortcut: dout * relu'(out), gated inside the dgrad epilogue (k3 None: dout arrived gated)
-        if abits is not None:
-            prev3 = None
-        dx, dw1, dg1, db1, _, pp = conv_bn_bwd(da1, None, c1, x, blk.conv1, blk.bn1, m1, i1, need_x, need_w,
-                                               addend=addend if need_x else None, addend_bits=abits if need_x else None, bits=None if p1 is not None else k1, pre_partial=p1,
-                                               prev3=prev3, prevd=prevd, addend_half=ctx.has_ds and half)
-        if pp is not None and prev3 is not None:
-            plink.pre3 = (dx.data_ptr(), tuple(dx.shape), pp)
-        return (dx, None, dw1, dg1, db1, dw2, dg2, db2, dw3, dg3, db3) + grads_ds
+            shortcut = Grad(dout, bits=g3.bits)     # identity shortcut: dout * relu'(out), gated inside the dgrad epilogue (no bits: dout arrived gated, or no ReLU)
+        if shortcut is not None and shortcut.bits is not None:
+            prev = None
+        dc1, dg1, db1, _ = _bn_bwd(da1, l1, blk.bn1, need_w)
+        dw1 = _conv_wgrad(blk.conv1, x, dc1) if need_w else None
+        gx = _conv_dgrad(dc1, blk.conv1, x, addend=shortcut, prev=prev, addend_half=half) if need_x else None
+        if prev is not None and gx.part is not None:            # (prev is None where need_x is false)
+            prev.pre3 = gx
+        return (gx.t if need_x else None, None, dw1, dg1, db1, dw2, dg2, db2, dw3, dg3, db3) + grads_ds
 
 
 def bottleneck_params(blk):
@@ -577,15 +595,14 @@ class PPMFn(torch.autograd.Function):
             cb, part = ops.conv2d_fwd(x4, wf4, spec4, pre_addend=gpri, want_stats=bt[1].training)
             mb, ib, scale, shift = _bn_coeffs(bt[1], part, cb.numel() // N)
             ab, kb = ops.bn_act(cb, scale, shift, relu=True, want_mask=True)
-            priors = cb.new_empty(0)
+            priors, lb = None, BNLayer(cb, mb, ib, kb)
         else:
             priors = ops.ppm_upsample_fwd(stage_act, x4.shape, sizes, x4.dtype)
-            cb, ab, mb, ib = conv_bn_fwd(priors, bt[0], bt[1], relu=True, x2=x4)
-            kb = cb.new_empty(0, dtype=torch.uint8)
+            ab, lb = conv_bn_fwd(priors, bt[0], bt[1], relu=True, x2=x4)          # no ReLU bits: the backward gates with ab itself
         wf, _ = prepared(bt[3].weight, x4.dtype)
         feat, _ = ops.conv2d_fwd(ab, wf, spec_of(bt[3]), bias=bt[3].bias.detach())
         ctx.dec = dec
-        ctx.save_for_backward(x4, pooled, stage_act, priors, cb, ab, mb, ib, *cl, *ml, *il, kb, call)
+        _save(ctx, x4, pooled, stage_act, priors, lb, ab, cl, ml, il, call)
         return feat
 
     @staticmethod
@@ -593,40 +610,29 @@ class PPMFn(torch.autograd.Function):
     def backward(ctx, dfeat):
         dec = ctx.dec
         sizes, nl = dec.sizes, len(dec.sizes)
-        sv = ctx.saved_tensors
-        x4, pooled, stage_act, priors, cb, ab, mb, ib = sv[:8]
-        cl, ml, il = sv[8:8 + nl], sv[8 + nl:8 + 2 * nl], sv[8 + 2 * nl:8 + 3 * nl]
-        kb = sv[8 + 3 * nl]                          # ReLU bits of the bottleneck BatchNorm (factorised path)
+        x4, pooled, stage_act, priors, lb, ab, cl, ml, il, call = _saved(ctx)      # lb.bits: ReLU bits of the bottleneck BatchNorm (factorised path)
         B, H, W, Cf = x4.shape
         Cs = stage_act.shape[1]
         bt = dec.bottleneck
         dfeat = dfeat.contiguous()
         need_w = ctx.needs_input_grad[2]
         need_x = ctx.needs_input_grad[0]
-        spec_f = spec_of(bt[3])
-        _, wbf = prepared(bt[3].weight, x4.dtype)
         # the classifier conv's data gradient gates its result with the bottleneck ReLU's bits and emits the bottleneck BatchNorm's backward column sums
         # in its epilogue where the kernel serves the shape (round 5: one 36 us reduce pass less per step)
-        dab = ppart = None
-        if ctx.fact and _BN_FUSE and bt[1].training and kb.numel():
-            r = ops.conv2d_bwd_data_bnstat(dfeat, wbf, spec_f, (H, W), kb, cb, mb, ib)
-            if r is not None:
-                dab, ppart = r
-        if dab is None:
-            dab = ops.conv2d_bwd_data(dfeat, wbf, spec_f, (H, W))
+        if ctx.fact:
+            dab = _conv_dgrad(dfeat, bt[3], ab, below=(lb, bt[1]))
+        else:                 # direct path: no bits were kept, the activation itself is the gate
+            dab = Grad(ops.conv2d_bwd_data(dfeat, prepared(bt[3].weight, x4.dtype)[1], spec_of(bt[3]), (H, W)), act=ab)
         gwf = grad_dst(bt[3].weight) if need_w else None
         dwf = dbias = None
         if need_w:
             # weight + bias gradient of the biased 1x1 conv in one kernel (the bias column sums come out of the weight-gradient kernel's dy fragments: round 6, one pass over dfeat less)
-            dwf, dbias = ops.conv2d_bwd_weight_bias(ab, dfeat, spec_f, out=gwf)
+            dwf, dbias = ops.conv2d_bwd_weight_bias(ab, dfeat, spec_of(bt[3]), out=gwf)
             dwf = grad_alias(dwf, gwf)
         if ctx.fact:
             N = bt[0].out_channels
             wq_f, wq_b, wf4, wb4 = _ppm_weights(bt[0].weight, Cs, nl, x4.dtype)
-            ggb, gbb = (grad_dst(bt[1].weight), grad_dst(bt[1].bias)) if need_w else (None, None)
-            dcb, _, dgb, dbb = ops.bn_bwd(dab, None, cb, mb, ib, bt[1].weight, train=bt[1].training, sync_world=sync_world(bt[1]), dgamma_out=ggb, dbeta_out=gbb,
-                                          mask=None if ppart is not None else kb, pre_partial=ppart)
-            dgb, dbb = grad_alias(dgb, ggb), grad_alias(dbb, gbb)
+            dcb, dgb, dbb, _ = _bn_bwd(dab, lb, bt[1], need_w)
             spec4 = ConvSpec(Cf, N, 3, 1, 1, 1)
             dcat = ops.conv2d_bwd_data(dcb, wb4, spec4, (H, W))                     # gradient of the x4 half only: [B,H,W,Cf]
             cat_off = 0
@@ -647,17 +653,17 @@ class PPMFn(torch.autograd.Function):
                         ops.conv2d_bwd_weight(stage_act[off:off + n].view(B, s, s, Cs), gq[off:off + n].view(B, s, s, 9 * N), qspec,
                                               out=dwq[k].view(9 * N, Cs, 1, 1))
                         off += n
-            if need_w:
                 ops.ppm_dwq_scatter(dwq, dwb, Cs, nl)
                 dwb = grad_alias(dwb, gwb)
         else:
-            dcat, dwb, dgb, dbb, _, _ = conv_bn_bwd(dab, ab, cb, priors, bt[0], bt[1], mb, ib, True, need_w, x2=x4)
+            dcb, dgb, dbb, _ = _bn_bwd(dab, lb, bt[1], need_w)
+            dwb = _conv_wgrad(bt[0], priors, dcb, x2=x4) if need_w else None
+            dcat = _conv_dgrad(dcb, bt[0], priors, x2=x4).t
             dstage = ops.ppm_upsample_bwd(dcat, x4.shape, sizes, Cs)
             cat_off = len(sizes) * Cs
         dc_all = torch.empty_like(stage_act)
         gstage, off = [], 0
         grouped = None
-        call = sv[9 + 3 * nl]
         if _BN_FUSE and _STAGE_BN_GROUPED and call.numel() and not any(sync_world(st[2]) for st in dec.stages):
             # all levels' BatchNorm + ReLU backward in ONE launch (round 5): twelve latency-bound launches less per step
             dsts = [(grad_dst(st[2].weight), grad_dst(st[2].bias)) if need_w else (None, None) for st in dec.stages]
@@ -672,13 +678,11 @@ class PPMFn(torch.autograd.Function):
             dws_all = ops.ppm_rows_wgrad(dc_all, pooled, B, sizes, outs=[grad_dst(st[1].weight) for st in dec.stages])
         for k, (s, st) in enumerate(zip(sizes, dec.stages)):
             n = B * s * s
-            ggs, gbs, gws = (grad_dst(st[2].weight), grad_dst(st[2].bias), grad_dst(st[1].weight)) if need_w else (None, None, None)
+            gws = grad_dst(st[1].weight) if need_w else None
             if grouped is not None:
                 dgs, dbs = grouped[k]
             else:
-                _, _, dgs, dbs = ops.bn_bwd(dstage[off:off + n], stage_act[off:off + n], cl[k], ml[k], il[k], st[2].weight, train=st[2].training,
-                                            out=dc_all[off:off + n], sync_world=sync_world(st[2]), dgamma_out=ggs, dbeta_out=gbs)
-                dgs, dbs = grad_alias(dgs, ggs), grad_alias(dbs, gbs)
+                _, dgs, dbs, _ = _bn_bwd(Grad(dstage[off:off + n], act=stage_act[off:off + n]), BNLayer(cl[k], ml[k], il[k], None), st[2], need_w, out=dc_all[off:off + n])
             if dws_all is not None:
                 dws = grad_alias(dws_all[k] if dws_all[k] is gws else dws_all[k].view_as(st[1].weight), gws)
             else:
