@@ -213,6 +213,10 @@ int sl_bn_finalize_eval(int C, const float* gamma, const float* beta, const floa
  * relu_mask (nullable): one byte per 16-byte vector of y, bit k = (y_k > 0): the backward reads this instead of y. */
 int sl_bn_act_fwd(int dtype, const void* x, const float* scale, const float* shift, const void* residual, int relu,
                   void* y, uint8_t* relu_mask, long long rows, int C, sl_stream_t stream);
+/* y = x*scale[c] + shift[c] + T(x2*scale2[c] + shift2[c]) (relu)   -- bn3 + downsample BN + ReLU of a stage's first bottleneck (resnet.py:71-76)
+ * in one pass: bit-identical to sl_bn_act_fwd(x2, relu 0) followed by sl_bn_act_fwd(x, residual = its result); the shortcut tensor is never written. */
+int sl_bn_act2_fwd(int dtype, const void* x, const float* scale, const float* shift, const void* x2, const float* scale2, const float* shift2,
+                   int relu, void* y, uint8_t* relu_mask, long long rows, int C, sl_stream_t stream);
 /* Backward, step 1: partial[blk][0][c] = sum g, partial[blk][1][c] = sum g*xhat with g = dy * relu'(y) (mask from
  * relu_mask if given, else from y > 0 if y is given, else none) and
  * xhat = (x - mean)*invstd.  Returns the number of partial rows through *nblk (buffer: float[nblk][2][C]). */

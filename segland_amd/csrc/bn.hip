@@ -126,6 +126,59 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ x
   }
 }
 
+// Stage entry of a bottleneck (resnet.py:71-76): y = act(bn3(c3) + bnd(c_ds)) in ONE pass -- the normalised shortcut is never written.  The same stream as
+// bn_act_fwd_kernel with two coefficient pairs; bit-identical to bn_act_fwd(x2, relu = 0) followed by bn_act_fwd(x, residual = that): the shortcut value is
+// rounded to T (pack16 / unpack16: what the round trip through memory did) before it is added.
+template <typename T, bool FIXEDC>
+__global__ __launch_bounds__(256) void bn_act2_fwd_kernel(const T* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ shift,
+                                   const T* __restrict__ x2, const float* __restrict__ scale2, const float* __restrict__ shift2,
+                                   int relu, T* __restrict__ y, uint8_t* __restrict__ mask_out, unsigned nvec, unsigned nvc) {
+  constexpr int V = Vec16<T>::N;
+  float sc[V], sh[V], sc2[V], sh2[V];
+  if (FIXEDC) {
+    const unsigned c = (threadIdx.x % nvc) * V;
+#pragma unroll
+    for (int k = 0; k < V; ++k) { sc[k] = scale[c + k]; sh[k] = shift[c + k]; sc2[k] = scale2[c + k]; sh2[k] = shift2[c + k]; }
+  }
+  const unsigned nchunk = (nvec + 1023u) >> 10;
+  for (unsigned ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+    const unsigned i0 = (ch << 10) + threadIdx.x;
+    uint4 xv[4], dv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const unsigned i = i0 + u * 256u;
+      if (i < nvec) { xv[u] = ((const uint4*)x)[i]; dv[u] = ((const uint4*)x2)[i]; }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const unsigned i = i0 + u * 256u;
+      if (i >= nvec) break;
+      if (!FIXEDC) {
+        const unsigned c = (i % nvc) * V;
+#pragma unroll
+        for (int k = 0; k < V; ++k) { sc[k] = scale[c + k]; sh[k] = shift[c + k]; sc2[k] = scale2[c + k]; sh2[k] = shift2[c + k]; }
+      }
+      float a[V], d[V], r[V], o[V];
+      unpack16<T>(xv[u], a);
+      unpack16<T>(dv[u], d);
+#pragma unroll
+      for (int k = 0; k < V; ++k) d[k] = d[k] * sc2[k] + sh2[k];
+      unpack16<T>(pack16<T>(d), r);                     // the shortcut as the tensor type holds it
+      unsigned bits = 0;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        float v = a[k] * sc[k] + sh[k];
+        v += r[k];
+        if (relu) v = v > 0.f ? v : 0.f;
+        bits |= (v > 0.f ? 1u : 0u) << k;
+        o[k] = v;
+      }
+      ((uint4*)y)[i] = pack16<T>(o);
+      if (mask_out) mask_out[i] = (uint8_t)bits;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ backward reduce
 // partial[blk][0][c] = sum g, partial[blk][1][c] = sum g * (x - mean) * invstd over the block's rows
 // DUAL: a second BatchNorm whose output was added to the first one's before the same ReLU (bn3 + downsample BN of a bottleneck, resnet.py:71-76): both backward
@@ -353,6 +406,30 @@ extern "C" int sl_bn_act_fwd(int dtype, const void* x, const float* scale, const
   if (dtype == SL_BF16) return launch_bn_act<bf16_t>(x, scale, shift, residual, relu, y, relu_mask, rows, C, (hipStream_t)stream);
   if (dtype == SL_F32) return launch_bn_act<float>(x, scale, shift, residual, relu, y, relu_mask, rows, C, (hipStream_t)stream);
   SL_REQUIRE(false, "bn_act_fwd: bad dtype");
+  return 0;
+}
+
+template <typename T>
+static int launch_bn_act2(const void* x, const float* scale, const float* shift, const void* x2, const float* scale2, const float* shift2, int relu, void* y,
+                          uint8_t* mask_out, long long rows, int C, hipStream_t st) {
+  constexpr int V = Vec16<T>::N;
+  const long long nvec = rows * C / V;
+  SL_REQUIRE(nvec < (1ll << 31), "bn_act2_fwd: tensor too large");
+  const unsigned nvc = C / V;
+  const bool fixed = nvc <= 256 && 256 % nvc == 0;
+  const int blocks = ew_blocks((nvec + 3) / 4);
+  if (fixed) hipLaunchKernelGGL((bn_act2_fwd_kernel<T, true>), dim3(blocks), dim3(256), 0, st, (const T*)x, scale, shift, (const T*)x2, scale2, shift2, relu, (T*)y, mask_out, (unsigned)nvec, nvc);
+  else hipLaunchKernelGGL((bn_act2_fwd_kernel<T, false>), dim3(blocks), dim3(256), 0, st, (const T*)x, scale, shift, (const T*)x2, scale2, shift2, relu, (T*)y, mask_out, (unsigned)nvec, nvc);
+  SL_LAUNCH_CHECK("bn_act2_fwd_kernel");
+  return 0;
+}
+
+extern "C" int sl_bn_act2_fwd(int dtype, const void* x, const float* scale, const float* shift, const void* x2, const float* scale2, const float* shift2,
+                              int relu, void* y, uint8_t* relu_mask, long long rows, int C, sl_stream_t stream) {
+  SL_REQUIRE(x && scale && shift && x2 && scale2 && shift2 && y && rows > 0 && C > 0 && C % 8 == 0, "bn_act2_fwd: bad args");
+  if (dtype == SL_BF16) return launch_bn_act2<bf16_t>(x, scale, shift, x2, scale2, shift2, relu, y, relu_mask, rows, C, (hipStream_t)stream);
+  if (dtype == SL_F32) return launch_bn_act2<float>(x, scale, shift, x2, scale2, shift2, relu, y, relu_mask, rows, C, (hipStream_t)stream);
+  SL_REQUIRE(false, "bn_act2_fwd: bad dtype");
   return 0;
 }
 

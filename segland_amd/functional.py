@@ -281,6 +281,7 @@ _BASE_CHAIN_CACHE = True   # test hook: ft mode, the frozen base classifier's ro
 # (The deep stem's pool backward is exempt: its kernel exists in the statistics-emitting form only, DeepStemFn.backward always takes bn3's column sums from it.)
 _BN_FUSE = os.environ.get('SEGLAND_BN_FUSE', '1') != '0'        # BN-backward statistics in the data-gradient epilogues (conv_gemm_common.h: conv_epilogue_fast MODE 3)
 _BN_DUAL = _BN_FUSE        # test hook: bn3 + downsample BN backward in one sweep each (bn.hip reduce2 / apply2)
+_BN_DUAL_FWD = True        # test hook: bn3 + downsample BN forward apply in one pass (bn.hip bn_act2_fwd_kernel); False: the downsample branch's own pass writes the shortcut
 _BN_CROSS = _BN_FUSE       # test hook: bn3's column sums from the NEXT block's conv1 data-gradient epilogue (pixel-stationary kernel MODE 5)
 
 
@@ -453,11 +454,18 @@ class BottleneckFn(torch.autograd.Function):
             return conv_bn_infer(a2, blk.conv3, blk.bn3, relu=blk.last_relu, residual=res)
         a1, l1 = conv_bn_fwd(x, blk.conv1, blk.bn1, relu=True, want_mask=True)
         a2, l2 = conv_bn_fwd(a1, blk.conv2, blk.bn2, relu=True, want_mask=True)
-        if blk.downsample is not None:
-            res, ld = conv_bn_fwd(x, blk.downsample[0], blk.downsample[1], relu=False)
+        dsc, dbn = (blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else (None, None)
+        if dsc is not None and _BN_DUAL_FWD and blk.bn3.training and dbn.training and not sync_world(blk.bn3) and not sync_world(dbn) and a2.dtype == x.dtype:
+            # a stage's first block: the downsample BatchNorm is applied inside bn3's pass (ops.bn_act2), its normalised output is never written
+            cd, part = ops.conv2d_fwd(x, prepared(dsc.weight, x.dtype)[0], spec_of(dsc), want_stats=True)
+            md, isd, scd, shd = _bn_coeffs(dbn, part, cd.numel() // cd.shape[-1])
+            c3, part = ops.conv2d_fwd(a2, prepared(blk.conv3.weight, a2.dtype)[0], spec_of(blk.conv3), want_stats=True)
+            m3, is3, sc3, sh3 = _bn_coeffs(blk.bn3, part, c3.numel() // c3.shape[-1])
+            out, k3 = ops.bn_act2(c3, sc3, sh3, cd, scd, shd, relu=blk.last_relu, want_mask=True)
+            ld, l3 = BNLayer(cd, md, isd, None), BNLayer(c3, m3, is3, k3)
         else:
-            res, ld = x, None
-        out, l3 = conv_bn_fwd(a2, blk.conv3, blk.bn3, relu=blk.last_relu, residual=res, want_mask=True)
+            res, ld = conv_bn_fwd(x, dsc, dbn, relu=False) if dsc is not None else (x, None)
+            out, l3 = conv_bn_fwd(a2, blk.conv3, blk.bn3, relu=blk.last_relu, residual=res, want_mask=True)
         ctx.blk = blk
         ctx.has_ds = blk.downsample is not None
         # the next bottleneck's backward produces this block's incoming gradient: it may gate it and reduce it against c3 right there (_BN_CROSS)

@@ -499,6 +499,19 @@ def bn_act(x, scale, shift, residual=None, relu=True, out=None, want_mask=False)
     return (y, mask) if want_mask else y
 
 
+def bn_act2(x, scale, shift, x2, scale2, shift2, relu=True, out=None, want_mask=False):
+    """y = act(x*scale + shift + T(x2*scale2 + shift2)): bn_act(x2, relu=False) and bn_act(x, residual=that) in one pass, bit for bit (the shortcut is rounded to
+    the tensor type before it is added) -- bn3 + downsample BatchNorm of a stage's first bottleneck; the normalised shortcut is never written."""
+    Cn = x.shape[-1]
+    y = out if out is not None else torch.empty_like(x)
+    assert y.numel() == x.numel() and y.dtype == x.dtype and x2.shape == x.shape and x2.dtype == x.dtype and x2.is_contiguous()
+    mask = torch.empty(x.numel() * x.element_size() // 16, dtype=torch.uint8, device=x.device) if (want_mask and relu) else None
+    tok = PROFILER.begin_bytes('bn_act_fwd', x.numel() * x.element_size() * 3 + (mask.numel() if mask is not None else 0))
+    check(_lib.lib().sl_bn_act2_fwd(dt(x), _p(x), _p(scale), _p(shift), _p(x2), _p(scale2), _p(shift2), int(relu), _p(y), _p(mask), x.numel() // Cn, Cn, _s()), 'bn_act2_fwd')
+    PROFILER.end_bytes(tok)
+    return (y, mask) if want_mask else y
+
+
 def bn_bwd(dy, y, x, mean, invstd, gamma, train=True, want_dres=False, mask=None, out=None, sync_world=0, dgamma_out=None, dbeta_out=None,
            pre_partial=None):
     """Returns (dx, dres, dgamma, dbeta).  ReLU gate of dy: `mask` (bit mask from bn_act) if given, else y > 0 if y is given.

@@ -24,7 +24,7 @@ from segland_amd.networks.pspnet_pop import GFSS_Model  # noqa: E402
 
 assert os.path.abspath(ops.__file__).startswith(TREE + os.sep), 'segland_amd was imported from %s' % ops.__file__
 DEV = 'cuda'
-HOOKS_OFF = ('_BN_DUAL', '_BN_CROSS', '_DS_HALF', '_STAGE_BN_GROUPED', '_PPM_WGRAD_GROUPED')
+HOOKS_OFF = ('_BN_DUAL', '_BN_DUAL_FWD', '_BN_CROSS', '_DS_HALF', '_STAGE_BN_GROUPED', '_PPM_WGRAD_GROUPED')
 LINES, TAG = [], ['']
 
 
@@ -97,12 +97,14 @@ def bottleneck_stack():
 
 def hook_off(name):
     def run():
-        was = getattr(sf, name)
-        setattr(sf, name, False)
+        was = getattr(sf, name, None)          # None: a tree from before this hook -- it runs what the hook switches back to
+        if was is not None:
+            setattr(sf, name, False)
         try:
             train_step(model())
         finally:
-            setattr(sf, name, was)
+            if was is not None:
+                setattr(sf, name, was)
     return run
 
 
