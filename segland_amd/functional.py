@@ -226,9 +226,14 @@ class Grad:
         self.t, self.bits, self.act, self.part, self.part2 = t, bits, act, part, part2
 
 
+# What the forward of a pyramid's stages (stages_fwd) keeps for stages_bwd: the pooled rows, the stage convs' output `call` and the activations stage_act (fp32
+# [rows][pitch], the levels' rows one after the other) and per level the BatchNorm's mean / invstd.
+StageRec = namedtuple('StageRec', 'pooled call stage_act mean invstd')
+
+
 def _save(ctx, *items):
-    """ctx.save_for_backward of tensors, None, BNLayer records and lists of tensors; _saved(ctx) gives the same sequence back."""
-    groups = [it if isinstance(it, (list, BNLayer)) else [it] for it in items]
+    """ctx.save_for_backward of tensors, None, BNLayer / StageRec records and lists of tensors; _saved(ctx) gives the same sequence back."""
+    groups = [[*it[:3], *it.mean, *it.invstd] if isinstance(it, StageRec) else it if isinstance(it, (list, BNLayer)) else [it] for it in items]
     ctx.saved_form = [(type(it), len(g)) for it, g in zip(items, groups)]
     ctx.save_for_backward(*[t for g in groups for t in g])
 
@@ -236,7 +241,8 @@ def _save(ctx, *items):
 def _saved(ctx):
     sv = iter(ctx.saved_tensors)
     groups = [(kind, [next(sv) for _ in range(n)]) for kind, n in ctx.saved_form]
-    return [BNLayer(*ts) if kind is BNLayer else ts if kind is list else ts[0] for kind, ts in groups]
+    return [BNLayer(*ts) if kind is BNLayer else StageRec(*ts[:3], ts[3:(len(ts) + 3) // 2], ts[(len(ts) + 3) // 2:]) if kind is StageRec
+            else ts if kind is list else ts[0] for kind, ts in groups]
 
 
 def conv_bn_fwd(x, conv, bn, relu, residual=None, x2=None, out=None, want_mask=False):
@@ -283,6 +289,7 @@ _BN_FUSE = os.environ.get('SEGLAND_BN_FUSE', '1') != '0'        # BN-backward st
 _BN_DUAL = _BN_FUSE        # test hook: bn3 + downsample BN backward in one sweep each (bn.hip reduce2 / apply2)
 _BN_DUAL_FWD = True        # test hook: bn3 + downsample BN forward apply in one pass (bn.hip bn_act2_fwd_kernel); False: the downsample branch's own pass writes the shortcut
 _BN_CROSS = _BN_FUSE       # test hook: bn3's column sums from the NEXT block's conv1 data-gradient epilogue (pixel-stationary kernel MODE 5)
+_PPM_FACTORISED = os.environ.get('SEGLAND_PPM_DIRECT') != '1'   # set_ppm_factorised: the prior half of the pyramid's 3x3 bottleneck conv contracted on the s x s grids
 
 
 def _bn_bwd(g, layer, bn, need_w, want_dres=False, out=None):
@@ -547,70 +554,129 @@ def bottleneck_params(blk):
 
 
 # ------------------------------------------------------------------------------------------------ pyramid pooling
+# How a decoder describes the stages of its pyramid (per level: adaptive pool -> 1x1 conv -> BatchNorm -> ReLU) to stages_fwd / stages_bwd; made per call, so the hooks are
+# read when the chain runs.  sizes / convs / bns: per level; pitch: channels of a pyramid row; w_fwd() / w_dgrad(): the stage weights in ops.ppm_rows_gemm's forward and
+# data-gradient form; coeffs(bn, c, part, count) -> (mean, invstd, scale, shift) of a level; gamma(bn): its scale vector at the pitch; dst(p): where parameter p's gradient is to
+# be written (None: a fresh tensor) and w_dsts(): that of all stage conv weights; grad(t, dst, p): what the backward returns for p's gradient t, which the kernels wrote at the
+# pitch; bn_grouped(call) / wgrad_grouped(bn_grouped): all levels' BatchNorm + ReLU backward in ONE launch (ops.ppm_stage_bn_bwd) / all stage weight gradients in one launch
+# (ops.ppm_rows_wgrad, which needs the gradient at every level's conv output complete).
+Pyramid = namedtuple('Pyramid', 'sizes convs bns pitch w_fwd w_dgrad coeffs gamma dst w_dsts grad bn_grouped wgrad_grouped')
+
+
+def ppm_stages(dec):
+    """The PSPNet-POP pyramid (pspnet_pop.PSPModule): the levels' prepared float weights, gradients written into DDP's bucket views where there are any; the grouped BatchNorm
+    backward saves twelve latency-bound launches per step (round 5), SyncBatchNorm stages take the per-level chain."""
+    convs, bns = [st[1] for st in dec.stages], [st[2] for st in dec.stages]
+    return Pyramid(dec.sizes, convs, bns, pitch=convs[0].out_channels, w_fwd=lambda: _stage_weights(dec)[0], w_dgrad=lambda: _stage_weights(dec)[1],
+                   coeffs=lambda bn, c, part, count: _bn_coeffs(bn, part, count), gamma=lambda bn: bn.weight,
+                   dst=grad_dst, w_dsts=lambda: [grad_dst(c.weight) for c in convs], grad=lambda t, dst, p: grad_alias(t if t is dst else t.view_as(p), dst),
+                   bn_grouped=lambda call: bool(_BN_FUSE and _STAGE_BN_GROUPED and call.numel() and not any(sync_world(bn) for bn in bns)),
+                   wgrad_grouped=lambda bn_grouped: _PPM_WGRAD_GROUPED and bn_grouped)
+
+
+def _level_rows(B, sizes):
+    """Row range [off[k], off[k + 1]) of level k in the pyramid's row tensors."""
+    off = [0]
+    for s in sizes:
+        off.append(off[-1] + B * s * s)
+    return off
+
+
+def stages_fwd(d, x, frozen=False, after_level=None):
+    """The stages of pyramid d on the NHWC map x: adaptive pool, the four 1x1 convs as ONE grouped skinny GEMM over the pyramid rows (16..576 rows per level), per level
+    BatchNorm + ReLU -> StageRec.  The stage path is fp32 (see ppm.hip).  frozen: a call that keeps nothing and takes no batch statistics; after_level(k, act): called
+    right after level k's activation rows are written."""
+    B, sizes = x.shape[0], d.sizes
+    pooled = ops.ppm_pool_fwd(x, sizes)
+    call, part = ops.ppm_rows_gemm(pooled, d.w_fwd(), B, sizes, want_stats=any(bn.training for bn in d.bns))
+    stage_act = torch.empty_like(call)
+    off, grp = _level_rows(B, sizes), None if frozen else ops.ppm_stat_groups(B, sizes)
+    ml, il = [], []
+    for k, bn in enumerate(d.bns):
+        c, act = call[off[k]:off[k + 1]], stage_act[off[k]:off[k + 1]]
+        m, i, scale, shift = d.coeffs(bn, c, part[grp[k]:grp[k + 1]] if bn.training else None, off[k + 1] - off[k])
+        ops.bn_act(c, scale, shift, relu=True, out=act)
+        if after_level is not None:
+            after_level(k, act)
+        ml.append(m); il.append(i)
+    return StageRec(pooled, call, stage_act, ml, il)
+
+
+def stages_bwd(d, rec, dstage, x_shape, x_dtype, need_w, need_x, dcat, cat_off):
+    """Backward of stages_fwd from dstage, the gradient at the activation rows: BatchNorm + ReLU backward and the stage convs' weight gradients, each grouped or level by
+    level as d says, the row GEMM back to the pooled rows and the pool backward, which adds the feature map's share dcat[..., cat_off:] of the concat's gradient.
+    -> (dx or None, [d conv weight, d gamma, d beta] per level)."""
+    B, sizes, nl = x_shape[0], d.sizes, len(d.sizes)
+    pooled, call, stage_act, ml, il = rec
+    P, Cf, off = call.shape[1], pooled.shape[1], _level_rows(B, sizes)
+    dc_all = torch.empty_like(stage_act)
+    vdst = [(d.dst(bn.weight), d.dst(bn.bias)) if need_w else (None, None) for bn in d.bns]
+    wdst = d.w_dsts() if need_w else None
+    grouped = d.bn_grouped(call)
+    if grouped:
+        tmp = torch.empty((nl, 2, P), dtype=torch.float32, device=call.device)
+        dgl, dbl = [[v[j] if v[j] is not None else tmp[k, j] for k, v in enumerate(vdst)] for j in (0, 1)]
+        ops.ppm_stage_bn_bwd(dstage, stage_act, call, B, sizes, ml, il, [d.gamma(bn) for bn in d.bns], [bn.training for bn in d.bns], dgl, dbl, out=dc_all)
+    dws_all = ops.ppm_rows_wgrad(dc_all, pooled, B, sizes, outs=wdst) if (need_w and d.wgrad_grouped(grouped)) else None
+    grads = []
+    for k, (s, conv, bn) in enumerate(zip(sizes, d.convs, d.bns)):
+        rows = slice(off[k], off[k + 1])
+        if grouped:
+            dgs, dbs = dgl[k], dbl[k]
+        else:
+            _, _, dgs, dbs = ops.bn_bwd(dstage[rows], stage_act[rows], call[rows], ml[k], il[k], d.gamma(bn), train=bn.training, out=dc_all[rows],
+                                        sync_world=sync_world(bn), dgamma_out=vdst[k][0], dbeta_out=vdst[k][1])
+        if not need_w:
+            grads += [None, None, None]
+            continue
+        gws = wdst[k] if wdst is not None else None
+        dws = dws_all[k] if dws_all is not None else ops.conv2d_bwd_weight(pooled[rows].view(B, s, s, Cf), dc_all[rows].view(B, s, s, P), ConvSpec(Cf, P, 1), out=gws)
+        grads += [d.grad(dws, gws, conv.weight), d.grad(dgs, vdst[k][0], bn.weight), d.grad(dbs, vdst[k][1], bn.bias)]
+    dx = None
+    if need_x:
+        dpooled = ops.ppm_rows_gemm(dc_all, d.w_dgrad(), B, sizes)[0]
+        dx = ops.ppm_pool_bwd(dpooled, x_shape, x_dtype, sizes, dcat=dcat, cat_off=cat_off)
+    return dx, grads
+
+
 class PPMFn(torch.autograd.Function):
     """networks/pspnet_pop.py:31-35: 4 x (adaptive pool -> 1x1 -> BN -> ReLU -> bilinear up) (+) feats -> 3x3 -> BN -> ReLU -> 1x1+bias.
     The 4096-channel concat is virtual: the 3x3 conv reads [priors | feats] from two tensors."""
 
     @staticmethod
     def forward(ctx, x4, dec, *params):
-        sizes = dec.sizes
+        sizes, bt = dec.sizes, dec.bottleneck
         B, H, W, Cf = x4.shape
-        Cs = dec.stages[0][1].out_channels
-        pooled = ops.ppm_pool_fwd(x4, sizes)
-        stage_act = torch.empty((pooled.shape[0], Cs), dtype=torch.float32, device=x4.device)   # stage path is fp32 (see ppm.hip)
-        if _frozen(ctx, dec.bottleneck[1], *[st[2] for st in dec.stages]):
-            call, _ = ops.ppm_rows_gemm(pooled, _stage_weights(dec)[0], B, sizes)     # the four stage convs in one grouped GEMM
-            off = 0
-            for s, st in zip(sizes, dec.stages):
-                n = B * s * s
-                _, _, scale, shift = _bn_eval_coeffs(st[2])
-                ops.bn_act(call[off:off + n], scale, shift, relu=True, out=stage_act[off:off + n])
-                off += n
-            bt = dec.bottleneck
-            if _PPM_FACTORISED:
-                # as in the training branch: the prior half of the 3x3 conv contracted on the s x s grids (exact), the x4 half on the MFMA kernel with the
-                # gathered prior term entering before the folded BatchNorm -- half the FLOPs of the virtual-concat conv, and a shape the patch kernel serves
-                N = bt[0].out_channels
-                wq_f, _, wf4, _ = _ppm_weights(bt[0].weight, Cs, len(sizes), x4.dtype)
-                q, _ = ops.ppm_rows_gemm(stage_act, wq_f, B, sizes)
-                gpri = ops.ppm_fact_gather(q, x4.shape, sizes, N, x4.dtype)
-                _, _, scale, shift = _bn_eval_coeffs(bt[1])
-                ab = ops.conv2d_affine_fwd(x4, wf4, ConvSpec(Cf, N, 3, 1, 1, 1), scale, shift, relu=True, pre_addend=gpri)
-            else:
-                priors = ops.ppm_upsample_fwd(stage_act, x4.shape, sizes, x4.dtype)
-                ab = conv_bn_infer(priors, bt[0], bt[1], relu=True, x2=x4)
-            wf, _ = prepared(bt[3].weight, x4.dtype)
-            return ops.conv2d_fwd(ab, wf, spec_of(bt[3]), bias=bt[3].bias.detach())[0]
-        # the four stage convs as ONE grouped skinny GEMM over the pyramid rows (16..576 rows per level)
-        wst_f, _ = _stage_weights(dec)
-        call, part = ops.ppm_rows_gemm(pooled, wst_f, B, sizes, want_stats=any(st[2].training for st in dec.stages))
-        cl, ml, il, off, grp = [], [], [], 0, ops.ppm_stat_groups(B, sizes)
-        for k, (s, st) in enumerate(zip(sizes, dec.stages)):
-            n = B * s * s
-            c = call[off:off + n]
-            m, i, scale, shift = _bn_coeffs(st[2], part[grp[k]:grp[k + 1]] if st[2].training else None, n)
-            ops.bn_act(c, scale, shift, relu=True, out=stage_act[off:off + n])
-            cl.append(c); ml.append(m); il.append(i); off += n
-        bt = dec.bottleneck
-        ctx.fact = _PPM_FACTORISED
-        if ctx.fact:
-            # prior half of the 3x3 conv contracted on the s x s grids (exact; see ppm.hip), x4 half on the MFMA kernel
+        frozen = _frozen(ctx, bt[1], *[st[2] for st in dec.stages])
+        rec = stages_fwd(ppm_stages(dec), x4, frozen)
+        fact, priors, lb = _PPM_FACTORISED, None, None
+        if fact:
+            # the prior half of the 3x3 conv contracted on the s x s grids (exact; see ppm.hip), the x4 half on the MFMA kernel with the gathered prior term entering
+            # before the BatchNorm -- half the FLOPs of the virtual-concat conv, and a shape the patch kernel serves
             N = bt[0].out_channels
-            wq_f, wq_b, wf4, wb4 = _ppm_weights(bt[0].weight, Cs, len(sizes), x4.dtype)
-            q, _ = ops.ppm_rows_gemm(stage_act, wq_f, B, sizes)
+            wq_f, _, wf4, _ = _ppm_weights(bt[0].weight, rec.stage_act.shape[1], len(sizes), x4.dtype)
+            q, _ = ops.ppm_rows_gemm(rec.stage_act, wq_f, B, sizes)
             gpri = ops.ppm_fact_gather(q, x4.shape, sizes, N, x4.dtype)
             spec4 = ConvSpec(Cf, N, 3, 1, 1, 1)
+        else:
+            priors = ops.ppm_upsample_fwd(rec.stage_act, x4.shape, sizes, x4.dtype)
+        if frozen and fact:
+            _, _, scale, shift = _bn_eval_coeffs(bt[1])
+            ab = ops.conv2d_affine_fwd(x4, wf4, spec4, scale, shift, relu=True, pre_addend=gpri)
+        elif frozen:
+            ab = conv_bn_infer(priors, bt[0], bt[1], relu=True, x2=x4)
+        elif fact:
             cb, part = ops.conv2d_fwd(x4, wf4, spec4, pre_addend=gpri, want_stats=bt[1].training)
             mb, ib, scale, shift = _bn_coeffs(bt[1], part, cb.numel() // N)
             ab, kb = ops.bn_act(cb, scale, shift, relu=True, want_mask=True)
-            priors, lb = None, BNLayer(cb, mb, ib, kb)
+            lb = BNLayer(cb, mb, ib, kb)
         else:
-            priors = ops.ppm_upsample_fwd(stage_act, x4.shape, sizes, x4.dtype)
             ab, lb = conv_bn_fwd(priors, bt[0], bt[1], relu=True, x2=x4)          # no ReLU bits: the backward gates with ab itself
         wf, _ = prepared(bt[3].weight, x4.dtype)
         feat, _ = ops.conv2d_fwd(ab, wf, spec_of(bt[3]), bias=bt[3].bias.detach())
-        ctx.dec = dec
-        _save(ctx, x4, pooled, stage_act, priors, lb, ab, cl, ml, il, call)
+        if not frozen:
+            ctx.dec, ctx.fact = dec, fact
+            _save(ctx, x4, rec, priors, lb, ab)
         return feat
 
     @staticmethod
@@ -618,7 +684,8 @@ class PPMFn(torch.autograd.Function):
     def backward(ctx, dfeat):
         dec = ctx.dec
         sizes, nl = dec.sizes, len(dec.sizes)
-        x4, pooled, stage_act, priors, lb, ab, cl, ml, il, call = _saved(ctx)      # lb.bits: ReLU bits of the bottleneck BatchNorm (factorised path)
+        x4, rec, priors, lb, ab = _saved(ctx)      # lb.bits: ReLU bits of the bottleneck BatchNorm (factorised path)
+        stage_act = rec.stage_act
         B, H, W, Cf = x4.shape
         Cs = stage_act.shape[1]
         bt = dec.bottleneck
@@ -669,40 +736,8 @@ class PPMFn(torch.autograd.Function):
             dcat = _conv_dgrad(dcb, bt[0], priors, x2=x4).t
             dstage = ops.ppm_upsample_bwd(dcat, x4.shape, sizes, Cs)
             cat_off = len(sizes) * Cs
-        dc_all = torch.empty_like(stage_act)
-        gstage, off = [], 0
-        grouped = None
-        if _BN_FUSE and _STAGE_BN_GROUPED and call.numel() and not any(sync_world(st[2]) for st in dec.stages):
-            # all levels' BatchNorm + ReLU backward in ONE launch (round 5): twelve latency-bound launches less per step
-            dsts = [(grad_dst(st[2].weight), grad_dst(st[2].bias)) if need_w else (None, None) for st in dec.stages]
-            tmp = torch.empty((nl, 2, Cs), dtype=torch.float32, device=x4.device)
-            dgl = [d_[0] if d_[0] is not None else tmp[k, 0] for k, d_ in enumerate(dsts)]
-            dbl = [d_[1] if d_[1] is not None else tmp[k, 1] for k, d_ in enumerate(dsts)]
-            ops.ppm_stage_bn_bwd(dstage, stage_act, call, B, sizes, ml, il, [st[2].weight for st in dec.stages], [st[2].training for st in dec.stages], dgl, dbl, out=dc_all)
-            grouped = [(grad_alias(dgl[k], dsts[k][0]), grad_alias(dbl[k], dsts[k][1])) for k in range(nl)]
-        dws_all = None
-        if need_w and _PPM_WGRAD_GROUPED and grouped is not None:
-            # the four stage convs' weight gradients in one launch (ops.ppm_rows_wgrad); dc_all is complete (the grouped BatchNorm backward wrote every level)
-            dws_all = ops.ppm_rows_wgrad(dc_all, pooled, B, sizes, outs=[grad_dst(st[1].weight) for st in dec.stages])
-        for k, (s, st) in enumerate(zip(sizes, dec.stages)):
-            n = B * s * s
-            gws = grad_dst(st[1].weight) if need_w else None
-            if grouped is not None:
-                dgs, dbs = grouped[k]
-            else:
-                _, dgs, dbs, _ = _bn_bwd(Grad(dstage[off:off + n], act=stage_act[off:off + n]), BNLayer(cl[k], ml[k], il[k], None), st[2], need_w, out=dc_all[off:off + n])
-            if dws_all is not None:
-                dws = grad_alias(dws_all[k] if dws_all[k] is gws else dws_all[k].view_as(st[1].weight), gws)
-            else:
-                dws = grad_alias(ops.conv2d_bwd_weight(pooled[off:off + n].view(B, s, s, Cf), dc_all[off:off + n].view(B, s, s, Cs), spec_of(st[1]), out=gws), gws) if need_w else None
-            gstage += [dws, dgs, dbs]; off += n
-        dpooled = ops.ppm_rows_gemm(dc_all, _stage_weights(dec)[1], B, sizes)[0] if need_x else None
-        dx4 = ops.ppm_pool_bwd(dpooled, x4.shape, x4.dtype, sizes, dcat=dcat, cat_off=cat_off) if need_x else None
+        dx4, gstage = stages_bwd(ppm_stages(dec), rec, dstage, x4.shape, x4.dtype, need_w, need_x, dcat, cat_off)
         return (dx4, None, *gstage, dwb, dgb, dbb, dwf, dbias)
-
-
-import os as _os
-_PPM_FACTORISED = _os.environ.get('SEGLAND_PPM_DIRECT') != '1'
 
 
 def set_ppm_factorised(flag):
@@ -728,7 +763,6 @@ def _ppm_weights(w, Cs, nl, dtype):
     if ent is None or ent[0] != _wver(w) or ent[1] != dtype or ent[2] != w.data_ptr():
         wq_f, wq_b = ops.ppm_wq_prep(w, Cs, nl)
         wf4, wb4 = ops.weight_prep_slice(w, dtype, nl * Cs, w.shape[1] - nl * Cs)
-        N = w.shape[0]
         ent = (_wver(w), dtype, w.data_ptr(), wq_f, wq_b, wf4, wb4)
         w._sl_ppm = ent
     return ent[3], ent[4], ent[5], ent[6]

@@ -11,7 +11,7 @@ from torch.autograd.function import once_differentiable
 
 from . import ops
 from . import ops_swin as osw
-from .functional import _nbt_pending, _wver
+from .functional import BNLayer, Pyramid, _nbt_pending, _save, _saved, _wver, stages_bwd, stages_fwd
 from .ops import ConvSpec
 from .ops_swin import pad_to
 
@@ -589,6 +589,33 @@ class AddResizedFn(torch.autograd.Function):
         return dy, (dy if ctx.same else osw.bilinear_bwd(dy, ctx.hw, ctx.align)), None
 
 
+def _stage_stack(psp, Ps):
+    """The stage 1x1 weights as one zero-padded stack [nl][Ps][Cf] for ops.ppm_rows_gemm, refreshed when a weight changes."""
+    convs = [st[1] for st in psp.stages]
+    nl, (Cs, Cf), dev = len(convs), convs[0].weight.shape[:2], convs[0].weight.device
+    wkey = tuple((_wver(c.weight), c.weight.data_ptr()) for c in convs)
+    went = psp.__dict__.get('_sl_wst')
+    if went is None or went[0] != wkey:
+        # the padded stack lives in one buffer (pad rows stay zero); a new optimizer step refills it with ONE multi-tensor copy (was: zeros + copy per level + stack)
+        buf = went[1] if (went is not None and went[1].shape == (nl, Ps, Cf) and went[1].device == dev) else torch.zeros((nl, Ps, Cf), dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            torch._foreach_copy_([buf[k, :Cs] for k in range(nl)], [c.weight.detach().view(Cs, Cf) for c in convs])
+        went = psp.__dict__['_sl_wst'] = (wkey, buf)
+    return went[1]
+
+
+def psp_stages(psp):
+    """The UperNet pyramid (swin_pop.PSPModule) for functional.stages_fwd / stages_bwd: rows at the padded pitch Ps, the stage weights as one padded stack, BatchNorm vectors at
+    the pitch (_bn_padded), gradients in fresh padded buffers, handed back as their [:Cs] slices in parameter shape.  _PSP_GROUPED (round 6): the four levels' BatchNorm + ReLU
+    backward and their weight gradients as two launches (the PSPNet-POP pyramid's kernels) instead of four (reduce, finalize, apply, weight gradient, slab reduce) chains."""
+    convs, bns = [st[1] for st in psp.stages], [st[2] for st in psp.stages]
+    Ps = pad_to(convs[0].out_channels)
+    return Pyramid(psp.sizes, convs, bns, pitch=Ps, w_fwd=lambda: _stage_stack(psp, Ps), w_dgrad=lambda: _stage_stack(psp, Ps).transpose(1, 2).contiguous(),
+                   coeffs=lambda bn, c, part, count: _bn_forward(bn, c, part, None, Ps), gamma=lambda bn: _bn_padded(bn, Ps)[0],
+                   dst=lambda p: None, w_dsts=lambda: None, grad=lambda t, dst, p: t.view(Ps, -1)[:p.shape[0]].view_as(p),
+                   bn_grouped=lambda call: _PSP_GROUPED, wgrad_grouped=lambda bn_grouped: _PSP_GROUPED)
+
+
 class PspSwinFn(torch.autograd.Function):
     """PSPModule of swin_pop.py:7-35: 4 x (adaptive pool -> 1x1 -> BN -> ReLU -> bilinear(align_corners=True)) (+) feats -> 1x1 -> BN -> ReLU
     -> Dropout2d(0.1).  x [B,h,w,Cf]; the concat is virtual ([priors | feats] read from two tensors); the pyramid rows stay fp32."""
@@ -599,27 +626,9 @@ class PspSwinFn(torch.autograd.Function):
         B, h, w, Cf = x.shape
         Cs = psp.stages[0][1].out_channels
         Ps = pad_to(Cs)
-        pooled = ops.ppm_pool_fwd(x, sizes)                                                   # [rows, Cf] float
-        wkey = tuple((_wver(st[1].weight), st[1].weight.data_ptr()) for st in psp.stages)
-        went = psp.__dict__.get('_sl_wst')
-        if went is None or went[0] != wkey:
-            # the padded stack lives in one buffer (pad rows stay zero); a new optimizer step refills it with ONE multi-tensor copy (was: zeros + copy per level + stack)
-            buf = went[1] if (went is not None and went[1].shape == (nl, Ps, Cf) and went[1].device == x.device) else torch.zeros((nl, Ps, Cf), dtype=torch.float32, device=x.device)
-            with torch.no_grad():
-                torch._foreach_copy_([buf[k, :Cs] for k in range(nl)], [st[1].weight.detach().view(Cs, Cf) for st in psp.stages])
-            went = psp.__dict__['_sl_wst'] = (wkey, buf)
-        wst = went[1]
-        call, part = ops.ppm_rows_gemm(pooled, wst, B, sizes, want_stats=any(st[2].training for st in psp.stages))
-        stage_act = torch.empty_like(call)
         priors = torch.empty((B, h, w, nl * Ps), dtype=x.dtype, device=x.device)
-        cl, ml, il, off, grp = [], [], [], 0, ops.ppm_stat_groups(B, sizes)
-        for k, (s, st) in enumerate(zip(sizes, psp.stages)):
-            n = B * s * s
-            c = call[off:off + n]
-            m, i, scale, shift = _bn_forward(st[2], c, part[grp[k]:grp[k + 1]] if st[2].training else None, None, Ps)
-            ops.bn_act(c, scale, shift, relu=True, out=stage_act[off:off + n])
-            osw.bilinear_fwd(stage_act[off:off + n].view(B, s, s, Ps), (h, w), True, out=priors, out_off=k * Ps)
-            cl.append(c); ml.append(m); il.append(i); off += n
+        # level k is upsampled into its slice of priors right after its activation is written
+        rec = stages_fwd(psp_stages(psp), x, after_level=lambda k, act: osw.bilinear_fwd(act.view(B, sizes[k], sizes[k], Ps), (h, w), True, out=priors, out_off=k * Ps))
         bt = psp.bottleneck
         wb_, bnb = bt[0].weight, bt[1]
         cmap = _psp_colmap(Cs, Ps, nl, Cf, x.device)
@@ -631,7 +640,7 @@ class PspSwinFn(torch.autograd.Function):
             y = osw.scale_add(y, drop, None, per_channel=True, Cn=bnb.num_features)
         if any(ctx.needs_input_grad):
             ctx.psp = psp
-            ctx.save_for_backward(x, pooled, stage_act, priors, cb, mb, ib, bits, drop, wst, *cl, *ml, *il, call)
+            _save(ctx, x, rec, priors, BNLayer(cb, mb, ib, bits), drop)
         return y
 
     @staticmethod
@@ -639,9 +648,7 @@ class PspSwinFn(torch.autograd.Function):
     def backward(ctx, dy):
         psp = ctx.psp
         sizes, nl = psp.sizes, len(psp.sizes)
-        sv = ctx.saved_tensors
-        x, pooled, stage_act, priors, cb, mb, ib, bits, drop, wst = sv[:10]
-        cl, ml, il = sv[10:10 + nl], sv[10 + nl:10 + 2 * nl], sv[10 + 2 * nl:10 + 3 * nl]
+        x, rec, priors, lb, drop = _saved(ctx)
         B, h, w, Cf = x.shape
         Cs = psp.stages[0][1].out_channels
         Ps = pad_to(Cs)
@@ -654,43 +661,16 @@ class PspSwinFn(torch.autograd.Function):
         cmap = _psp_colmap(Cs, Ps, nl, Cf, x.device)
         L = lin_prep(bt[0].weight, None, x.dtype, Kp=nl * Ps + Cf, col_map=cmap)
         gw = _bn_padded(bnb, L.Np)[0]
-        dcb, _, dgb, dbb = ops.bn_bwd(dy, None, cb, mb, ib, gw, train=bnb.training, mask=bits)
+        dcb, _, dgb, dbb = ops.bn_bwd(dy, None, lb.c, lb.mean, lb.invstd, gw, train=bnb.training, mask=lb.bits)
         dcat, dwb, _ = lin_bwd(priors, dcb, L, need_w=need_w, col_map=cmap, x2=x)
         if need_w:
             dwb = dwb.view(bt[0].weight.shape)
-        dstage = torch.empty_like(stage_act)
-        dc_all = torch.empty_like(stage_act)
-        gstage, off = [], 0
-        call = sv[10 + 3 * nl]
-        if _PSP_GROUPED:
-            # round 6: the four levels' BatchNorm + ReLU backward in one launch and their stage-conv weight gradients in one launch (the PSPNet-POP pyramid's kernels:
-            # ops.ppm_stage_bn_bwd, ops.ppm_rows_wgrad) instead of four (reduce, finalize, apply, weight gradient, slab reduce) chains: 16 launches less per step
-            for k, s in enumerate(sizes):
-                n = B * s * s
-                osw.bilinear_bwd(dcat, (s, s), True, out=dstage[off:off + n].view(B, s, s, Ps), Cn=Ps, dy_off=k * Ps)
-                off += n
-            dgb_l = torch.empty((nl, 2, Ps), dtype=torch.float32, device=x.device)
-            ops.ppm_stage_bn_bwd(dstage, stage_act, call, B, sizes, ml, il, [_bn_padded(st[2], Ps)[0] for st in psp.stages], [st[2].training for st in psp.stages],
-                                 [dgb_l[k, 0] for k in range(nl)], [dgb_l[k, 1] for k in range(nl)], out=dc_all)
-            dws_l = ops.ppm_rows_wgrad(dc_all, pooled, B, sizes) if need_w else None
-            for k in range(nl):
-                gstage += [dws_l[k].view(Ps, Cf)[:Cs].view_as(psp.stages[k][1].weight) if need_w else None,
-                           dgb_l[k, 0, :Cs] if need_w else None, dgb_l[k, 1, :Cs] if need_w else None]
-        else:
-            for k, (s, st) in enumerate(zip(sizes, psp.stages)):
-                n = B * s * s
-                osw.bilinear_bwd(dcat, (s, s), True, out=dstage[off:off + n].view(B, s, s, Ps), Cn=Ps, dy_off=k * Ps)
-                gwk = _bn_padded(st[2], Ps)[0]
-                _, _, dgs, dbs = ops.bn_bwd(dstage[off:off + n], stage_act[off:off + n], cl[k], ml[k], il[k], gwk, train=st[2].training, out=dc_all[off:off + n])
-                dws = None
-                if need_w:
-                    dws = ops.conv2d_bwd_weight(pooled[off:off + n].view(B, s, s, Cf), dc_all[off:off + n].view(B, s, s, Ps), ConvSpec(Cf, Ps, 1))[:Cs].contiguous()
-                gstage += [dws, dgs[:Cs].contiguous() if need_w else None, dbs[:Cs].contiguous() if need_w else None]
-                off += n
-        dx = None
-        if need_x:
-            dpooled = ops.ppm_rows_gemm(dc_all, wst.transpose(1, 2).contiguous(), B, sizes)[0]
-            dx = ops.ppm_pool_bwd(dpooled, x.shape, x.dtype, sizes, dcat=dcat, cat_off=nl * Ps)
+        dstage, off = torch.empty_like(rec.stage_act), 0
+        for k, s in enumerate(sizes):
+            n = B * s * s
+            osw.bilinear_bwd(dcat, (s, s), True, out=dstage[off:off + n].view(B, s, s, Ps), Cn=Ps, dy_off=k * Ps)
+            off += n
+        dx, gstage = stages_bwd(psp_stages(psp), rec, dstage, x.shape, x.dtype, need_w, need_x, dcat, nl * Ps)
         Cb = bnb.num_features
         return (dx, None, None, *gstage, dwb, dgb[:Cb].contiguous() if need_w else None, dbb[:Cb].contiguous() if need_w else None)
 
