@@ -357,7 +357,9 @@ int sl_ppm_fact_scatter(const SlPpmDesc* d, int N, const void* dcb, float* gq, v
  * pspnet_pop.py:95-121 orthogonal_decompose + :178-182 / :210-219 classifier on the components, evaluated in the
  * exactly equivalent collapsed form: for a class k with unit prototype s_k and p = s_k.q,
  * MLP(p*s_k) = max(p,0)*MLP(s_k) + max(-p,0)*MLP(-s_k) because the MLP is bias-free and ReLU is positively
- * homogeneous; only the residual (background) feature needs the per-pixel MLP. */
+ * homogeneous; only the residual (background) feature needs the per-pixel MLP.
+ * sl_pop_decompose_fwd/bwd and sl_pop_combine_fwd/bwd take 1 <= Kt <= 32 prototypes (base + novel; 33 logit channels with background), C = 128, 256 or 512; up to
+ * 16 prototypes run on kernels that hold all of them at once, 17..32 on kernels that walk two chunks of 16.  More than 32 is SL_EINVAL and the message names the limit. */
 /* proj[r][k] = S[k].q[r];  bg[r] = q[r] - sum_k proj[r][k] S[k].   S: float[Kt][C], already L2-normalised. */
 int sl_pop_decompose_fwd(int dtype, const void* feats, const float* S, int Kt, float* proj, void* bg, long long R,
                          int C, sl_stream_t stream);
@@ -417,7 +419,9 @@ int sl_pop_decompose_bwd(int dtype, const void* dg, const void* feats, const flo
 
 /* ------------------------------------------------------------------------------------------------ loss
  * loss/criterion.py:51-52: F.interpolate(bilinear, align_corners=True) to the label size fused with
- * CrossEntropyLoss(ignore_index, mean); the H x W logits are never written. */
+ * CrossEntropyLoss(ignore_index, mean); the H x W logits are never written.
+ * sl_upsample_ce_fwd/bwd, sl_pseudo_label, sl_upsample_argmax and sl_upsample_logits take 1 <= K <= 33 logit channels (background + 32 prototypes); more is SL_EINVAL
+ * and the message names the limit.  The backward's tiled kernel cuts more than 16 channels into slices of at most 16 (its LDS holds one slice of the tile's footprint). */
 int sl_upsample_ce_rows(int B, int H, int W);
 /* partial[blk][2] = (sum of pixel losses, number of valid pixels) */
 int sl_upsample_ce_fwd(const float* logits, const int64_t* target, int B, int K, int h, int w, int H, int W,

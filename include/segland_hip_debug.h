@@ -31,6 +31,7 @@ void sl_debug_wgrad_bias(int on);          /* bias-gradient column sums inside t
 void sl_debug_wgrad_tr(int on);            /* ds_read_b64_tr_b16 fragment reads vs scalar LDS reads (bit-identical) */
 void sl_debug_wgrad_pair_min(int rows);    /* pixel-pair weight gradients from this many rows (0: the built-in rule) */
 void sl_debug_attn_valu(int v);            /* 1: window attention on the VALU reference kernels, -1: default (MFMA for bf16) */
+void sl_debug_ce_tiled(int on);            /* tiled upsample + cross-entropy backward (one-pass up to 16 channels, channel-sliced above) vs the per-cell gather kernel */
 
 /* s_memtime phase stamps: a device buffer the named kernel fills, NULL detaches (production) */
 void sl_debug_p8_trace(void* buf);         /* conv_gemm_p8_kernel: [blocks][8] u64 */

@@ -38,6 +38,7 @@ extern "C" void sl_debug_wgrad_bias(int v) { g_sl_debug.wgrad_bias = v ? 1 : 0; 
 extern "C" void sl_debug_wgrad_tr(int v) { g_sl_debug.wgrad_tr = v ? 1 : 0; }
 extern "C" void sl_debug_wgrad_pair_min(int rows) { g_sl_debug.wgrad_pair_min_rows = rows; }
 extern "C" void sl_debug_attn_valu(int v) { g_sl_debug.attn_valu = v; }
+extern "C" void sl_debug_ce_tiled(int v) { g_sl_debug.ce_tiled = v ? 1 : 0; }
 extern "C" void sl_debug_p8_trace(void* buf) { g_sl_debug.p8_trace = (unsigned long long*)buf; }
 extern "C" void sl_debug_wgrad_trace(void* buf) { g_sl_debug.wgrad_trace = (unsigned long long*)buf; }
 extern "C" void sl_debug_wgrad3_trace(void* buf) { g_sl_debug.wgrad3_trace = (unsigned long long*)buf; }

@@ -105,6 +105,7 @@ struct SlDebugState {
   int wgrad_tr = 1;                // bf16 fragments by ds_read_b64_tr_b16 (0: scalar LDS reads; the two must agree bit for bit)
   long long wgrad_pair_min_rows = 0;  // > 0: 1x1 layers with a 64- (not 128-) multiple channel count run as pixel pairs from this many rows
   int attn_valu = -1;              // 1: window attention on the VALU kernels (the MFMA kernels' reference)
+  int ce_tiled = 1;                // tiled upsample + cross-entropy backward where its footprint fits the LDS (0: the per-cell gather kernel takes every launch)
   unsigned long long* p8_trace = nullptr;      // [blocks][8] u64 phase stamps (tools/p8_trace.py)
   unsigned long long* wgrad_trace = nullptr;   // [blocks][8] (tools/wgrad_trace.py)
   unsigned long long* wgrad3_trace = nullptr;  // [blocks][8]

@@ -5,7 +5,9 @@
 
 namespace {
 
-constexpr int KMAXC = 16;   // max logit channels
+constexpr int KMAXC = 33;  // max logit channels (background + 32 prototypes) of sl_upsample_ce_* / sl_pseudo_label / sl_upsample_argmax / sl_upsample_logits: the ONE limit of this file
+constexpr int KNC = 16;    // up to KNC channels run on the <KNC> instantiations and the one-pass tiled backward (device code as before the wide head); more on <KMAXC> and the
+                           // channel-sliced tiled backward.  KW below is the per-thread array width of an instantiation.
 
 struct UpGeom { int B, K, h, w, H, W; float sy, sx; };
 
@@ -21,6 +23,7 @@ __device__ __forceinline__ void src_index_ac1(int dst, int in, float scale, int&
 }
 
 // interpolated logits of pixel (Y,X) of image b into v[0..K)
+template <int KW>
 __device__ __forceinline__ void pixel_logits(const UpGeom& g, const float* __restrict__ lg, int b, int Y, int X, float* v) {
   int y0, y1, x0, x1; float ly, lx;
   src_index_ac1(Y, g.h, g.sy, y0, y1, ly);
@@ -28,7 +31,7 @@ __device__ __forceinline__ void pixel_logits(const UpGeom& g, const float* __res
   const float wy0 = 1.f - ly, wx0 = 1.f - lx;
   const float* p = lg + (size_t)b * g.K * g.h * g.w;
 #pragma unroll
-  for (int k = 0; k < KMAXC; ++k) {
+  for (int k = 0; k < KW; ++k) {
     if (k < g.K) {
       const float* q = p + (size_t)k * g.h * g.w;
       v[k] = wy0 * (wx0 * q[y0 * g.w + x0] + lx * q[y0 * g.w + x1]) + ly * (wx0 * q[y1 * g.w + x0] + lx * q[y1 * g.w + x1]);
@@ -36,6 +39,7 @@ __device__ __forceinline__ void pixel_logits(const UpGeom& g, const float* __res
   }
 }
 
+template <int KW>
 __global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(UpGeom g, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
                                                               int ignore, float* __restrict__ part) {
   __shared__ float red[2][4];
@@ -46,14 +50,14 @@ __global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(UpGeom g, const fl
     if (t == ignore || t < 0 || t >= g.K) continue;
     const int X = (int)(i % g.W); const long long r = i / g.W;
     const int Y = (int)(r % g.H), b = (int)(r / g.H);
-    float v[KMAXC];
-    pixel_logits(g, lg, b, Y, X, v);
+    float v[KW];
+    pixel_logits<KW>(g, lg, b, Y, X, v);
     float m = v[0], vt = 0.f;
 #pragma unroll
-    for (int k = 0; k < KMAXC; ++k) { m = fmaxf(m, v[k]); if (k == (int)t) vt = v[k]; }
+    for (int k = 0; k < KW; ++k) { m = fmaxf(m, v[k]); if (k == (int)t) vt = v[k]; }
     float s = 0.f;
 #pragma unroll
-    for (int k = 0; k < KMAXC; ++k) if (k < g.K) s += expf(v[k] - m);
+    for (int k = 0; k < KW; ++k) if (k < g.K) s += expf(v[k] - m);
     loss += logf(s) + m - vt;
     cnt += 1.f;
   }
@@ -82,6 +86,7 @@ __global__ void upsample_ce_finalize_kernel(const float* __restrict__ part, int 
 
 // four lanes per low-resolution cell (each takes every 4th footprint row), gather over the pixels whose bilinear
 // footprint touches the cell, then a 4-lane shuffle reduction: deterministic, no atomics.
+template <int KW>
 __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
                                                               const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
                                                               int ignore, float* __restrict__ dlg) {
@@ -92,9 +97,9 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
   const long long cc = live ? ci : 0;
   const int j = (int)(cc % g.w); const long long r = cc / g.w;
   const int i = (int)(r % g.h), b = (int)(r / g.h);
-  float acc[KMAXC];
+  float acc[KW];
 #pragma unroll
-  for (int k = 0; k < KMAXC; ++k) acc[k] = 0.f;
+  for (int k = 0; k < KW; ++k) acc[k] = 0.f;
   const int Ylo = g.sy > 0.f ? max(0, (int)floorf((float)(i - 1) / g.sy)) : 0;
   const int Yhi = g.sy > 0.f ? min(g.H - 1, (int)ceilf((float)(i + 1) / g.sy)) : g.H - 1;
   const int Xlo = g.sx > 0.f ? max(0, (int)floorf((float)(j - 1) / g.sx)) : 0;
@@ -112,23 +117,23 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
         if (wx == 0.f) continue;
         const long long t = tgt[((size_t)b * g.H + Y) * g.W + X];
         if (t == ignore || t < 0 || t >= g.K) continue;
-        float v[KMAXC];
-        pixel_logits(g, lg, b, Y, X, v);
+        float v[KW];
+        pixel_logits<KW>(g, lg, b, Y, X, v);
         float m = v[0];
 #pragma unroll
-        for (int k = 0; k < KMAXC; ++k) m = fmaxf(m, v[k]);
+        for (int k = 0; k < KW; ++k) m = fmaxf(m, v[k]);
         float s = 0.f;
 #pragma unroll
-        for (int k = 0; k < KMAXC; ++k) { v[k] = k < g.K ? expf(v[k] - m) : 0.f; s += v[k]; }
+        for (int k = 0; k < KW; ++k) { v[k] = k < g.K ? expf(v[k] - m) : 0.f; s += v[k]; }
         const float wgt = wy * wx, inv = 1.f / s;
 #pragma unroll
-        for (int k = 0; k < KMAXC; ++k) acc[k] += wgt * (v[k] * inv - (k == (int)t ? 1.f : 0.f));
+        for (int k = 0; k < KW; ++k) acc[k] += wgt * (v[k] * inv - (k == (int)t ? 1.f : 0.f));
       }
     }
   }
   const float f = gscale[0] / loss_cnt[1];
 #pragma unroll
-  for (int k = 0; k < KMAXC; ++k) {
+  for (int k = 0; k < KW; ++k) {
     float a = acc[k];
     a += __shfl_xor(a, 1, 64);
     a += __shfl_xor(a, 2, 64);
@@ -147,6 +152,7 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
                                                                     const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
                                                                     int ignore, float* __restrict__ dlg) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
+  constexpr int KW = KNC;                            // this kernel serves K <= KNC (G holds all K channels of every footprint pixel)
   const int K = g.K;
   float* lgt = sm;                                   // [(CT+2)^2][K] logits of the cells around the tile (clamped at the map border)
   float* wy0 = lgt + (CT + 2) * (CT + 2) * K;        // per footprint row: weight on cell y0, weight on y1 ; y0 as int
@@ -222,19 +228,19 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
     const float* q01 = lgt + (ry0 * (CT + 2) + rx1) * K;
     const float* q10 = lgt + (ry1 * (CT + 2) + rx0) * K;
     const float* q11 = lgt + (ry1 * (CT + 2) + rx1) * K;
-    float v[KMAXC];
+    float v[KW];
     float m = -INFINITY;
 #pragma unroll
-    for (int k = 0; k < KMAXC; ++k) {
+    for (int k = 0; k < KW; ++k) {
       if (k < K) { v[k] = wya * (wxa * q00[k] + lx * q01[k]) + ly * (wxa * q10[k] + lx * q11[k]); m = fmaxf(m, v[k]); }
       else v[k] = -INFINITY;
     }
     float ssum = 0.f;
 #pragma unroll
-    for (int k = 0; k < KMAXC; ++k) { v[k] = k < K ? __expf(v[k] - m) : 0.f; ssum += v[k]; }      // hardware exp2-based: 2 ulp, the gradient's tolerance is 1e-3
+    for (int k = 0; k < KW; ++k) { v[k] = k < K ? __expf(v[k] - m) : 0.f; ssum += v[k]; }      // hardware exp2-based: 2 ulp, the gradient's tolerance is 1e-3
     const float inv = 1.f / ssum;
 #pragma unroll
-    for (int k = 0; k < KMAXC; ++k) if (k < K) out[k] = v[k] * inv - (k == (int)t ? 1.f : 0.f);
+    for (int k = 0; k < KW; ++k) if (k < K) out[k] = v[k] * inv - (k == (int)t ? 1.f : 0.f);
   }
   __syncthreads();
   // ---- pass 2a: along X
@@ -263,7 +269,133 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
   }
 }
 
-template <bool PSEUDO>
+// The tiled gradient for K > KNC.  G[NY][NX][K] does not fit the LDS any more (x8 upsampling, CT = 4: 44 x 44 pixels x 33 channels x 4 B = 256 KB of 160 KiB), so
+// the channels go through G and H1 in slices of KS <= KNC (the host picks the fewest slices that fit).  One pass over the footprint first computes every pixel's
+// max and 1 / sum over ALL K channels from lgt and keeps them with the label (three words per pixel); passes 1, 2a, 2b then run once per slice on those statistics.
+// Each pixel's softmax is still evaluated once (2 K exponentials instead of K); sums in a fixed order, no atomics.
+struct UpTileW { int NYmax, NXmax, KS; };
+struct UpTap {            // the four neighbourhood cells a footprint pixel interpolates from, and its weights
+  const float *q00, *q01, *q10, *q11;
+  float wya, wxa, ly, lx;
+  __device__ __forceinline__ float at(int k) const { return wya * (wxa * q00[k] + lx * q01[k]) + ly * (wxa * q10[k] + lx * q11[k]); }
+};
+__device__ __forceinline__ UpTap up_tap(const float* lgt, const float* wy0, const float* wx0, int yr, int xr, int i0, int j0, int K) {
+  const int y0 = __float_as_int(wy0[3 * yr]), y1 = __float_as_int(wy0[3 * yr + 1]);
+  const int x0 = __float_as_int(wx0[3 * xr]), x1 = __float_as_int(wx0[3 * xr + 1]);
+  UpTap t;
+  t.ly = wy0[3 * yr + 2]; t.lx = wx0[3 * xr + 2];
+  t.wya = 1.f - t.ly; t.wxa = 1.f - t.lx;
+  // a rim pixel may interpolate from a cell outside the (CT+2)^2 neighbourhood; it has zero weight on every cell of this tile: clamp the index (as in the one-pass kernel)
+  const int ry0 = min(max(y0 - i0 + 1, 0), CT + 1), ry1 = min(max(y1 - i0 + 1, 0), CT + 1);
+  const int rx0 = min(max(x0 - j0 + 1, 0), CT + 1), rx1 = min(max(x1 - j0 + 1, 0), CT + 1);
+  t.q00 = lgt + (ry0 * (CT + 2) + rx0) * K; t.q01 = lgt + (ry0 * (CT + 2) + rx1) * K;
+  t.q10 = lgt + (ry1 * (CT + 2) + rx0) * K; t.q11 = lgt + (ry1 * (CT + 2) + rx1) * K;
+  return t;
+}
+template <int NT>
+__global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g, UpTileW ut, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
+                                                                         const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
+                                                                         int ignore, float* __restrict__ dlg) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int K = g.K, KS = ut.KS;
+  float* lgt = sm;                                   // [(CT+2)^2][K]
+  float* wy0 = lgt + (CT + 2) * (CT + 2) * K;        // as in the one-pass kernel
+  float* wx0 = wy0 + 3 * ut.NYmax;
+  float* wxj = wx0 + 3 * ut.NXmax;                   // [NX][CT]
+  float* wyi = wxj + CT * ut.NXmax;                  // [NY][CT]
+  float* st = wyi + CT * ut.NYmax;                   // [NY][NX][3]: max, 1 / sum, label as int (-1: the pixel does not count)
+  float* H1 = st + 3 * ut.NYmax * ut.NXmax;          // [NY][CT][KS]
+  float* G = H1 + ut.NYmax * CT * KS;                // [NY][NX][KS]
+  const int tid = threadIdx.x;
+  const int tw = cdiv(g.w, CT), th = cdiv(g.h, CT);
+  int blk = blockIdx.x;
+  const int tj = blk % tw; blk /= tw;
+  const int ti = blk % th; const int b = blk / th;
+  const int i0 = ti * CT, j0 = tj * CT;
+  const int i1 = min(i0 + CT, g.h) - 1, j1 = min(j0 + CT, g.w) - 1;          // last cell of the tile
+  const int Ylo = g.sy > 0.f ? max(0, (int)floorf((float)(i0 - 1) / g.sy)) : 0;
+  const int Yhi = g.sy > 0.f ? min(g.H - 1, (int)ceilf((float)(i1 + 1) / g.sy)) : g.H - 1;
+  const int Xlo = g.sx > 0.f ? max(0, (int)floorf((float)(j0 - 1) / g.sx)) : 0;
+  const int Xhi = g.sx > 0.f ? min(g.W - 1, (int)ceilf((float)(j1 + 1) / g.sx)) : g.W - 1;
+  const int NY = Yhi - Ylo + 1, NX = Xhi - Xlo + 1;
+  const float* lb = lg + (size_t)b * K * g.h * g.w;
+  for (int e = tid; e < (CT + 2) * (CT + 2) * K; e += NT) {
+    const int k = e % K, c = e / K, cy = c / (CT + 2), cx = c - cy * (CT + 2);
+    const int yy = min(max(i0 - 1 + cy, 0), g.h - 1), xx = min(max(j0 - 1 + cx, 0), g.w - 1);
+    lgt[e] = lb[((size_t)k * g.h + yy) * g.w + xx];
+  }
+  for (int e = tid; e < NY; e += NT) {
+    int y0, y1; float ly; src_index_ac1(Ylo + e, g.h, g.sy, y0, y1, ly);
+    wy0[3 * e] = __int_as_float(y0); wy0[3 * e + 1] = __int_as_float(y1); wy0[3 * e + 2] = ly;
+#pragma unroll
+    for (int r = 0; r < CT; ++r) wyi[e * CT + r] = (y0 == i0 + r ? 1.f - ly : 0.f) + (y1 == i0 + r ? ly : 0.f);
+  }
+  for (int e = tid; e < NX; e += NT) {
+    int x0, x1; float lx; src_index_ac1(Xlo + e, g.w, g.sx, x0, x1, lx);
+    wx0[3 * e] = __int_as_float(x0); wx0[3 * e + 1] = __int_as_float(x1); wx0[3 * e + 2] = lx;
+#pragma unroll
+    for (int r = 0; r < CT; ++r) wxj[e * CT + r] = (x0 == j0 + r ? 1.f - lx : 0.f) + (x1 == j0 + r ? lx : 0.f);
+  }
+  __syncthreads();
+  // ---- pass 0: max and 1 / sum over all K channels of every footprint pixel, once
+  for (int pix = tid; pix < NY * NX; pix += NT) {
+    const int yr = pix / NX, xr = pix - yr * NX;
+    const long long t = tgt[((size_t)b * g.H + Ylo + yr) * g.W + Xlo + xr];
+    float* s = st + 3 * pix;
+    if (t == ignore || t < 0 || t >= K) { s[2] = __int_as_float(-1); continue; }
+    const UpTap tap = up_tap(lgt, wy0, wx0, yr, xr, i0, j0, K);
+    float m = -INFINITY;
+    for (int k = 0; k < K; ++k) m = fmaxf(m, tap.at(k));
+    float ssum = 0.f;
+    for (int k = 0; k < K; ++k) ssum += __expf(tap.at(k) - m);
+    s[0] = m; s[1] = 1.f / ssum; s[2] = __int_as_float((int)t);
+  }
+  __syncthreads();
+  const float f = gscale[0] / loss_cnt[1];
+  for (int k0 = 0; k0 < K; k0 += KS) {
+    const int kn = min(KS, K - k0);
+    // ---- pass 1: softmax - onehot of the slice's channels
+    for (int pix = tid; pix < NY * NX; pix += NT) {
+      const int yr = pix / NX, xr = pix - yr * NX;
+      const float* s = st + 3 * pix;
+      float* out = G + (size_t)pix * KS;
+      const int t = __float_as_int(s[2]);
+      if (t < 0) {
+        for (int kk = 0; kk < kn; ++kk) out[kk] = 0.f;
+        continue;
+      }
+      const UpTap tap = up_tap(lgt, wy0, wx0, yr, xr, i0, j0, K);
+      const float m = s[0], inv = s[1];
+      for (int kk = 0; kk < kn; ++kk) out[kk] = __expf(tap.at(k0 + kk) - m) * inv - (k0 + kk == t ? 1.f : 0.f);
+    }
+    __syncthreads();
+    // ---- pass 2a: along X
+    for (int e = tid; e < NY * CT * kn; e += NT) {
+      const int kk = e % kn, r = e / kn, jr = r % CT, yr = r / CT;
+      const int j = j0 + jr;
+      float acc = 0.f;
+      if (j <= j1) {
+        const int xa = (g.sx > 0.f ? max(Xlo, (int)floorf((float)(j - 1) / g.sx)) : Xlo) - Xlo, xb = (g.sx > 0.f ? min(Xhi, (int)ceilf((float)(j + 1) / g.sx)) : Xhi) - Xlo;
+        const float* grow = G + (size_t)yr * NX * KS + kk;
+        for (int xr = xa; xr <= xb; ++xr) acc += wxj[xr * CT + jr] * grow[xr * KS];
+      }
+      H1[(yr * CT + jr) * KS + kk] = acc;
+    }
+    __syncthreads();
+    // ---- pass 2b: along Y, scale, store.  The next slice's pass 1 writes G only, and H1 is written again after the barrier that follows it.
+    for (int e = tid; e < CT * CT * kn; e += NT) {
+      const int kk = e % kn, c = e / kn, ir = c / CT, jr = c - ir * CT;
+      const int i = i0 + ir, j = j0 + jr;
+      if (i > i1 || j > j1) continue;
+      const int ya = g.sy > 0.f ? max(Ylo, (int)floorf((float)(i - 1) / g.sy)) : Ylo, yb = g.sy > 0.f ? min(Yhi, (int)ceilf((float)(i + 1) / g.sy)) : Yhi;
+      float acc = 0.f;
+      for (int yr = ya - Ylo; yr <= yb - Ylo; ++yr) acc += wyi[yr * CT + ir] * H1[(yr * CT + jr) * KS + kk];
+      dlg[(((size_t)b * K + k0 + kk) * g.h + i) * g.w + j] = acc * f;
+    }
+  }
+}
+
+template <bool PSEUDO, int KW>
 __global__ void upsample_argmax_kernel(UpGeom g, const float* __restrict__ lg, uint8_t* __restrict__ labels, int64_t* __restrict__ mask,
                                        int n_base) {
   const long long total = (long long)g.B * g.H * g.W;
@@ -271,27 +403,28 @@ __global__ void upsample_argmax_kernel(UpGeom g, const float* __restrict__ lg, u
     if (PSEUDO && mask[i] != 0) continue;
     const int X = (int)(i % g.W); const long long r = i / g.W;
     const int Y = (int)(r % g.H), b = (int)(r / g.H);
-    float v[KMAXC];
-    pixel_logits(g, lg, b, Y, X, v);
+    float v[KW];
+    pixel_logits<KW>(g, lg, b, Y, X, v);
     int best = 0; float bv = v[0];
 #pragma unroll
-    for (int k = 1; k < KMAXC; ++k) if (k < g.K && v[k] > bv) { bv = v[k]; best = k; }   // first maximum wins (torch.argmax)
+    for (int k = 1; k < KW; ++k) if (k < g.K && v[k] > bv) { bv = v[k]; best = k; }   // first maximum wins (torch.argmax)
     if (PSEUDO) mask[i] = best > 0 ? best + n_base : 0;
     else labels[i] = (uint8_t)best;
   }
 }
 
 // probability-map dump of eval_base.py:168,189-190: the full-resolution logits F.interpolate(align_corners=True) produced, NCHW float
+template <int KW>
 __global__ void upsample_logits_kernel(UpGeom g, const float* __restrict__ lg, float* __restrict__ out) {
   const long long total = (long long)g.B * g.H * g.W;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int X = (int)(i % g.W); const long long r = i / g.W;
     const int Y = (int)(r % g.H), b = (int)(r / g.H);
-    float v[KMAXC];
-    pixel_logits(g, lg, b, Y, X, v);
+    float v[KW];
+    pixel_logits<KW>(g, lg, b, Y, X, v);
     const size_t plane = (size_t)g.H * g.W;
 #pragma unroll
-    for (int k = 0; k < KMAXC; ++k) if (k < g.K) out[((size_t)b * g.K + k) * plane + (size_t)Y * g.W + X] = v[k];
+    for (int k = 0; k < KW; ++k) if (k < g.K) out[((size_t)b * g.K + k) * plane + (size_t)Y * g.W + X] = v[k];
   }
 }
 
@@ -399,9 +532,11 @@ extern "C" int sl_upsample_ce_rows(int B, int H, int W) { return ce_blocks((long
 
 extern "C" int sl_upsample_ce_fwd(const float* logits, const int64_t* target, int B, int K, int h, int w, int H, int W,
                                   int ignore_index, float* partial, sl_stream_t stream) {
-  SL_REQUIRE(logits && target && partial && B > 0 && K >= 1 && K <= KMAXC && h > 0 && w > 0 && H > 0 && W > 0, "upsample_ce_fwd: bad args");
+  SL_REQUIRE(logits && target && partial && B > 0 && K >= 1 && h > 0 && w > 0 && H > 0 && W > 0, "upsample_ce_fwd: bad args");
+  SL_REQUIRE(K <= KMAXC, "upsample_ce_fwd: %d logit channels; this build holds at most %d", K, KMAXC);
   const UpGeom g = make_up(B, K, h, w, H, W);
-  hipLaunchKernelGGL(upsample_ce_fwd_kernel, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, target, ignore_index, partial);
+  if (K <= KNC) hipLaunchKernelGGL(upsample_ce_fwd_kernel<KNC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, target, ignore_index, partial);
+  else hipLaunchKernelGGL(upsample_ce_fwd_kernel<KMAXC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, target, ignore_index, partial);
   SL_LAUNCH_CHECK("upsample_ce_fwd_kernel");
   return 0;
 }
@@ -416,11 +551,28 @@ extern "C" int sl_upsample_ce_finalize(const float* partial, int nblk, float* lo
 extern "C" int sl_upsample_ce_bwd(const float* logits, const int64_t* target, const float* loss_and_count, const float* gscale,
                                   int B, int K, int h, int w, int H, int W, int ignore_index, float* dlogits,
                                   sl_stream_t stream) {
-  SL_REQUIRE(logits && target && loss_and_count && gscale && dlogits && K >= 1 && K <= KMAXC, "upsample_ce_bwd: bad args");
+  SL_REQUIRE(logits && target && loss_and_count && gscale && dlogits && K >= 1, "upsample_ce_bwd: bad args");
+  SL_REQUIRE(K <= KMAXC, "upsample_ce_bwd: %d logit channels; this build holds at most %d", K, KMAXC);
   const UpGeom g = make_up(B, K, h, w, H, W);
   const long long cells = (long long)B * h * w;
-  // tiled kernel when the joint footprint of a CT x CT cell tile fits the LDS (always for an upsampling factor <= ~12 at K <= 16)
-  if (g.sy > 0.f && g.sx > 0.f) {
+  // tiled kernel when the joint footprint of a CT x CT cell tile fits the LDS (always for an upsampling factor <= ~12 at K <= 16); test hook sl_debug_ce_tiled(0): never
+  if (g.sy > 0.f && g.sx > 0.f && g_sl_debug.ce_tiled && K > KNC) {
+    // channel-sliced form: the fewest slices (of at most KNC channels) whose G and H1 fit next to the per-pixel statistics
+    UpTileW ut;
+    ut.NYmax = (int)ceilf((float)(CT + 1) / g.sy) + 3; if (ut.NYmax > H) ut.NYmax = H;
+    ut.NXmax = (int)ceilf((float)(CT + 1) / g.sx) + 3; if (ut.NXmax > W) ut.NXmax = W;
+    const size_t fixed = (size_t)(CT + 2) * (CT + 2) * K + (3 + CT) * (ut.NYmax + ut.NXmax) + 3 * (size_t)ut.NYmax * ut.NXmax;
+    for (int ns = cdiv(K, KNC); ns <= K; ++ns) {
+      ut.KS = cdiv(K, ns);
+      const size_t lds = (fixed + (size_t)ut.NYmax * CT * ut.KS + (size_t)ut.NYmax * ut.NXmax * ut.KS) * sizeof(float);
+      if (lds > 150 * 1024) continue;
+      static bool opted = false;
+      if (!opted) { (void)hipFuncSetAttribute((const void*)upsample_ce_bwd_tiled_wide_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); opted = true; }
+      hipLaunchKernelGGL(upsample_ce_bwd_tiled_wide_kernel<512>, dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(512), lds, (hipStream_t)stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits);
+      SL_LAUNCH_CHECK("upsample_ce_bwd_tiled_wide_kernel");
+      return 0;
+    }
+  } else if (g.sy > 0.f && g.sx > 0.f && g_sl_debug.ce_tiled) {
     UpTile ut;
     ut.NYmax = (int)ceilf((float)(CT + 1) / g.sy) + 3; if (ut.NYmax > H) ut.NYmax = H;
     ut.NXmax = (int)ceilf((float)(CT + 1) / g.sx) + 3; if (ut.NXmax > W) ut.NXmax = W;
@@ -436,33 +588,40 @@ extern "C" int sl_upsample_ce_bwd(const float* logits, const int64_t* target, co
       return 0;
     }
   }
-  hipLaunchKernelGGL(upsample_ce_bwd_kernel, dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, logits, target, loss_and_count, gscale, ignore_index, dlogits);
+  if (K <= KNC) hipLaunchKernelGGL(upsample_ce_bwd_kernel<KNC>, dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, logits, target, loss_and_count, gscale, ignore_index, dlogits);
+  else hipLaunchKernelGGL(upsample_ce_bwd_kernel<KMAXC>, dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, logits, target, loss_and_count, gscale, ignore_index, dlogits);
   SL_LAUNCH_CHECK("upsample_ce_bwd_kernel");
   return 0;
 }
 
 extern "C" int sl_pseudo_label(const float* logits, int K2, int h, int w, int64_t* mask, int B, int H, int W, int n_base,
                                sl_stream_t stream) {
-  SL_REQUIRE(logits && mask && K2 >= 1 && K2 <= KMAXC && B > 0, "pseudo_label: bad args");
+  SL_REQUIRE(logits && mask && K2 >= 1 && B > 0, "pseudo_label: bad args");
+  SL_REQUIRE(K2 <= KMAXC, "pseudo_label: %d logit channels; this build holds at most %d", K2, KMAXC);
   const UpGeom g = make_up(B, K2, h, w, H, W);
-  hipLaunchKernelGGL(upsample_argmax_kernel<true>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, (uint8_t*)nullptr, mask, n_base);
+  if (K2 <= KNC) hipLaunchKernelGGL((upsample_argmax_kernel<true, KNC>), dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, (uint8_t*)nullptr, mask, n_base);
+  else hipLaunchKernelGGL((upsample_argmax_kernel<true, KMAXC>), dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, (uint8_t*)nullptr, mask, n_base);
   SL_LAUNCH_CHECK("pseudo_label_kernel");
   return 0;
 }
 
 extern "C" int sl_upsample_argmax(const float* logits, int B, int K, int h, int w, int H, int W, uint8_t* labels,
                                   sl_stream_t stream) {
-  SL_REQUIRE(logits && labels && K >= 1 && K <= KMAXC && B > 0, "upsample_argmax: bad args");
+  SL_REQUIRE(logits && labels && K >= 1 && B > 0, "upsample_argmax: bad args");
+  SL_REQUIRE(K <= KMAXC, "upsample_argmax: %d logit channels; this build holds at most %d", K, KMAXC);
   const UpGeom g = make_up(B, K, h, w, H, W);
-  hipLaunchKernelGGL(upsample_argmax_kernel<false>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, labels, (int64_t*)nullptr, 0);
+  if (K <= KNC) hipLaunchKernelGGL((upsample_argmax_kernel<false, KNC>), dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, labels, (int64_t*)nullptr, 0);
+  else hipLaunchKernelGGL((upsample_argmax_kernel<false, KMAXC>), dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, labels, (int64_t*)nullptr, 0);
   SL_LAUNCH_CHECK("upsample_argmax_kernel");
   return 0;
 }
 
 extern "C" int sl_upsample_logits(const float* logits, int B, int K, int h, int w, int H, int W, float* out, sl_stream_t stream) {
-  SL_REQUIRE(logits && out && K >= 1 && K <= KMAXC && B > 0, "upsample_logits: bad args");
+  SL_REQUIRE(logits && out && K >= 1 && B > 0, "upsample_logits: bad args");
+  SL_REQUIRE(K <= KMAXC, "upsample_logits: %d logit channels; this build holds at most %d", K, KMAXC);
   const UpGeom g = make_up(B, K, h, w, H, W);
-  hipLaunchKernelGGL(upsample_logits_kernel, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, out);
+  if (K <= KNC) hipLaunchKernelGGL(upsample_logits_kernel<KNC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, out);
+  else hipLaunchKernelGGL(upsample_logits_kernel<KMAXC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, out);
   SL_LAUNCH_CHECK("upsample_logits_kernel");
   return 0;
 }

@@ -4,11 +4,15 @@
 //   pred[r][0] = MLP(bg_r)            pred[r][1+k] = a_k max(p,0) + b_k max(-p,0),  a_k = MLP(S_k), b_k = MLP(-S_k)
 // A pixel row is owned by LPR lanes of a wavefront (C = LPR x 16-byte vectors x NV: 64 lanes for the 512-channel PSPNet head, 16 / 32
 // lanes -- 4 / 2 rows per wavefront -- for the 128-channel Swin head), shuffle reductions inside the LPR-lane group for the K projections.
+// Limit: KMAXP = 32 prototypes (base + novel; 33 logit channels).  Up to KCH = 16 the kernels hold every prototype at once; 17..32 run on the *_wide kernels, which walk
+// two chunks of KCH.  sl_pop_proto_* keep their own, smaller limit (pp_fits).
 #include "common.h"
 
 namespace {
 
-constexpr int KMAXP = 16;  // max prototypes (base + novel)
+constexpr int KMAXP = 32;  // max prototypes (base + novel) of sl_pop_decompose_* / sl_pop_combine_*: the ONE limit of this file (33 logit channels with background)
+constexpr int KCH = 16;    // prototypes per chunk: up to KCH run on the kernels that hold every prototype's accumulators at once (unchanged device code), more on the
+                           // *_wide kernels below, which walk KMAXP / KCH chunks
 
 template <int LPR> __device__ __forceinline__ float group_sum(float v) {      // sum over the LPR lanes that share a row
 #pragma unroll
@@ -53,6 +57,22 @@ __device__ __forceinline__ void group_sum_multi(float (&d)[KM], int lane) {
 // (a scalar load -> store loop was 16 dependent memory round trips at the top of every block)
 template <int N>
 __device__ __forceinline__ void pop_fill_protos(const float* __restrict__ S, int n, float* Sl) {
+  static_assert(N % 1024 == 0, "prototype tile: whole float4 sweeps of the block");
+  constexpr int IT = N / 1024;
+  float4 v[IT];
+#pragma unroll
+  for (int u = 0; u < IT; ++u) {
+    const int e = (u * 256 + threadIdx.x) * 4;
+    v[u] = e + 3 < n ? *(const float4*)(S + e) : make_float4(e < n ? S[e] : 0.f, e + 1 < n ? S[e + 1] : 0.f, e + 2 < n ? S[e + 2] : 0.f, 0.f);
+  }
+#pragma unroll
+  for (int u = 0; u < IT; ++u) *(float4*)(Sl + (u * 256 + threadIdx.x) * 4) = v[u];
+}
+
+// The same fill for the *_wide kernels: all KMAXP rows in one sweep.  A function of its own on purpose: when the wide kernels shared pop_fill_protos' instantiations, the
+// compiler scheduled the prologue of the kernels for <= KCH prototypes differently (tools/device_code_diff.py), and those kernels are to stay instruction-identical.
+template <int N>
+__device__ __forceinline__ void pop_fill_protos_wide(const float* __restrict__ S, int n, float* Sl) {
   static_assert(N % 1024 == 0, "prototype tile: whole float4 sweeps of the block");
   constexpr int IT = N / 1024;
   float4 v[IT];
@@ -125,6 +145,72 @@ __global__ __launch_bounds__(256) void pop_decompose_fwd_kernel(const T* __restr
         for (int j = 0; j < NV; ++j)
 #pragma unroll
           for (int e = 0; e < V; ++e) o[j * V + e] -= d[k] * (SREG ? sreg[k][j * V + e] : Sl[k * C + (j * LPR + sub) * V + e]);
+      }
+    }
+    if (live) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) *(uint4*)(bg + (size_t)r * C + (j * LPR + sub) * V) = pack16<T>(&o[j * V]);
+    }
+  }
+}
+
+// More than KCH prototypes: the same row pipeline, the prototypes walked in chunks of KCH (group_sum_multi needs KCH <= LPR: 16 lanes own a row of the bf16 128-channel
+// head).  All KMAXP rows are resident in the LDS as fp32 ([KMAXP][C]: 64 KiB at 512 channels, the whole default dynamic allowance: two blocks per CU by LDS where 32 KiB
+// admit five); every projection uses q, not the running residual, so the chunking is exact, and the subtractions keep the ascending order of k.  The chunk loop is rolled
+// on purpose: unrolled, the compiler keeps the lane's slice of all 32 rows in 256 VGPRs + ~170-240 AGPRs (one wave per SIMD, 9 % slower at 65 536 rows).
+template <typename T, int NV, int LPR>
+__global__ __launch_bounds__(256) void pop_decompose_fwd_wide_kernel(const T* __restrict__ feats, const float* __restrict__ S, int Kt,
+                                                                     float* __restrict__ proj, T* __restrict__ bg, long long R, int C) {
+  constexpr int V = Vec16<T>::N, RPW = 64 / LPR;
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* Sl = sm;                       // [KMAXP][C], rows >= Kt are zero
+  pop_fill_protos_wide<KMAXP * LPR * NV * V>(S, Kt * C, Sl);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane % LPR, grp = lane / LPR;
+  const int nch = (Kt + KCH - 1) / KCH;
+  const long long rstep = gridDim.x * 4LL * RPW;
+  uint4 nxt[NV];
+  {
+    const long long r = (blockIdx.x * 4LL + wave) * RPW + grp;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) nxt[j] = r < R ? *(const uint4*)(feats + (size_t)r * C + (j * LPR + sub) * V) : make_uint4(0, 0, 0, 0);
+  }
+  for (long long rb = (blockIdx.x * 4LL + wave) * RPW; rb < R; rb += rstep) {
+    const long long r = rb + grp;
+    const bool live = r < R;
+    float q[NV * V], o[NV * V];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) unpack16<T>(nxt[j], &q[j * V]);             // rows past R were loaded as zeros
+    {
+      const long long rn = r + rstep;
+#pragma unroll
+      for (int j = 0; j < NV; ++j) nxt[j] = (rb + rstep < R && rn < R) ? *(const uint4*)(feats + (size_t)rn * C + (j * LPR + sub) * V) : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int e = 0; e < NV * V; ++e) o[e] = q[e];
+#pragma unroll 1
+    for (int ch = 0; ch < nch; ++ch) {                    // block-uniform trip count; the chunk's rows come from the LDS every time (no room to keep 32 rows in registers)
+      const float* Sc = Sl + (size_t)ch * KCH * C;
+      float d[KCH];
+#pragma unroll
+      for (int k = 0; k < KCH; ++k) {
+        float a = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+#pragma unroll
+          for (int e = 0; e < V; ++e) a = fmaf(q[j * V + e], Sc[k * C + (j * LPR + sub) * V + e], a);
+        d[k] = a;
+      }
+      group_sum_multi<LPR, KCH>(d, lane);
+#pragma unroll
+      for (int k = 0; k < KCH; ++k) {                     // k ascending over the chunks
+        if (ch * KCH + k < Kt) {
+          if (sub == 0 && live) proj[(size_t)r * Kt + ch * KCH + k] = d[k];
+#pragma unroll
+          for (int j = 0; j < NV; ++j)
+#pragma unroll
+            for (int e = 0; e < V; ++e) o[j * V + e] -= d[k] * Sc[k * C + (j * LPR + sub) * V + e];
+        }
       }
     }
     if (live) {
@@ -329,15 +415,16 @@ __global__ void pop_combine_fwd_kernel(const float* __restrict__ proj, const flo
   }
 }
 
+template <int KM>      // KM >= Kt prototype slots per thread (unrolled): KCH, or KMAXP for the wide head
 __global__ __launch_bounds__(256) void pop_combine_bwd_kernel(const float* __restrict__ dpreds, const float* __restrict__ proj,
                                                               const float* __restrict__ a, const float* __restrict__ b, int Kt,
                                                               float* __restrict__ dzbg, float* __restrict__ dproj,
                                                               float* __restrict__ dab, int B, int N, long long rows_per_blk) {
-  __shared__ float red[4][2 * KMAXP];
+  __shared__ float red[4][2 * KM];
   const long long R = (long long)B * N;
-  float da[KMAXP], db[KMAXP];
+  float da[KM], db[KM];
 #pragma unroll
-  for (int k = 0; k < KMAXP; ++k) { da[k] = 0.f; db[k] = 0.f; }
+  for (int k = 0; k < KM; ++k) { da[k] = 0.f; db[k] = 0.f; }
   const long long r0 = blockIdx.x * rows_per_blk;
   long long r1 = r0 + rows_per_blk; if (r1 > R) r1 = R;
   for (long long r = r0 + threadIdx.x; r < r1; r += 256) {
@@ -345,7 +432,7 @@ __global__ __launch_bounds__(256) void pop_combine_bwd_kernel(const float* __res
     const float* g = dpreds + (size_t)bb * (1 + Kt) * N + n;
     dzbg[r] = g[0];
 #pragma unroll
-    for (int k = 0; k < KMAXP; ++k) {
+    for (int k = 0; k < KM; ++k) {
       if (k < Kt) {
         const float p = proj[(size_t)r * Kt + k], d = g[(size_t)(1 + k) * N];
         dproj[(size_t)r * Kt + k] = p > 0.f ? d * a[k] : (p < 0.f ? -d * b[k] : 0.f);
@@ -356,14 +443,14 @@ __global__ __launch_bounds__(256) void pop_combine_bwd_kernel(const float* __res
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < KMAXP; ++k) {
+  for (int k = 0; k < KM; ++k) {
     const float x = wave_sum(da[k]), y = wave_sum(db[k]);
-    if (lane == 0) { red[wave][k] = x; red[wave][KMAXP + k] = y; }
+    if (lane == 0) { red[wave][k] = x; red[wave][KM + k] = y; }
   }
   __syncthreads();
   if (threadIdx.x < 2 * Kt) {
     const int k = threadIdx.x % Kt, which = threadIdx.x / Kt;
-    const int s = which * KMAXP + k;
+    const int s = which * KM + k;
     dab[(size_t)blockIdx.x * 2 * Kt + which * Kt + k] = red[0][s] + red[1][s] + red[2][s] + red[3][s];
   }
 }
@@ -455,6 +542,104 @@ __global__ __launch_bounds__(256) void pop_decompose_bwd_kernel(const T* __restr
       for (int c = threadIdx.x; c < C; c += 256)
         dSpart[((size_t)blockIdx.x * Kt + k) * C + c] = red[c] + red[C + c] + red[2 * C + c] + red[3 * C + c];
       __syncthreads();
+    }
+  }
+}
+
+// More than KCH prototypes.  acc[KMAXP][CL] would be 256 accumulator registers per lane, so the block walks its row range once per chunk of KCH prototypes (re-reading dg and
+// feats; the dS accumulators stay in registers).  Pass 0 computes t_k of EVERY chunk (dq needs them all, k ascending) and finishes dq, accumulating dS of chunk 0 only; pass
+// p > 0 recomputes t_k of chunk p alone and accumulates its dS.  Kt = 17 is therefore about three chunk-units of arithmetic against one at Kt = 16 (two in pass 0, one in pass
+// 1, plus the second read of the rows).  The cross-wave reduction of pass p reuses the LDS rows of chunk p, which no later pass reads; fixed order, dS_partial[blk][Kt][C] as
+// in the narrow kernel.
+template <typename T, int NV, int LPR>
+__global__ __launch_bounds__(256) void pop_decompose_bwd_wide_kernel(const T* __restrict__ dg, const T* __restrict__ feats, const float* __restrict__ S,
+                                                                     const float* __restrict__ proj, const float* __restrict__ dproj, int Kt,
+                                                                     T* __restrict__ dq, float* __restrict__ dSpart, long long R, int C,
+                                                                     long long rows_per_blk) {
+  constexpr int V = Vec16<T>::N, CL = NV * V, RPW = 64 / LPR;
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* Sl = sm;                                 // [KMAXP][C], rows >= Kt are zero
+  pop_fill_protos_wide<KMAXP * LPR * NV * V>(S, Kt * C, Sl);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane % LPR, grp = lane / LPR;
+  const int nch = (Kt + KCH - 1) / KCH;
+  const long long r0 = blockIdx.x * rows_per_blk;
+  long long r1 = r0 + rows_per_blk; if (r1 > R) r1 = R;
+#pragma unroll 1
+  for (int pass = 0; pass < nch; ++pass) {
+    float acc[KCH][CL];
+#pragma unroll
+    for (int k = 0; k < KCH; ++k)
+#pragma unroll
+      for (int e = 0; e < CL; ++e) acc[k][e] = 0.f;
+    const int c1 = pass == 0 ? nch : pass + 1;
+    for (long long rb = r0 + wave * RPW; rb < r1; rb += 4 * RPW) {
+      const long long r = rb + grp;
+      const bool live = r < r1;
+      float g[CL], q[CL], o[CL];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        if (live) {
+          unpack16<T>(*(const uint4*)(dg + (size_t)r * C + (j * LPR + sub) * V), &g[j * V]);
+          unpack16<T>(*(const uint4*)(feats + (size_t)r * C + (j * LPR + sub) * V), &q[j * V]);
+        } else {
+#pragma unroll
+          for (int e = 0; e < V; ++e) { g[j * V + e] = 0.f; q[j * V + e] = 0.f; }
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < CL; ++e) o[e] = g[e];
+#pragma unroll 1
+      for (int c = pass; c < c1; ++c) {             // block-uniform
+        const float* Sc = Sl + (size_t)c * KCH * C;
+        const int kb = c * KCH;
+        float d[KCH], tp[KCH], pp[KCH];
+#pragma unroll
+        for (int k = 0; k < KCH; ++k) {
+          float a = 0.f;
+#pragma unroll
+          for (int e = 0; e < CL; ++e) a = fmaf(g[e], Sc[k * C + ((e / V) * LPR + sub) * V + (e % V)], a);
+          d[k] = a;
+          tp[k] = (live && kb + k < Kt) ? dproj[(size_t)r * Kt + kb + k] : 0.f;
+          pp[k] = (live && kb + k < Kt) ? proj[(size_t)r * Kt + kb + k] : 0.f;
+        }
+        group_sum_multi<LPR, KCH>(d, lane);
+#pragma unroll
+        for (int k = 0; k < KCH; ++k) {
+          if (kb + k < Kt) {
+            const float t = live ? tp[k] - d[k] : 0.f, p = pp[k];
+            if (pass == 0) {
+#pragma unroll
+              for (int e = 0; e < CL; ++e) o[e] = fmaf(t, Sc[k * C + ((e / V) * LPR + sub) * V + (e % V)], o[e]);
+            }
+            if (c == pass) {
+#pragma unroll
+              for (int e = 0; e < CL; ++e) acc[k][e] += t * q[e] - p * g[e];
+            }
+          }
+        }
+      }
+      if (pass == 0 && live) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) *(uint4*)(dq + (size_t)r * C + (j * LPR + sub) * V) = pack16<T>(&o[j * V]);
+      }
+    }
+    // cross-wave reduction of this chunk's dS, one prototype at a time, through the LDS rows of the chunk itself
+    __syncthreads();
+    float* red = Sl + (size_t)pass * KCH * C;   // [4][C]
+#pragma unroll
+    for (int k = 0; k < KCH; ++k) {
+      if (pass * KCH + k < Kt) {                // block-uniform
+#pragma unroll
+        for (int e = 0; e < CL; ++e) {
+          const float t = across_groups<LPR>(acc[k][e]);
+          if (grp == 0) red[wave * C + ((e / V) * LPR + sub) * V + (e % V)] = t;
+        }
+        __syncthreads();
+        for (int c = threadIdx.x; c < C; c += 256)
+          dSpart[((size_t)blockIdx.x * Kt + pass * KCH + k) * C + c] = red[c] + red[C + c] + red[2 * C + c] + red[3 * C + c];
+        __syncthreads();
+      }
     }
   }
 }
@@ -569,12 +754,25 @@ __global__ __launch_bounds__(256) void pop_proto_bwd_kernel(const float* __restr
 
 extern "C" int sl_pop_decompose_fwd(int dtype, const void* feats, const float* S, int Kt, float* proj, void* bg, long long R,
                                     int C, sl_stream_t stream) {
-  SL_REQUIRE(feats && S && proj && bg && R > 0 && Kt >= 1 && Kt <= KMAXP, "pop_decompose_fwd: bad args");
+  SL_REQUIRE(feats && S && proj && bg && R > 0 && Kt >= 1, "pop_decompose_fwd: bad args");
+  SL_REQUIRE(Kt <= KMAXP, "pop_decompose_fwd: %d prototypes; this build holds at most %d", Kt, KMAXP);
   hipStream_t st = (hipStream_t)stream;
   // 16 rows per block (four per wave) until 2048 blocks: every block first brings the prototypes (up to 32 KB) into the LDS and its registers, which four rows per block
   // (2048 blocks for the fine-tune pair's 8 192 rows: 60 us) do not repay; from 32 768 rows on the cap binds and nothing changes
   const int blocks = row_blocks(R * 4, 2048);
-  const size_t lds = (size_t)KMAXP * C * sizeof(float);
+  if (Kt > KCH) {          // wide head: chunked kernel, every prototype row resident (64 KiB at 512 channels: exactly the default allowance, the opt-in is a formality)
+    const size_t wlds = (size_t)KMAXP * C * sizeof(float);
+    if (int e = pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) {
+          using T = decltype(t);
+          auto kern = pop_decompose_fwd_wide_kernel<T, decltype(nv)::value, decltype(lpr)::value>;
+          static bool opted = false;        // per instantiation
+          if (!opted) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds); opted = true; }
+          hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), wlds, st, (const T*)feats, S, Kt, proj, (T*)bg, R, C);
+          return 0; })) return e;
+    SL_LAUNCH_CHECK("pop_decompose_fwd_wide_kernel");
+    return 0;
+  }
+  const size_t lds = (size_t)KCH * C * sizeof(float);
   if (int e = pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) {
         using T = decltype(t);
         if (Kt <= 8) hipLaunchKernelGGL((pop_decompose_fwd_kernel<T, decltype(nv)::value, decltype(lpr)::value, 8>), dim3(blocks), dim3(256), lds, st, (const T*)feats, S, Kt, proj, (T*)bg, R, C);
@@ -712,7 +910,8 @@ extern "C" int sl_f64_split(const double* totals, int n, float* hi_lo, sl_stream
 
 extern "C" int sl_pop_combine_fwd(const float* proj, const float* z_bg, const float* a, const float* b, int Kt, float* preds,
                                   int B, int N, sl_stream_t stream) {
-  SL_REQUIRE(proj && z_bg && a && b && preds && Kt >= 1 && Kt <= KMAXP && B > 0 && N > 0, "pop_combine_fwd: bad args");
+  SL_REQUIRE(proj && z_bg && a && b && preds && Kt >= 1 && B > 0 && N > 0, "pop_combine_fwd: bad args");
+  SL_REQUIRE(Kt <= KMAXP, "pop_combine_fwd: %d prototypes; this build holds at most %d", Kt, KMAXP);
   const long long R = (long long)B * N;
   const int blocks = (int)((R + 255) / 256 < 4096 ? (R + 255) / 256 : 4096);
   hipLaunchKernelGGL(pop_combine_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, proj, z_bg, a, b, Kt, preds, B, N);
@@ -724,11 +923,13 @@ extern "C" int sl_pop_combine_bwd_rows(int B, int N) { return row_blocks((long l
 
 extern "C" int sl_pop_combine_bwd(const float* dpreds, const float* proj, const float* a, const float* b, int Kt, float* dz_bg,
                                   float* dproj, float* dab_partial, int B, int N, sl_stream_t stream) {
-  SL_REQUIRE(dpreds && proj && a && b && dz_bg && dproj && dab_partial && Kt >= 1 && Kt <= KMAXP, "pop_combine_bwd: bad args");
+  SL_REQUIRE(dpreds && proj && a && b && dz_bg && dproj && dab_partial && Kt >= 1, "pop_combine_bwd: bad args");
+  SL_REQUIRE(Kt <= KMAXP, "pop_combine_bwd: %d prototypes; this build holds at most %d", Kt, KMAXP);
   const long long R = (long long)B * N;
   const int nblk = sl_pop_combine_bwd_rows(B, N);
   const long long rpb = (R + nblk - 1) / nblk;
-  hipLaunchKernelGGL(pop_combine_bwd_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, dpreds, proj, a, b, Kt, dz_bg, dproj, dab_partial, B, N, rpb);
+  if (Kt <= KCH) hipLaunchKernelGGL(pop_combine_bwd_kernel<KCH>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, dpreds, proj, a, b, Kt, dz_bg, dproj, dab_partial, B, N, rpb);
+  else hipLaunchKernelGGL(pop_combine_bwd_kernel<KMAXP>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, dpreds, proj, a, b, Kt, dz_bg, dproj, dab_partial, B, N, rpb);
   SL_LAUNCH_CHECK("pop_combine_bwd_kernel");
   return 0;
 }
@@ -743,10 +944,23 @@ extern "C" int sl_pop_decompose_bwd_rows(long long R) { return dec_bwd_blocks(R)
 extern "C" int sl_pop_decompose_bwd(int dtype, const void* dg, const void* feats, const float* S, const float* proj,
                                     const float* dproj, int Kt, void* dq, float* dS_partial, long long R, int C,
                                     sl_stream_t stream) {
-  SL_REQUIRE(dg && feats && S && proj && dproj && dq && dS_partial && R > 0 && Kt >= 1 && Kt <= KMAXP, "pop_decompose_bwd: bad args");
+  SL_REQUIRE(dg && feats && S && proj && dproj && dq && dS_partial && R > 0 && Kt >= 1, "pop_decompose_bwd: bad args");
+  SL_REQUIRE(Kt <= KMAXP, "pop_decompose_bwd: %d prototypes; this build holds at most %d", Kt, KMAXP);
   hipStream_t st = (hipStream_t)stream;
   const int nblk = dec_bwd_blocks(R);
   const long long rpb = (R + nblk - 1) / nblk;
+  if (Kt > KCH) {          // wide head: one pass over the block's rows per chunk of KCH prototypes
+    const size_t lds = (size_t)KMAXP * C * sizeof(float);
+    if (int e = pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) {
+          using T = decltype(t);
+          auto kern = pop_decompose_bwd_wide_kernel<T, decltype(nv)::value, decltype(lpr)::value>;
+          static bool opted = false;        // per instantiation
+          if (!opted) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); opted = true; }
+          hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, (const T*)dg, (const T*)feats, S, proj, dproj, Kt, (T*)dq, dS_partial, R, C, rpb);
+          return 0; })) return e;
+    SL_LAUNCH_CHECK("pop_decompose_bwd_wide_kernel");
+    return 0;
+  }
   if (Kt <= 8) {
     const size_t lds = 8 * (size_t)C * sizeof(float);
     if (int e = pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) {

@@ -7,6 +7,9 @@ eval).  All arithmetic runs in libsegland_hip.so (segland_amd.functional); there
 Extra (keyword-only) knob: compute_dtype = torch.bfloat16 (default, MFMA bf16 with fp32 accumulate) or torch.float32
 (exact-fp32 MFMA; the parity mode).  BatchNorm statistics are always per-GPU (nn.SyncBatchNorm modules passed as
 norm_layer are accepted as parameter holders; see DESIGN.md, multi-GPU).
+
+The head, loss and label kernels hold n_base + n_novel <= 32 prototypes (33 logit channels with background); a larger model raises
+RuntimeError in its first forward, with the limit in the message.
 """
 import torch
 import torch.nn as nn

@@ -902,6 +902,7 @@ def ppm_fact_scatter(dcb, x_shape, sizes):
 
 # --------------------------------------------------------------------------------------------- POP head
 def pop_decompose_into(feats2d, S, bg_out):
+    """proj [R, Kt] = feats2d @ S^T, bg_out = feats2d - proj @ S.  S: float [Kt, C] unit rows, 1 <= Kt <= 32 (more raises RuntimeError naming the limit), C 128 / 256 / 512."""
     R, Cn = feats2d.shape
     Kt = S.shape[0]
     proj = _f32((R, Kt), feats2d.device)
@@ -982,6 +983,7 @@ def rowdot_bwd(h, w, dz):
 
 
 def pop_combine_fwd(proj, z_bg, a, b, B, N):
+    """preds [B, 1 + Kt, N] from the projections, the background logit and the per-prototype MLP values a, b; Kt <= 32."""
     Kt = proj.shape[1]
     preds = _f32((B, 1 + Kt, N), proj.device)
     check(_lib.lib().sl_pop_combine_fwd(_p(proj), _p(z_bg), _p(a), _p(b), Kt, _p(preds), B, N, _s()), 'pop_combine_fwd')
@@ -989,6 +991,7 @@ def pop_combine_fwd(proj, z_bg, a, b, B, N):
 
 
 def pop_combine_bwd(dpreds, proj, a, b, B, N):
+    """(dz_bg [B*N], dproj [B*N, Kt], da [Kt], db [Kt]); Kt <= 32.  The partial buffer is [blocks, 2 Kt]: its size follows Kt."""
     Kt = proj.shape[1]
     L = _lib.lib()
     nblk = L.sl_pop_combine_bwd_rows(B, N)
@@ -1001,6 +1004,7 @@ def pop_combine_bwd(dpreds, proj, a, b, B, N):
 
 
 def pop_decompose_bwd(dg, feats2d, S, proj, dproj):
+    """(dq like feats2d, dS [Kt, C]); Kt <= 32.  The partial buffer is [blocks, Kt, C] whichever kernel runs (one pass over the rows up to 16 prototypes, two above)."""
     R, Cn = feats2d.shape
     Kt = S.shape[0]
     L = _lib.lib()
@@ -1015,6 +1019,8 @@ def pop_decompose_bwd(dg, feats2d, S, proj, dproj):
 
 # --------------------------------------------------------------------------------------------- loss & labels
 def upsample_ce_fwd(logits, target, ignore_index):
+    """float [2] = (mean cross-entropy of the upsampled logits over the valid pixels, number of valid pixels).  logits float [B, K, h, w], K <= 33 (more raises
+    RuntimeError naming the limit); the same limit holds for upsample_ce_bwd, pseudo_label_, upsample_argmax and upsample_logits."""
     B, K, h, w = logits.shape
     H, W = target.shape[1:]
     L = _lib.lib()
@@ -1039,7 +1045,7 @@ def upsample_ce_bwd(logits, target, loss_cnt, gscale, ignore_index):
 
 
 def pseudo_label_(logits, mask, n_base):
-    """In place on `mask` (int64 [B,H,W]); logits [B,K2,h,w] float."""
+    """In place on `mask` (int64 [B,H,W]); logits [B,K2,h,w] float, K2 <= 33."""
     B, K2, h, w = logits.shape
     check(_lib.lib().sl_pseudo_label(_p(logits), K2, h, w, _p(mask), B, mask.shape[1], mask.shape[2], n_base, _s()), 'pseudo_label')
     return mask

@@ -4,14 +4,23 @@ function instruction by instruction (mnemonics, operands and branch labels).  A 
 
     python tools/device_code_diff.py parent/conv_wgrad.o segland_amd/csrc/conv_wgrad.o"""
 import os
+import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import loop_density  # noqa: E402
 
 
+def local_labels(items):
+    """Branch labels renumbered per function in order of appearance: the assembler numbers them through the whole object, so a function added in front of an untouched
+    one would otherwise make it 'differ'."""
+    seen = {}
+    sub = lambda m: seen.setdefault(m.group(0), 'L#%d' % len(seen))
+    return [tuple(re.sub(r'\bL\d+\b', sub, x) if isinstance(x, str) else x for x in it) for it in items]
+
+
 def main():
-    a, b = loop_density.kernels(sys.argv[1]), loop_density.kernels(sys.argv[2])
+    a, b = ({k: local_labels(v) for k, v in loop_density.kernels(p).items()} for p in sys.argv[1:3])
     nice = loop_density.demangle(sorted(set(a) | set(b)))
     bad = 0
     for sym in sorted(set(a) | set(b)):
