@@ -74,14 +74,13 @@ class _PrepPlan:
     def refresh(self, convs, dtypes):
         import struct
         ws = [c.weight for c in convs]
-        stale = [w for w, d in zip(ws, dtypes) if (getattr(w, '_sl_prep', None) is None or w._sl_prep[0] != _wver(w)
-                                                    or w._sl_prep[1] != d or w._sl_prep[2] != w.data_ptr())]
+        stale = [(w, d) for w, d in zip(ws, dtypes) if (getattr(w, '_sl_prep', None) is None or w._sl_prep[0] != _wver(w)
+                                                         or w._sl_prep[1] != d or w._sl_prep[2] != w.data_ptr())]
         if not stale:
             return
         if len(stale) * 4 < len(ws) and self.key is not None:   # a few trainable weights over a frozen backbone (ft_pop): per-conv launches
-            for w, d in zip(ws, dtypes):
-                if w._sl_prep[0] != _wver(w) or w._sl_prep[1] != d or w._sl_prep[2] != w.data_ptr():
-                    prepared(w, d)
+            for w, d in stale:
+                prepared(w, d)
             return
         key = tuple((w.data_ptr(), d) for w, d in zip(ws, dtypes))
         if key != self.key:                                   # (re)build buffers + the device table
