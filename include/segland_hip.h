@@ -430,6 +430,17 @@ int sl_upsample_ce_finalize(const float* partial, int nblk, float* loss_and_coun
 /* dlogits[b][k][i][j] = gscale/nvalid * sum over pixels of weight * (softmax - onehot); loss_and_count from fwd */
 int sl_upsample_ce_bwd(const float* logits, const int64_t* target, const float* loss_and_count, const float* gscale,
                        int B, int K, int h, int w, int H, int W, int ignore_index, float* dlogits, sl_stream_t stream);
+/* loss/criterion.py:33,51-52 with nn.CrossEntropyLoss(weight=class_weight, label_smoothing=eps, ignore_index, mean), torch's semantics: for a valid pixel of label t
+ * c_k = (1-eps) w_t [k==t] + (eps/K) w_k;  partial[blk][2] = (sum of -sum_k c_k logp_k, sum of w_t), so sl_upsample_ce_finalize gives (loss, weight sum of the valid
+ * pixels).  class_weight: K floats on the device, read by the kernels (a captured step follows an in-place update).  1 <= K <= 33, class_weight != NULL and
+ * 0 <= label_smoothing <= 1, else SL_EINVAL before any launch.  The plain pair above launches its own kernels, not these with weights of one. */
+int sl_upsample_ce_weighted_fwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing,
+                                int B, int K, int h, int w, int H, int W, int ignore_index, float* partial, sl_stream_t stream);
+/* loss/criterion.py:33,51-52: dlogits = gscale / loss_and_count[1] * sum over pixels of bilinear weight * (softmax_k C_t - c_k),
+ * C_t = (1-eps) w_t + (eps/K) sum_j w_j;  loss_and_count from the weighted forward.  Same kernel routes (and sl_debug_ce_tiled hook) as sl_upsample_ce_bwd. */
+int sl_upsample_ce_weighted_bwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing,
+                                const float* loss_and_count, const float* gscale, int B, int K, int h, int w, int H, int W,
+                                int ignore_index, float* dlogits, sl_stream_t stream);
 /* pspnet_pop.py:221-231: argmax of the upsampled (align_corners=True) [K2][h][w] logits of tile b, ids > 0 shifted
  * by n_base, written into mask[b] where mask == 0 (in place, int64). */
 int sl_pseudo_label(const float* logits, int K2, int h, int w, int64_t* mask, int B, int H, int W, int n_base,

@@ -11,6 +11,13 @@ constexpr int KNC = 16;    // up to KNC channels run on the <KNC> instantiations
 
 struct UpGeom { int B, K, h, w, H, W; float sy, sx; };
 
+// Class weights and label smoothing of the weighted forms (nn.CrossEntropyLoss(weight, label_smoothing); loss/criterion.py:33,51-52).  For a valid pixel of label t
+//   c_k = (1 - eps) w_t [k == t] + (eps / K) w_k,   numerator = -sum_k c_k logp_k,   denominator = w_t,
+//   d numerator / d v_k = softmax_k C_t - c_k   with   C_t = (1 - eps) w_t + (eps / K) sum_j w_j   (sum_j in index order, inside the kernel).
+// The plain kernels are the <WT = false> instantiations: CeW<false> is empty and every statement of the weighted form sits under `if constexpr (WT)`.
+template <bool WT> struct CeW {};
+template <> struct CeW<true> { const float* w; float keep, epsk; };   // w[K] on the device, keep = 1 - eps, epsk = eps / K
+
 __host__ inline float ac1_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 
 // ATen upsample_bilinear2d source index, align_corners = True
@@ -39,9 +46,10 @@ __device__ __forceinline__ void pixel_logits(const UpGeom& g, const float* __res
   }
 }
 
-template <int KW>
+// part[blk] = (sum of pixel losses, number of valid pixels); WT: (sum of the pixel numerators, sum of w_t)
+template <int KW, bool WT>
 __global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(UpGeom g, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
-                                                              int ignore, float* __restrict__ part) {
+                                                              int ignore, float* __restrict__ part, CeW<WT> cw) {
   __shared__ float red[2][4];
   const long long total = (long long)g.B * g.H * g.W;
   float loss = 0.f, cnt = 0.f;
@@ -58,8 +66,17 @@ __global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(UpGeom g, const fl
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < KW; ++k) if (k < g.K) s += expf(v[k] - m);
-    loss += logf(s) + m - vt;
-    cnt += 1.f;
+    if constexpr (WT) {
+      const float lse = logf(s) + m, wt = cw.w[t];
+      float sm = 0.f;                                   // sum_k w_k (-logp_k), in index order
+#pragma unroll
+      for (int k = 0; k < KW; ++k) if (k < g.K) sm += cw.w[k] * (lse - v[k]);
+      loss += cw.keep * wt * (lse - vt) + cw.epsk * sm;
+      cnt += wt;
+    } else {
+      loss += logf(s) + m - vt;
+      cnt += 1.f;
+    }
   }
   loss = wave_sum(loss); cnt = wave_sum(cnt);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -86,10 +103,10 @@ __global__ void upsample_ce_finalize_kernel(const float* __restrict__ part, int 
 
 // four lanes per low-resolution cell (each takes every 4th footprint row), gather over the pixels whose bilinear
 // footprint touches the cell, then a 4-lane shuffle reduction: deterministic, no atomics.
-template <int KW>
+template <int KW, bool WT>
 __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
                                                               const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
-                                                              int ignore, float* __restrict__ dlg) {
+                                                              int ignore, float* __restrict__ dlg, CeW<WT> cw) {
   const long long cells = (long long)g.B * g.h * g.w;
   const long long ci = (blockIdx.x * 256LL + threadIdx.x) >> 2;
   const int sub = threadIdx.x & 3;
@@ -104,6 +121,11 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
   const int Yhi = g.sy > 0.f ? min(g.H - 1, (int)ceilf((float)(i + 1) / g.sy)) : g.H - 1;
   const int Xlo = g.sx > 0.f ? max(0, (int)floorf((float)(j - 1) / g.sx)) : 0;
   const int Xhi = g.sx > 0.f ? min(g.W - 1, (int)ceilf((float)(j + 1) / g.sx)) : g.W - 1;
+  float wsum = 0.f;
+  if constexpr (WT) {
+#pragma unroll
+    for (int k = 0; k < KW; ++k) if (k < g.K) wsum += cw.w[k];
+  }
   if (live) {
     for (int Y = Ylo + sub; Y <= Yhi; Y += 4) {
       int y0, y1; float ly;
@@ -126,8 +148,14 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
 #pragma unroll
         for (int k = 0; k < KW; ++k) { v[k] = k < g.K ? expf(v[k] - m) : 0.f; s += v[k]; }
         const float wgt = wy * wx, inv = 1.f / s;
+        if constexpr (WT) {
+          const float hit = cw.keep * cw.w[t], ct = hit + cw.epsk * wsum;
 #pragma unroll
-        for (int k = 0; k < KW; ++k) acc[k] += wgt * (v[k] * inv - (k == (int)t ? 1.f : 0.f));
+          for (int k = 0; k < KW; ++k) if (k < g.K) acc[k] += wgt * (v[k] * inv * ct - ((k == (int)t ? hit : 0.f) + cw.epsk * cw.w[k]));
+        } else {
+#pragma unroll
+          for (int k = 0; k < KW; ++k) acc[k] += wgt * (v[k] * inv - (k == (int)t ? 1.f : 0.f));
+        }
       }
     }
   }
@@ -147,10 +175,10 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
 // Sums run in a fixed order (deterministic); they are associated differently from the gather kernel (last-bit differences).
 constexpr int CT = 4;
 struct UpTile { int NYmax, NXmax; };
-template <int NT>
+template <int NT, bool WT>
 __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpTile ut, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
                                                                     const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
-                                                                    int ignore, float* __restrict__ dlg) {
+                                                                    int ignore, float* __restrict__ dlg, CeW<WT> cw) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int KW = KNC;                            // this kernel serves K <= KNC (G holds all K channels of every footprint pixel)
   const int K = g.K;
@@ -161,6 +189,8 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
   float* wyi = wxj + CT * ut.NXmax;                  // [NY][CT]
   float* H1 = wyi + CT * ut.NYmax;                   // [NY][CT][K]
   float* G = H1 + ut.NYmax * CT * K;                 // [NY][NX][K]
+  float* wl = nullptr;                               // WT: [K] class weights behind G (the host adds K floats to the launch's LDS)
+  if constexpr (WT) wl = G + (size_t)ut.NYmax * ut.NXmax * K;
   const int tid = threadIdx.x;
   const int tw = cdiv(g.w, CT), th = cdiv(g.h, CT);
   int blk = blockIdx.x;
@@ -179,6 +209,7 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
     const int yy = min(max(i0 - 1 + cy, 0), g.h - 1), xx = min(max(j0 - 1 + cx, 0), g.w - 1);
     lgt[e] = lb[((size_t)k * g.h + yy) * g.w + xx];
   }
+  if constexpr (WT) for (int e = tid; e < K; e += NT) wl[e] = cw.w[e];
   for (int e = tid; e < NY; e += NT) {
     int y0, y1; float ly; src_index_ac1(Ylo + e, g.h, g.sy, y0, y1, ly);
     wy0[3 * e] = __int_as_float(y0); wy0[3 * e + 1] = __int_as_float(y1); wy0[3 * e + 2] = ly;
@@ -202,6 +233,8 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
     const int yr = pix / NX, xr = pix - yr * NX;
     tpre[u] = pix < NY * NX ? tgt[((size_t)b * g.H + Ylo + yr) * g.W + Xlo + xr] : (long long)ignore;
   }
+  float wsum = 0.f;
+  if constexpr (WT) for (int k = 0; k < K; ++k) wsum += wl[k];
 #pragma unroll 1
   for (int u = 0; tid + NT * u < NY * NX; ++u) {
     const int pix = tid + NT * u;
@@ -239,8 +272,14 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
 #pragma unroll
     for (int k = 0; k < KW; ++k) { v[k] = k < K ? __expf(v[k] - m) : 0.f; ssum += v[k]; }      // hardware exp2-based: 2 ulp, the gradient's tolerance is 1e-3
     const float inv = 1.f / ssum;
+    if constexpr (WT) {
+      const float hit = cw.keep * wl[t], ct = hit + cw.epsk * wsum;
 #pragma unroll
-    for (int k = 0; k < KW; ++k) if (k < K) out[k] = v[k] * inv - (k == (int)t ? 1.f : 0.f);
+      for (int k = 0; k < KW; ++k) if (k < K) out[k] = v[k] * inv * ct - ((k == (int)t ? hit : 0.f) + cw.epsk * wl[k]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < KW; ++k) if (k < K) out[k] = v[k] * inv - (k == (int)t ? 1.f : 0.f);
+    }
   }
   __syncthreads();
   // ---- pass 2a: along X
@@ -292,10 +331,10 @@ __device__ __forceinline__ UpTap up_tap(const float* lgt, const float* wy0, cons
   t.q10 = lgt + (ry1 * (CT + 2) + rx0) * K; t.q11 = lgt + (ry1 * (CT + 2) + rx1) * K;
   return t;
 }
-template <int NT>
+template <int NT, bool WT>
 __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g, UpTileW ut, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
                                                                          const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
-                                                                         int ignore, float* __restrict__ dlg) {
+                                                                         int ignore, float* __restrict__ dlg, CeW<WT> cw) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int K = g.K, KS = ut.KS;
   float* lgt = sm;                                   // [(CT+2)^2][K]
@@ -306,6 +345,8 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
   float* st = wyi + CT * ut.NYmax;                   // [NY][NX][3]: max, 1 / sum, label as int (-1: the pixel does not count)
   float* H1 = st + 3 * ut.NYmax * ut.NXmax;          // [NY][CT][KS]
   float* G = H1 + ut.NYmax * CT * KS;                // [NY][NX][KS]
+  float* wl = nullptr;                               // WT: [K] class weights behind G (the host adds K floats to the launch's LDS)
+  if constexpr (WT) wl = G + (size_t)ut.NYmax * ut.NXmax * KS;
   const int tid = threadIdx.x;
   const int tw = cdiv(g.w, CT), th = cdiv(g.h, CT);
   int blk = blockIdx.x;
@@ -324,6 +365,7 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
     const int yy = min(max(i0 - 1 + cy, 0), g.h - 1), xx = min(max(j0 - 1 + cx, 0), g.w - 1);
     lgt[e] = lb[((size_t)k * g.h + yy) * g.w + xx];
   }
+  if constexpr (WT) for (int e = tid; e < K; e += NT) wl[e] = cw.w[e];
   for (int e = tid; e < NY; e += NT) {
     int y0, y1; float ly; src_index_ac1(Ylo + e, g.h, g.sy, y0, y1, ly);
     wy0[3 * e] = __int_as_float(y0); wy0[3 * e + 1] = __int_as_float(y1); wy0[3 * e + 2] = ly;
@@ -352,6 +394,8 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
   }
   __syncthreads();
   const float f = gscale[0] / loss_cnt[1];
+  float wsum = 0.f;
+  if constexpr (WT) for (int k = 0; k < K; ++k) wsum += wl[k];
   for (int k0 = 0; k0 < K; k0 += KS) {
     const int kn = min(KS, K - k0);
     // ---- pass 1: softmax - onehot of the slice's channels
@@ -366,7 +410,12 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
       }
       const UpTap tap = up_tap(lgt, wy0, wx0, yr, xr, i0, j0, K);
       const float m = s[0], inv = s[1];
-      for (int kk = 0; kk < kn; ++kk) out[kk] = __expf(tap.at(k0 + kk) - m) * inv - (k0 + kk == t ? 1.f : 0.f);
+      if constexpr (WT) {
+        const float hit = cw.keep * wl[t], ct = hit + cw.epsk * wsum;
+        for (int kk = 0; kk < kn; ++kk) out[kk] = __expf(tap.at(k0 + kk) - m) * inv * ct - ((k0 + kk == t ? hit : 0.f) + cw.epsk * wl[k0 + kk]);
+      } else {
+        for (int kk = 0; kk < kn; ++kk) out[kk] = __expf(tap.at(k0 + kk) - m) * inv - (k0 + kk == t ? 1.f : 0.f);
+      }
     }
     __syncthreads();
     // ---- pass 2a: along X
@@ -526,6 +575,66 @@ inline UpGeom make_up(int B, int K, int h, int w, int H, int W) {
 }
 inline int ce_blocks(long long total) { long long b = (total + 255) / 256; return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); }
 
+// One launch plan for the plain (WT = false) and the weighted (WT = true) forms: which kernel runs depends on K, the scale and the hook only.
+template <bool WT>
+int launch_ce_fwd(const UpGeom& g, const float* logits, const int64_t* target, int ignore_index, float* partial, hipStream_t stream, CeW<WT> cw) {
+  const int nblk = ce_blocks((long long)g.B * g.H * g.W);
+  if (g.K <= KNC) hipLaunchKernelGGL((upsample_ce_fwd_kernel<KNC, WT>), dim3(nblk), dim3(256), 0, stream, g, logits, target, ignore_index, partial, cw);
+  else hipLaunchKernelGGL((upsample_ce_fwd_kernel<KMAXC, WT>), dim3(nblk), dim3(256), 0, stream, g, logits, target, ignore_index, partial, cw);
+  SL_LAUNCH_CHECK("upsample_ce_fwd_kernel");
+  return 0;
+}
+
+template <bool WT>
+int launch_ce_bwd(const UpGeom& g, const float* logits, const int64_t* target, const float* loss_and_count, const float* gscale, int ignore_index, float* dlogits,
+                  hipStream_t stream, CeW<WT> cw) {
+  const int B = g.B, K = g.K, h = g.h, w = g.w, H = g.H, W = g.W;
+  const long long cells = (long long)B * h * w;
+  const size_t wl = WT ? (size_t)K : 0;              // the weighted kernels keep the K class weights behind G
+  // tiled kernel when the joint footprint of a CT x CT cell tile fits the LDS (always for an upsampling factor <= ~12 at K <= 16); test hook sl_debug_ce_tiled(0): never
+  if (g.sy > 0.f && g.sx > 0.f && g_sl_debug.ce_tiled && K > KNC) {
+    // channel-sliced form: the fewest slices (of at most KNC channels) whose G and H1 fit next to the per-pixel statistics
+    UpTileW ut;
+    ut.NYmax = (int)ceilf((float)(CT + 1) / g.sy) + 3; if (ut.NYmax > H) ut.NYmax = H;
+    ut.NXmax = (int)ceilf((float)(CT + 1) / g.sx) + 3; if (ut.NXmax > W) ut.NXmax = W;
+    const size_t fixed = (size_t)(CT + 2) * (CT + 2) * K + (3 + CT) * (ut.NYmax + ut.NXmax) + 3 * (size_t)ut.NYmax * ut.NXmax + wl;
+    for (int ns = cdiv(K, KNC); ns <= K; ++ns) {
+      ut.KS = cdiv(K, ns);
+      const size_t lds = (fixed + (size_t)ut.NYmax * CT * ut.KS + (size_t)ut.NYmax * ut.NXmax * ut.KS) * sizeof(float);
+      if (lds > 150 * 1024) continue;
+      static bool opted = false;
+      if (!opted) { (void)hipFuncSetAttribute((const void*)upsample_ce_bwd_tiled_wide_kernel<512, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); opted = true; }
+      hipLaunchKernelGGL((upsample_ce_bwd_tiled_wide_kernel<512, WT>), dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(512), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw);
+      SL_LAUNCH_CHECK("upsample_ce_bwd_tiled_wide_kernel");
+      return 0;
+    }
+  } else if (g.sy > 0.f && g.sx > 0.f && g_sl_debug.ce_tiled) {
+    UpTile ut;
+    ut.NYmax = (int)ceilf((float)(CT + 1) / g.sy) + 3; if (ut.NYmax > H) ut.NYmax = H;
+    ut.NXmax = (int)ceilf((float)(CT + 1) / g.sx) + 3; if (ut.NXmax > W) ut.NXmax = W;
+    const size_t lds = ((size_t)(CT + 2) * (CT + 2) * K + (3 + CT) * (ut.NYmax + ut.NXmax) + (size_t)ut.NYmax * CT * K + (size_t)ut.NYmax * ut.NXmax * K + wl) * sizeof(float);
+    if (lds <= 150 * 1024) {
+      static size_t attr = 0;
+#ifndef SL_UPCE_NT
+#define SL_UPCE_NT 512      // threads per block of the tiled kernel (A/B build: 256)
+#endif
+      if (lds > attr) { (void)hipFuncSetAttribute((const void*)upsample_ce_bwd_tiled_kernel<SL_UPCE_NT, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); attr = 150 * 1024; }
+      hipLaunchKernelGGL((upsample_ce_bwd_tiled_kernel<SL_UPCE_NT, WT>), dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(SL_UPCE_NT), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw);
+      SL_LAUNCH_CHECK("upsample_ce_bwd_tiled_kernel");
+      return 0;
+    }
+  }
+  if (K <= KNC) hipLaunchKernelGGL((upsample_ce_bwd_kernel<KNC, WT>), dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, stream, g, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw);
+  else hipLaunchKernelGGL((upsample_ce_bwd_kernel<KMAXC, WT>), dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, stream, g, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw);
+  SL_LAUNCH_CHECK("upsample_ce_bwd_kernel");
+  return 0;
+}
+
+inline CeW<true> make_cew(const float* class_weight, float label_smoothing, int K) {
+  CeW<true> cw; cw.w = class_weight; cw.keep = 1.f - label_smoothing; cw.epsk = label_smoothing / (float)K;
+  return cw;
+}
+
 }  // namespace
 
 extern "C" int sl_upsample_ce_rows(int B, int H, int W) { return ce_blocks((long long)B * H * W); }
@@ -534,11 +643,17 @@ extern "C" int sl_upsample_ce_fwd(const float* logits, const int64_t* target, in
                                   int ignore_index, float* partial, sl_stream_t stream) {
   SL_REQUIRE(logits && target && partial && B > 0 && K >= 1 && h > 0 && w > 0 && H > 0 && W > 0, "upsample_ce_fwd: bad args");
   SL_REQUIRE(K <= KMAXC, "upsample_ce_fwd: %d logit channels; this build holds at most %d", K, KMAXC);
-  const UpGeom g = make_up(B, K, h, w, H, W);
-  if (K <= KNC) hipLaunchKernelGGL(upsample_ce_fwd_kernel<KNC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, target, ignore_index, partial);
-  else hipLaunchKernelGGL(upsample_ce_fwd_kernel<KMAXC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, target, ignore_index, partial);
-  SL_LAUNCH_CHECK("upsample_ce_fwd_kernel");
-  return 0;
+  return launch_ce_fwd<false>(make_up(B, K, h, w, H, W), logits, target, ignore_index, partial, (hipStream_t)stream, CeW<false>());
+}
+
+// loss/criterion.py:33,51-52 with nn.CrossEntropyLoss(weight=class_weight, label_smoothing): partial[blk] = (sum of pixel numerators, sum of w_t)
+extern "C" int sl_upsample_ce_weighted_fwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing,
+                                           int B, int K, int h, int w, int H, int W, int ignore_index, float* partial, sl_stream_t stream) {
+  SL_REQUIRE(logits && target && partial && B > 0 && h > 0 && w > 0 && H > 0 && W > 0, "upsample_ce_weighted_fwd: bad args");
+  SL_REQUIRE(K >= 1 && K <= KMAXC, "upsample_ce_weighted_fwd: %d logit channels; this build holds at most %d", K, KMAXC);
+  SL_REQUIRE(class_weight, "upsample_ce_weighted_fwd: class_weight is null (K floats on the device)");
+  SL_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, "upsample_ce_weighted_fwd: label_smoothing %g outside [0, 1]", (double)label_smoothing);
+  return launch_ce_fwd<true>(make_up(B, K, h, w, H, W), logits, target, ignore_index, partial, (hipStream_t)stream, make_cew(class_weight, label_smoothing, K));
 }
 
 extern "C" int sl_upsample_ce_finalize(const float* partial, int nblk, float* loss_and_count, sl_stream_t stream) {
@@ -553,45 +668,19 @@ extern "C" int sl_upsample_ce_bwd(const float* logits, const int64_t* target, co
                                   sl_stream_t stream) {
   SL_REQUIRE(logits && target && loss_and_count && gscale && dlogits && K >= 1, "upsample_ce_bwd: bad args");
   SL_REQUIRE(K <= KMAXC, "upsample_ce_bwd: %d logit channels; this build holds at most %d", K, KMAXC);
-  const UpGeom g = make_up(B, K, h, w, H, W);
-  const long long cells = (long long)B * h * w;
-  // tiled kernel when the joint footprint of a CT x CT cell tile fits the LDS (always for an upsampling factor <= ~12 at K <= 16); test hook sl_debug_ce_tiled(0): never
-  if (g.sy > 0.f && g.sx > 0.f && g_sl_debug.ce_tiled && K > KNC) {
-    // channel-sliced form: the fewest slices (of at most KNC channels) whose G and H1 fit next to the per-pixel statistics
-    UpTileW ut;
-    ut.NYmax = (int)ceilf((float)(CT + 1) / g.sy) + 3; if (ut.NYmax > H) ut.NYmax = H;
-    ut.NXmax = (int)ceilf((float)(CT + 1) / g.sx) + 3; if (ut.NXmax > W) ut.NXmax = W;
-    const size_t fixed = (size_t)(CT + 2) * (CT + 2) * K + (3 + CT) * (ut.NYmax + ut.NXmax) + 3 * (size_t)ut.NYmax * ut.NXmax;
-    for (int ns = cdiv(K, KNC); ns <= K; ++ns) {
-      ut.KS = cdiv(K, ns);
-      const size_t lds = (fixed + (size_t)ut.NYmax * CT * ut.KS + (size_t)ut.NYmax * ut.NXmax * ut.KS) * sizeof(float);
-      if (lds > 150 * 1024) continue;
-      static bool opted = false;
-      if (!opted) { (void)hipFuncSetAttribute((const void*)upsample_ce_bwd_tiled_wide_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); opted = true; }
-      hipLaunchKernelGGL(upsample_ce_bwd_tiled_wide_kernel<512>, dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(512), lds, (hipStream_t)stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits);
-      SL_LAUNCH_CHECK("upsample_ce_bwd_tiled_wide_kernel");
-      return 0;
-    }
-  } else if (g.sy > 0.f && g.sx > 0.f && g_sl_debug.ce_tiled) {
-    UpTile ut;
-    ut.NYmax = (int)ceilf((float)(CT + 1) / g.sy) + 3; if (ut.NYmax > H) ut.NYmax = H;
-    ut.NXmax = (int)ceilf((float)(CT + 1) / g.sx) + 3; if (ut.NXmax > W) ut.NXmax = W;
-    const size_t lds = ((size_t)(CT + 2) * (CT + 2) * K + (3 + CT) * (ut.NYmax + ut.NXmax) + (size_t)ut.NYmax * CT * K + (size_t)ut.NYmax * ut.NXmax * K) * sizeof(float);
-    if (lds <= 150 * 1024) {
-      static size_t attr = 0;
-#ifndef SL_UPCE_NT
-#define SL_UPCE_NT 512      // threads per block of the tiled kernel (A/B build: 256)
-#endif
-      if (lds > attr) { (void)hipFuncSetAttribute((const void*)upsample_ce_bwd_tiled_kernel<SL_UPCE_NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); attr = 150 * 1024; }
-      hipLaunchKernelGGL(upsample_ce_bwd_tiled_kernel<SL_UPCE_NT>, dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(SL_UPCE_NT), lds, (hipStream_t)stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits);
-      SL_LAUNCH_CHECK("upsample_ce_bwd_tiled_kernel");
-      return 0;
-    }
-  }
-  if (K <= KNC) hipLaunchKernelGGL(upsample_ce_bwd_kernel<KNC>, dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, logits, target, loss_and_count, gscale, ignore_index, dlogits);
-  else hipLaunchKernelGGL(upsample_ce_bwd_kernel<KMAXC>, dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, logits, target, loss_and_count, gscale, ignore_index, dlogits);
-  SL_LAUNCH_CHECK("upsample_ce_bwd_kernel");
-  return 0;
+  return launch_ce_bwd<false>(make_up(B, K, h, w, H, W), logits, target, loss_and_count, gscale, ignore_index, dlogits, (hipStream_t)stream, CeW<false>());
+}
+
+// loss/criterion.py:33,51-52, gradient of the weighted form: loss_and_count[1] is the weight sum of the valid pixels (from the weighted forward + finalize)
+extern "C" int sl_upsample_ce_weighted_bwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing,
+                                           const float* loss_and_count, const float* gscale, int B, int K, int h, int w, int H, int W,
+                                           int ignore_index, float* dlogits, sl_stream_t stream) {
+  SL_REQUIRE(logits && target && loss_and_count && gscale && dlogits && B > 0 && h > 0 && w > 0 && H > 0 && W > 0, "upsample_ce_weighted_bwd: bad args");
+  SL_REQUIRE(K >= 1 && K <= KMAXC, "upsample_ce_weighted_bwd: %d logit channels; this build holds at most %d", K, KMAXC);
+  SL_REQUIRE(class_weight, "upsample_ce_weighted_bwd: class_weight is null (K floats on the device)");
+  SL_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, "upsample_ce_weighted_bwd: label_smoothing %g outside [0, 1]", (double)label_smoothing);
+  return launch_ce_bwd<true>(make_up(B, K, h, w, H, W), logits, target, loss_and_count, gscale, ignore_index, dlogits, (hipStream_t)stream,
+                             make_cew(class_weight, label_smoothing, K));
 }
 
 extern "C" int sl_pseudo_label(const float* logits, int K2, int h, int w, int64_t* mask, int B, int H, int W, int n_base,

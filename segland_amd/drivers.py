@@ -18,6 +18,40 @@ def str2bool(v):
     raise argparse.ArgumentTypeError('Boolean value expected.')
 
 
+def class_weights(v):
+    """'' -> () (no weights); '1,0.5,2' -> (1.0, 0.5, 2.0).  One finite, non-negative value per logit channel (the count is checked against the model's channels
+    by OrthLoss, which knows them)."""
+    if isinstance(v, (tuple, list)):
+        return tuple(float(x) for x in v)
+    if not v.strip():
+        return ()
+    try:
+        w = tuple(float(x) for x in v.split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError('comma-separated floats expected, one per logit channel (got %r)' % (v,))
+    if not all(np.isfinite(x) and x >= 0.0 for x in w):
+        raise argparse.ArgumentTypeError('class weights must be finite and non-negative (got %r)' % (v,))
+    return w
+
+
+def label_smoothing(v):
+    try:
+        eps = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError('float expected (got %r)' % (v,))
+    if not 0.0 <= eps <= 1.0:
+        raise argparse.ArgumentTypeError('label smoothing must lie in [0, 1] (got %r)' % (v,))
+    return eps
+
+
+def log_loss_options(args):
+    """One line at start: the two controls of the segmentation criterion (loss.get_loss reads the same fields)."""
+    import logging
+    w = class_weights(getattr(args, 'class_weights', ()) or ())
+    logging.getLogger('Segmentation').info('segmentation loss: class weights %s, label smoothing %g',
+                                           ','.join('%g' % x for x in w) if w else 'none', float(getattr(args, 'label_smoothing', 0.0)))
+
+
 # (flag, kwargs) -- common to both drivers
 _COMMON = [
     ('--dataset', dict(type=str, default='cityscapes', help='Dataset for training')),
@@ -49,6 +83,9 @@ _COMMON = [
                                  'the step as one captured HIP graph (segland_amd/graph_step.py; single-GPU AdamW runs only).')),
     ('--allow-random-init', dict(action='store_true', default=False, help='continue with random weights when --restore-from does not exist '
                                                                            '(the reference fails in torch.load; so does this build without the flag).')),
+    ('--class-weights', dict(type=class_weights, default='', help='comma-separated class weights of the segmentation cross-entropy, one per logit channel '
+                                                                  '(1 + base classes; 1 + base + novel classes when fine-tuning); default: none.')),
+    ('--label-smoothing', dict(type=label_smoothing, default=0.0, help='label smoothing of the segmentation cross-entropy, in [0, 1]; default 0.')),
     ('--fp16', dict(action='store_true', default=False, help='mixed precision: bf16 MFMA with fp32 accumulate on MI355X '
                                                                 '(the reference uses fp16 autocast + GradScaler); default is exact-fp32 MFMA.')),
 ]

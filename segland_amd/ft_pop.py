@@ -12,7 +12,7 @@ import torch.optim as optim
 from . import dataset as dataset_pkg
 from . import networks
 from . import graph_step
-from .drivers import adjust_learning_rate_poly, build_parser, checkpoint_or_none, compute_dtype, ft_batch_to_device, resolve, save_checkpoint, validate
+from .drivers import adjust_learning_rate_poly, build_parser, checkpoint_or_none, compute_dtype, ft_batch_to_device, log_loss_options, resolve, save_checkpoint, validate
 from .engine import Engine
 from .loss import get_loss
 from .utils import pyt_utils as my_utils
@@ -69,6 +69,8 @@ def main(argv=None):
         logger = my_utils.prep_experiment(args) if engine.is_main else None
         input_size = tuple(map(int, args.input_size.split(',')))
         base_size = tuple(map(int, args.base_size.split(',')))
+        if engine.is_main:
+            log_loss_options(args)
         for seed in map(int, args.random_seed.split(',')):
             my_utils.set_seed(seed)
             ds_ft, ds = resolve(dataset_pkg, args.dataset + '_ft'), resolve(dataset_pkg, args.dataset)

@@ -984,19 +984,21 @@ class ProtoFn(torch.autograd.Function):
 
 # ------------------------------------------------------------------------------------------------ loss
 class UpsampleCEFn(torch.autograd.Function):
-    """F.interpolate(align_corners=True) + CrossEntropyLoss(ignore_index, mean) of loss/criterion.py:51-52, fused."""
+    """F.interpolate(align_corners=True) + CrossEntropyLoss(ignore_index, mean) of loss/criterion.py:51-52, fused.  `weight` (float32 [K] on the device, no gradient)
+    and `label_smoothing` are CrossEntropyLoss's own (loss/criterion.py:33); with the defaults the plain kernels run."""
 
     @staticmethod
-    def forward(ctx, logits, target, ignore_index):
+    def forward(ctx, logits, target, ignore_index, weight=None, label_smoothing=0.0):
         logits = logits.contiguous()
-        out = ops.upsample_ce_fwd(logits, target, ignore_index)
+        out = ops.upsample_ce_fwd(logits, target, ignore_index, weight, label_smoothing)
         ctx.ignore = ignore_index
-        ctx.save_for_backward(logits, target, out)
+        ctx.eps = label_smoothing
+        ctx.save_for_backward(logits, target, out, weight)
         return out[0].clone()
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        logits, target, out = ctx.saved_tensors
+        logits, target, out, weight = ctx.saved_tensors
         gs = g.detach().reshape(1).float().contiguous()
-        return ops.upsample_ce_bwd(logits, target, out, gs, ctx.ignore), None, None
+        return ops.upsample_ce_bwd(logits, target, out, gs, ctx.ignore, weight, ctx.eps), None, None, None, None

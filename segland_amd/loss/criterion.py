@@ -15,11 +15,25 @@ class OrthTerm:
 
 
 class OrthLoss(nn.Module):
-    def __init__(self, ignore_index=255, reduction='mean'):
+    """`weight` and `label_smoothing` are those of the nn.CrossEntropyLoss the reference builds its segmentation criterion from (loss/criterion.py:33), with torch's
+    semantics; the main and the auxiliary loss both use them.  `weight` (one value per logit channel; 1 + n_base + n_novel of them in fine-tune mode) is kept as a float32
+    NON-persistent buffer: it follows .to() / .cuda() and adds no key to a state_dict.  The kernels read the buffer itself, so an in-place update
+    (criterion.weight.copy_(...)) reaches a captured training step without a new capture."""
+
+    def __init__(self, ignore_index=255, reduction='mean', weight=None, label_smoothing=0.0):
         super().__init__()
         if reduction != 'mean':
             raise ValueError('segland_amd OrthLoss implements reduction="mean" (what the reference uses)')
+        label_smoothing = float(label_smoothing)
+        if not 0.0 <= label_smoothing <= 1.0:
+            raise ValueError('OrthLoss: label_smoothing %r outside [0, 1]' % (label_smoothing,))
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32).detach().clone().contiguous()
+            if weight.dim() != 1 or weight.numel() == 0:
+                raise ValueError('OrthLoss: weight must be a non-empty vector, one value per logit channel (got shape %s)' % (tuple(weight.shape),))
+        self.register_buffer('weight', weight, persistent=False)
         self.ignore_index = ignore_index
+        self.label_smoothing = label_smoothing
         self.w = 10.0
         self._triu = {}
 
@@ -36,7 +50,9 @@ class OrthLoss(nn.Module):
         return torch.abs(proto_sim[idx[0], idx[1]]).mean()
 
     def seg_loss(self, preds, target):
-        return UpsampleCEFn.apply(preds.float(), target.contiguous(), self.ignore_index)
+        if self.weight is not None and self.weight.numel() != preds.shape[1]:
+            raise ValueError('OrthLoss: %d class weights for %d logit channels' % (self.weight.numel(), preds.shape[1]))
+        return UpsampleCEFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.weight, self.label_smoothing)
 
     def forward(self, preds, target, is_ft=False, proto_sim=None, aux_preds=None):
         seg_loss = self.seg_loss(preds, target)

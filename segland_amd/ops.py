@@ -1018,28 +1018,58 @@ def pop_decompose_bwd(dg, feats2d, S, proj, dproj):
 
 
 # --------------------------------------------------------------------------------------------- loss & labels
-def upsample_ce_fwd(logits, target, ignore_index):
+_CE_ONES = {}
+
+
+def _ce_class_weight(weight, K, device):
+    """The K class weights the weighted kernels read: `weight` itself (float32, on the logits' device, one per channel), or a cached vector of ones when only label
+    smoothing is asked for.  The kernels read this buffer at run time, so an in-place update of `weight` reaches a captured step."""
+    if weight is None:
+        key = (K, str(device))
+        w = _CE_ONES.get(key)
+        if w is None:
+            w = _CE_ONES[key] = torch.ones(K, dtype=torch.float32, device=device)
+        return w
+    if weight.dtype != torch.float32 or weight.device != device or weight.dim() != 1 or not weight.is_contiguous():
+        raise ValueError('upsample_ce: weight must be a contiguous float32 vector on %s (got %s %s on %s)' % (device, weight.dtype, tuple(weight.shape), weight.device))
+    if weight.numel() != K:
+        raise ValueError('upsample_ce: %d class weights for %d logit channels' % (weight.numel(), K))
+    return weight
+
+
+def upsample_ce_fwd(logits, target, ignore_index, weight=None, label_smoothing=0.0):
     """float [2] = (mean cross-entropy of the upsampled logits over the valid pixels, number of valid pixels).  logits float [B, K, h, w], K <= 33 (more raises
-    RuntimeError naming the limit); the same limit holds for upsample_ce_bwd, pseudo_label_, upsample_argmax and upsample_logits."""
+    RuntimeError naming the limit); the same limit holds for upsample_ce_bwd, pseudo_label_, upsample_argmax and upsample_logits.
+    With `weight` (float32 [K] on the device) or `label_smoothing` > 0: torch's CrossEntropyLoss(weight, label_smoothing) on the weighted kernels, and the second
+    element is the weight sum of the valid pixels (what the mean divides by)."""
     B, K, h, w = logits.shape
     H, W = target.shape[1:]
     L = _lib.lib()
     nblk = L.sl_upsample_ce_rows(B, H, W)
     part = _f32((nblk, 2), logits.device)
     tok = PROFILER.begin_bytes('upsample_ce_fwd', logits.numel() * 4 + target.numel() * target.element_size())
-    check(L.sl_upsample_ce_fwd(_p(logits), _p(target), B, K, h, w, H, W, ignore_index, _p(part), _s()), 'upsample_ce_fwd')
+    if weight is None and label_smoothing == 0.0:
+        check(L.sl_upsample_ce_fwd(_p(logits), _p(target), B, K, h, w, H, W, ignore_index, _p(part), _s()), 'upsample_ce_fwd')
+    else:
+        cw = _ce_class_weight(weight, K, logits.device)
+        check(L.sl_upsample_ce_weighted_fwd(_p(logits), _p(target), _p(cw), label_smoothing, B, K, h, w, H, W, ignore_index, _p(part), _s()), 'upsample_ce_weighted_fwd')
     PROFILER.end_bytes(tok)
     out = _f32((2,), logits.device)
     check(L.sl_upsample_ce_finalize(_p(part), nblk, _p(out), _s()), 'upsample_ce_finalize')
     return out
 
 
-def upsample_ce_bwd(logits, target, loss_cnt, gscale, ignore_index):
+def upsample_ce_bwd(logits, target, loss_cnt, gscale, ignore_index, weight=None, label_smoothing=0.0):
     B, K, h, w = logits.shape
     H, W = target.shape[1:]
     dl = torch.empty_like(logits)
     tok = PROFILER.begin_bytes('upsample_ce_bwd', 2 * logits.numel() * 4 + target.numel() * target.element_size())
-    check(_lib.lib().sl_upsample_ce_bwd(_p(logits), _p(target), _p(loss_cnt), _p(gscale), B, K, h, w, H, W, ignore_index, _p(dl), _s()), 'upsample_ce_bwd')
+    if weight is None and label_smoothing == 0.0:
+        check(_lib.lib().sl_upsample_ce_bwd(_p(logits), _p(target), _p(loss_cnt), _p(gscale), B, K, h, w, H, W, ignore_index, _p(dl), _s()), 'upsample_ce_bwd')
+    else:
+        cw = _ce_class_weight(weight, K, logits.device)
+        check(_lib.lib().sl_upsample_ce_weighted_bwd(_p(logits), _p(target), _p(cw), label_smoothing, _p(loss_cnt), _p(gscale), B, K, h, w, H, W, ignore_index,
+                                                      _p(dl), _s()), 'upsample_ce_weighted_bwd')
     PROFILER.end_bytes(tok)
     return dl
 

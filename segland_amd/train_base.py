@@ -15,7 +15,7 @@ from . import dataset as dataset_pkg
 from . import networks
 from . import bucket_step
 from . import graph_step
-from .drivers import adjust_learning_rate_poly, batch_to_device, build_parser, load_training_state, save_training_state, checkpoint_or_none, compute_dtype, miou, resolve, save_checkpoint, validate
+from .drivers import adjust_learning_rate_poly, batch_to_device, build_parser, load_training_state, save_training_state, checkpoint_or_none, compute_dtype, log_loss_options, miou, resolve, save_checkpoint, validate
 from .engine import Engine
 from .loss import get_loss
 from .utils import pyt_utils as my_utils
@@ -55,7 +55,9 @@ def main(argv=None):
             test_sampler.set_epoch(0)
 
         criterion = get_loss(args)
-        norm = nn.SyncBatchNorm if engine.distributed else nn.BatchNorm2d       # parameter holders; statistics are per GPU
+        if engine.is_main:
+            log_loss_options(args)
+        norm =nn.SyncBatchNorm if engine.distributed else nn.BatchNorm2d       # parameter holders; statistics are per GPU
         assert args.os in (8, 16, 32)
         model_cls = getattr(networks, args.model).GFSS_Model                    # `networks.<model>.GFSS_Model`
         seg_model = model_cls(n_base=args.base_classes, criterion=criterion, backbone=args.backbone, norm_layer=norm,
