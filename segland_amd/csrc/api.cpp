@@ -1,6 +1,8 @@
 // Error string + version of libsegland_hip.so
 #include <stdarg.h>
 #include <stdio.h>
+#include <mutex>
+#include <unordered_map>
 #include "common.h"
 
 static thread_local char g_err[512] = "";
@@ -14,7 +16,24 @@ void sl_set_error(const char* fmt, ...) {
 
 extern "C" int sl_version(void) { return 100; }
 extern "C" const char* sl_last_error_string(void) { return g_err; }
-// the runtime's sticky "last error" of this thread, read and reset: after a failed stream capture the next SL_LAUNCH_CHECK would otherwise report THAT error for a
+
+// Per kernel and once per process (again only for a larger request): the limit that has been granted to each kernel so far.
+__attribute__((visibility("hidden"))) int sl_lds_opt_in(const char* name, const void* kernel, size_t lds_bytes) {
+  static std::mutex mu;
+  static std::unordered_map<const void*, size_t> granted;
+  std::lock_guard<std::mutex> lock(mu);
+  size_t& have = granted[kernel];
+  if (lds_bytes <= have) return 0;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  if (e != hipSuccess) {
+    sl_set_error("%s: opt-in to %zu bytes of dynamic LDS refused: %s", name, lds_bytes, hipGetErrorString(e));
+    return (int)e;
+  }
+  have = lds_bytes;
+  return 0;
+}
+
+// the runtime's sticky "last error" of this thread, read and reset: after a failed stream capture the next sl_launch would otherwise report THAT error for a
 // launch that went through (the kernel-by-kernel step right after a failed capture attempt: graph_step.py / bucket_step.py call this in their except branch)
 extern "C" int sl_hip_clear_error(void) { return (int)hipGetLastError(); }
 

@@ -58,8 +58,6 @@ extern "C" int sl_augment_batch(const void* tiles_dev, const int* flip_rot_dev, 
   static_assert(sizeof(AugTile) == 32, "table layout is part of the ABI");
   const long long n = (long long)B * crop_h * crop_w;
   const int grid = (int)((n + 255) / 256 > 16384 ? 16384 : (n + 255) / 256);
-  hipLaunchKernelGGL(augment_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const AugTile*)tiles_dev, flip_rot_dev, B, crop_h, crop_w,
-                     mean3_host[0], mean3_host[1], mean3_host[2], std3_host[0], std3_host[1], std3_host[2], ignore_label, label_lut_dev, out_img, out_lbl);
-  SL_LAUNCH_CHECK("augment_kernel");
-  return 0;
+  return sl_launch("augment_kernel", augment_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const AugTile*)tiles_dev, flip_rot_dev, B, crop_h, crop_w,
+                   mean3_host[0], mean3_host[1], mean3_host[2], std3_host[0], std3_host[1], std3_host[2], ignore_label, label_lut_dev, out_img, out_lbl);
 }

@@ -359,10 +359,8 @@ extern "C" int sl_bn_finalize_train(const float* stat_partial, int stat_rows, in
                                     float* mean, float* invstd, float* scale, float* shift, sl_stream_t stream) {
   SL_REQUIRE(stat_partial && mean && invstd && scale && shift && C > 0 && stat_rows > 0 && count > 0, "bn_finalize_train: bad args");
   SL_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "bn_finalize_train: running stats must come in pairs");
-  hipLaunchKernelGGL((bn_finalize_train_kernel<32, 32>), dim3(cdiv(C, 32)), dim3(1024), 0, (hipStream_t)stream, stat_partial, stat_rows, C, (double)count, gamma, beta,
-                     running_mean, running_var, momentum, eps, mean, invstd, scale, shift, (const float*)nullptr, 0);
-  SL_LAUNCH_CHECK("bn_finalize_train_kernel");
-  return 0;
+  return sl_launch("bn_finalize_train_kernel", bn_finalize_train_kernel<32, 32>, dim3(cdiv(C, 32)), dim3(1024), 0, (hipStream_t)stream, stat_partial, stat_rows, C, (double)count, gamma, beta,
+                   running_mean, running_var, momentum, eps, mean, invstd, scale, shift, (const float*)nullptr, 0);
 }
 
 extern "C" int sl_bn_finalize_train_bias(const float* stat_partial, int stat_rows, int C, long long count, const float* gamma,
@@ -370,67 +368,45 @@ extern "C" int sl_bn_finalize_train_bias(const float* stat_partial, int stat_row
                                          float* mean, float* invstd, float* scale, float* shift, const float* conv_bias, int bias_n, sl_stream_t stream) {
   SL_REQUIRE(stat_partial && mean && invstd && scale && shift && C > 0 && stat_rows > 0 && count > 0, "bn_finalize_train_bias: bad args");
   SL_REQUIRE(running_mean && running_var && conv_bias && bias_n > 0 && bias_n <= C, "bn_finalize_train_bias: running stats and bias_n in 1..C conv bias entries are required");
-  hipLaunchKernelGGL((bn_finalize_train_kernel<32, 32>), dim3(cdiv(C, 32)), dim3(1024), 0, (hipStream_t)stream, stat_partial, stat_rows, C, (double)count, gamma, beta,
-                     running_mean, running_var, momentum, eps, mean, invstd, scale, shift, conv_bias, bias_n);
-  SL_LAUNCH_CHECK("bn_finalize_train_kernel");
-  return 0;
+  return sl_launch("bn_finalize_train_kernel", bn_finalize_train_kernel<32, 32>, dim3(cdiv(C, 32)), dim3(1024), 0, (hipStream_t)stream, stat_partial, stat_rows, C, (double)count, gamma, beta,
+                   running_mean, running_var, momentum, eps, mean, invstd, scale, shift, conv_bias, bias_n);
 }
 
 extern "C" int sl_bn_finalize_eval(int C, const float* gamma, const float* beta, const float* running_mean,
                                    const float* running_var, float eps, float* mean, float* invstd, float* scale,
                                    float* shift, sl_stream_t stream) {
   SL_REQUIRE(running_mean && running_var && scale && shift && C > 0, "bn_finalize_eval: bad args");
-  hipLaunchKernelGGL(bn_finalize_eval_kernel, dim3(cdiv(C, 64)), dim3(64), 0, (hipStream_t)stream, C, gamma, beta, running_mean,
-                     running_var, eps, mean, invstd, scale, shift);
-  SL_LAUNCH_CHECK("bn_finalize_eval_kernel");
-  return 0;
+  return sl_launch("bn_finalize_eval_kernel", bn_finalize_eval_kernel, dim3(cdiv(C, 64)), dim3(64), 0, (hipStream_t)stream, C, gamma, beta, running_mean,
+                   running_var, eps, mean, invstd, scale, shift);
 }
 
-template <typename T>
-static int launch_bn_act(const void* x, const float* scale, const float* shift, const void* residual, int relu, void* y, uint8_t* mask_out, long long rows, int C, hipStream_t st) {
-  constexpr int V = Vec16<T>::N;
-  const long long nvec = rows * C / V;
-  SL_REQUIRE(nvec < (1ll << 31), "bn_act_fwd: tensor too large");
-  const unsigned nvc = C / V;
-  const bool fixed = nvc <= 256 && 256 % nvc == 0;
-  const int blocks = ew_blocks((nvec + 3) / 4);
-  if (fixed) hipLaunchKernelGGL((bn_act_fwd_kernel<T, true>), dim3(blocks), dim3(256), 0, st, (const T*)x, scale, shift, (const T*)residual, relu, (T*)y, mask_out, (unsigned)nvec, nvc);
-  else hipLaunchKernelGGL((bn_act_fwd_kernel<T, false>), dim3(blocks), dim3(256), 0, st, (const T*)x, scale, shift, (const T*)residual, relu, (T*)y, mask_out, (unsigned)nvec, nvc);
-  SL_LAUNCH_CHECK("bn_act_fwd_kernel");
-  return 0;
-}
+// the element-wise passes: C / V channel vectors per row; a block's threads keep their channels when 256 is a multiple of that (FIXEDC)
+static bool fixed_channels(unsigned nvc) { return nvc <= 256 && 256 % nvc == 0; }
 
 extern "C" int sl_bn_act_fwd(int dtype, const void* x, const float* scale, const float* shift, const void* residual,
                              int relu, void* y, uint8_t* relu_mask, long long rows, int C, sl_stream_t stream) {
   SL_REQUIRE(x && scale && shift && y && rows > 0 && C > 0 && C % 8 == 0, "bn_act_fwd: bad args");
-  if (dtype == SL_BF16) return launch_bn_act<bf16_t>(x, scale, shift, residual, relu, y, relu_mask, rows, C, (hipStream_t)stream);
-  if (dtype == SL_F32) return launch_bn_act<float>(x, scale, shift, residual, relu, y, relu_mask, rows, C, (hipStream_t)stream);
-  SL_REQUIRE(false, "bn_act_fwd: bad dtype");
-  return 0;
-}
-
-template <typename T>
-static int launch_bn_act2(const void* x, const float* scale, const float* shift, const void* x2, const float* scale2, const float* shift2, int relu, void* y,
-                          uint8_t* mask_out, long long rows, int C, hipStream_t st) {
-  constexpr int V = Vec16<T>::N;
-  const long long nvec = rows * C / V;
-  SL_REQUIRE(nvec < (1ll << 31), "bn_act2_fwd: tensor too large");
-  const unsigned nvc = C / V;
-  const bool fixed = nvc <= 256 && 256 % nvc == 0;
-  const int blocks = ew_blocks((nvec + 3) / 4);
-  if (fixed) hipLaunchKernelGGL((bn_act2_fwd_kernel<T, true>), dim3(blocks), dim3(256), 0, st, (const T*)x, scale, shift, (const T*)x2, scale2, shift2, relu, (T*)y, mask_out, (unsigned)nvec, nvc);
-  else hipLaunchKernelGGL((bn_act2_fwd_kernel<T, false>), dim3(blocks), dim3(256), 0, st, (const T*)x, scale, shift, (const T*)x2, scale2, shift2, relu, (T*)y, mask_out, (unsigned)nvec, nvc);
-  SL_LAUNCH_CHECK("bn_act2_fwd_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "bn_act_fwd", [&](auto t) -> int {
+    using T = decltype(t);
+    const long long nvec = rows * C / Vec16<T>::N;
+    SL_REQUIRE(nvec < (1ll << 31), "bn_act_fwd: tensor too large");
+    const unsigned nvc = C / Vec16<T>::N;
+    return sl_launch("bn_act_fwd_kernel", fixed_channels(nvc) ? bn_act_fwd_kernel<T, true> : bn_act_fwd_kernel<T, false>, dim3(ew_blocks((nvec + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                     (const T*)x, scale, shift, (const T*)residual, relu, (T*)y, relu_mask, (unsigned)nvec, nvc);
+  });
 }
 
 extern "C" int sl_bn_act2_fwd(int dtype, const void* x, const float* scale, const float* shift, const void* x2, const float* scale2, const float* shift2,
                               int relu, void* y, uint8_t* relu_mask, long long rows, int C, sl_stream_t stream) {
   SL_REQUIRE(x && scale && shift && x2 && scale2 && shift2 && y && rows > 0 && C > 0 && C % 8 == 0, "bn_act2_fwd: bad args");
-  if (dtype == SL_BF16) return launch_bn_act2<bf16_t>(x, scale, shift, x2, scale2, shift2, relu, y, relu_mask, rows, C, (hipStream_t)stream);
-  if (dtype == SL_F32) return launch_bn_act2<float>(x, scale, shift, x2, scale2, shift2, relu, y, relu_mask, rows, C, (hipStream_t)stream);
-  SL_REQUIRE(false, "bn_act2_fwd: bad dtype");
-  return 0;
+  return sl_by_dtype(dtype, "bn_act2_fwd", [&](auto t) -> int {
+    using T = decltype(t);
+    const long long nvec = rows * C / Vec16<T>::N;
+    SL_REQUIRE(nvec < (1ll << 31), "bn_act2_fwd: tensor too large");
+    const unsigned nvc = C / Vec16<T>::N;
+    return sl_launch("bn_act2_fwd_kernel", fixed_channels(nvc) ? bn_act2_fwd_kernel<T, true> : bn_act2_fwd_kernel<T, false>, dim3(ew_blocks((nvec + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                     (const T*)x, scale, shift, (const T*)x2, scale2, shift2, relu, (T*)y, relu_mask, (unsigned)nvec, nvc);
+  });
 }
 
 extern "C" int sl_bn_bwd_reduce_rows(long long rows, int C) { (void)C; return reduce_blocks(rows); }
@@ -438,92 +414,56 @@ extern "C" int sl_bn_bwd_reduce_rows(long long rows, int C) { (void)C; return re
 extern "C" int sl_bn_bwd_reduce(int dtype, const void* dy, const void* y, const uint8_t* relu_mask, const void* x, const float* mean,
                                 const float* invstd, float* partial, long long rows, int C, sl_stream_t stream) {
   SL_REQUIRE(dy && x && mean && invstd && partial && rows > 0 && C > 0 && C % 8 == 0, "bn_bwd_reduce: bad args");
-  const int nblk = reduce_blocks(rows);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SL_BF16)
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16_t>, dim3(nblk), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)y, relu_mask, (const bf16_t*)x, mean, invstd, partial, rows, C);
-  else if (dtype == SL_F32)
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(nblk), dim3(256), 0, st, (const float*)dy, (const float*)y, relu_mask, (const float*)x, mean, invstd, partial, rows, C);
-  else SL_REQUIRE(false, "bn_bwd_reduce: bad dtype");
-  SL_LAUNCH_CHECK("bn_bwd_reduce_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "bn_bwd_reduce", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("bn_bwd_reduce_kernel", bn_bwd_reduce_kernel<T>, dim3(reduce_blocks(rows)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (const T*)y, relu_mask, (const T*)x, mean, invstd,
+                     partial, rows, C, nullptr, nullptr, nullptr, nullptr);
+  });
 }
 
 extern "C" int sl_bn_bwd_finalize(const float* partial, int nblk, int C, long long count, const float* gamma,
                                   const float* mean, const float* invstd, int train, float* dgamma, float* dbeta,
                                   float* cA, float* cB, float* cC, sl_stream_t stream) {
   SL_REQUIRE(partial && invstd && cA && cB && cC && nblk > 0 && C > 0 && count > 0, "bn_bwd_finalize: bad args");
-  hipLaunchKernelGGL((bn_bwd_finalize_kernel<32, 32>), dim3(cdiv(C, 32)), dim3(1024), 0, (hipStream_t)stream, partial, nblk, C, (double)count, gamma, mean, invstd, train,
-                     dgamma, dbeta, cA, cB, cC);
-  SL_LAUNCH_CHECK("bn_bwd_finalize_kernel");
-  return 0;
-}
-
-template <typename T>
-static int launch_bn_apply(const void* dy, const void* y, const uint8_t* mask, const void* x, const float* cA, const float* cB, const float* cC, const float* mean,
-                           void* dx, void* dres, long long rows, int C, hipStream_t st) {
-  constexpr int V = Vec16<T>::N;
-  const long long nvec = rows * C / V;
-  SL_REQUIRE(nvec < (1ll << 31), "bn_bwd_apply: tensor too large");
-  const unsigned nvc = C / V;
-  const bool fixed = nvc <= 256 && 256 % nvc == 0;
-  const int blocks = ew_blocks((nvec + 1) / 2);
-  if (fixed) hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true>), dim3(blocks), dim3(256), 0, st, (const T*)dy, (const T*)y, mask, (const T*)x, cA, cB, cC, mean, (T*)dx, (T*)dres, (unsigned)nvec, nvc);
-  else hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false>), dim3(blocks), dim3(256), 0, st, (const T*)dy, (const T*)y, mask, (const T*)x, cA, cB, cC, mean, (T*)dx, (T*)dres, (unsigned)nvec, nvc);
-  SL_LAUNCH_CHECK("bn_bwd_apply_kernel");
-  return 0;
+  return sl_launch("bn_bwd_finalize_kernel", bn_bwd_finalize_kernel<32, 32>, dim3(cdiv(C, 32)), dim3(1024), 0, (hipStream_t)stream, partial, nblk, C, (double)count, gamma, mean, invstd, train,
+                   dgamma, dbeta, cA, cB, cC);
 }
 
 extern "C" int sl_bn_bwd_apply(int dtype, const void* dy, const void* y, const uint8_t* relu_mask, const void* x, const float* cA, const float* cB,
                                const float* cC, const float* mean, void* dx, void* dres, long long rows, int C,
                                sl_stream_t stream) {
   SL_REQUIRE(dy && x && cA && cB && cC && mean && dx && rows > 0 && C > 0 && C % 8 == 0, "bn_bwd_apply: bad args");
-  if (dtype == SL_BF16) return launch_bn_apply<bf16_t>(dy, y, relu_mask, x, cA, cB, cC, mean, dx, dres, rows, C, (hipStream_t)stream);
-  if (dtype == SL_F32) return launch_bn_apply<float>(dy, y, relu_mask, x, cA, cB, cC, mean, dx, dres, rows, C, (hipStream_t)stream);
-  SL_REQUIRE(false, "bn_bwd_apply: bad dtype");
-  return 0;
+  return sl_by_dtype(dtype, "bn_bwd_apply", [&](auto t) -> int {
+    using T = decltype(t);
+    const long long nvec = rows * C / Vec16<T>::N;
+    SL_REQUIRE(nvec < (1ll << 31), "bn_bwd_apply: tensor too large");
+    const unsigned nvc = C / Vec16<T>::N;
+    return sl_launch("bn_bwd_apply_kernel", fixed_channels(nvc) ? bn_bwd_apply_kernel<T, true> : bn_bwd_apply_kernel<T, false>, dim3(ew_blocks((nvec + 1) / 2)), dim3(256), 0, (hipStream_t)stream,
+                     (const T*)dy, (const T*)y, relu_mask, (const T*)x, cA, cB, cC, mean, (T*)dx, (T*)dres, (unsigned)nvec, nvc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  });
 }
 
 // Two BatchNorms behind one ReLU (bn3 + the downsample BN of the first bottleneck of a stage): ONE sweep over dy and the ReLU bits for both reduces / both applies.
 extern "C" int sl_bn_bwd_reduce2(int dtype, const void* dy, const uint8_t* relu_mask, const void* x1, const float* mean1, const float* invstd1, float* partial1,
                                  const void* x2, const float* mean2, const float* invstd2, float* partial2, long long rows, int C, sl_stream_t stream) {
   SL_REQUIRE(dy && x1 && x2 && mean1 && invstd1 && mean2 && invstd2 && partial1 && partial2 && rows > 0 && C > 0 && C % 8 == 0, "bn_bwd_reduce2: bad args");
-  const int nblk = reduce_blocks(rows);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SL_BF16)
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16_t, true>), dim3(nblk), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)nullptr, relu_mask, (const bf16_t*)x1, mean1, invstd1, partial1, rows, C,
-                       (const bf16_t*)x2, mean2, invstd2, partial2);
-  else if (dtype == SL_F32)
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<float, true>), dim3(nblk), dim3(256), 0, st, (const float*)dy, (const float*)nullptr, relu_mask, (const float*)x1, mean1, invstd1, partial1, rows, C,
-                       (const float*)x2, mean2, invstd2, partial2);
-  else SL_REQUIRE(false, "bn_bwd_reduce2: bad dtype");
-  SL_LAUNCH_CHECK("bn_bwd_reduce_kernel<dual>");
-  return 0;
-}
-
-template <typename T>
-static int launch_bn_apply2(const void* dy, const uint8_t* mask, const void* x1, const float* cA1, const float* cB1, const float* cC1, const float* mean1, void* dx1,
-                            const void* x2, const float* cA2, const float* cB2, const float* cC2, const float* mean2, void* dx2, long long rows, int C, hipStream_t st) {
-  constexpr int V = Vec16<T>::N;
-  const long long nvec = rows * C / V;
-  SL_REQUIRE(nvec < (1ll << 31), "bn_bwd_apply2: tensor too large");
-  const unsigned nvc = C / V;
-  const bool fixed = nvc <= 256 && 256 % nvc == 0;
-  const int blocks = ew_blocks((nvec + 1) / 2);
-  if (fixed) hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true, true>), dim3(blocks), dim3(256), 0, st, (const T*)dy, (const T*)nullptr, mask, (const T*)x1, cA1, cB1, cC1, mean1, (T*)dx1, (T*)nullptr,
-                                (unsigned)nvec, nvc, (const T*)x2, cA2, cB2, cC2, mean2, (T*)dx2);
-  else hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false, true>), dim3(blocks), dim3(256), 0, st, (const T*)dy, (const T*)nullptr, mask, (const T*)x1, cA1, cB1, cC1, mean1, (T*)dx1, (T*)nullptr,
-                          (unsigned)nvec, nvc, (const T*)x2, cA2, cB2, cC2, mean2, (T*)dx2);
-  SL_LAUNCH_CHECK("bn_bwd_apply_kernel<dual>");
-  return 0;
+  return sl_by_dtype(dtype, "bn_bwd_reduce2", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("bn_bwd_reduce_kernel", bn_bwd_reduce_kernel<T, true>, dim3(reduce_blocks(rows)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, nullptr, relu_mask, (const T*)x1, mean1, invstd1,
+                     partial1, rows, C, (const T*)x2, mean2, invstd2, partial2);
+  });
 }
 
 extern "C" int sl_bn_bwd_apply2(int dtype, const void* dy, const uint8_t* relu_mask, const void* x1, const float* cA1, const float* cB1, const float* cC1,
                                 const float* mean1, void* dx1, const void* x2, const float* cA2, const float* cB2, const float* cC2, const float* mean2, void* dx2,
                                 long long rows, int C, sl_stream_t stream) {
   SL_REQUIRE(dy && x1 && x2 && cA1 && cB1 && cC1 && mean1 && dx1 && cA2 && cB2 && cC2 && mean2 && dx2 && rows > 0 && C > 0 && C % 8 == 0, "bn_bwd_apply2: bad args");
-  if (dtype == SL_BF16) return launch_bn_apply2<bf16_t>(dy, relu_mask, x1, cA1, cB1, cC1, mean1, dx1, x2, cA2, cB2, cC2, mean2, dx2, rows, C, (hipStream_t)stream);
-  if (dtype == SL_F32) return launch_bn_apply2<float>(dy, relu_mask, x1, cA1, cB1, cC1, mean1, dx1, x2, cA2, cB2, cC2, mean2, dx2, rows, C, (hipStream_t)stream);
-  SL_REQUIRE(false, "bn_bwd_apply2: bad dtype");
-  return 0;
+  return sl_by_dtype(dtype, "bn_bwd_apply2", [&](auto t) -> int {
+    using T = decltype(t);
+    const long long nvec = rows * C / Vec16<T>::N;
+    SL_REQUIRE(nvec < (1ll << 31), "bn_bwd_apply2: tensor too large");
+    const unsigned nvc = C / Vec16<T>::N;
+    return sl_launch("bn_bwd_apply_kernel", fixed_channels(nvc) ? bn_bwd_apply_kernel<T, true, true> : bn_bwd_apply_kernel<T, false, true>, dim3(ew_blocks((nvec + 1) / 2)), dim3(256), 0, (hipStream_t)stream,
+                     (const T*)dy, nullptr, relu_mask, (const T*)x1, cA1, cB1, cC1, mean1, (T*)dx1, nullptr, (unsigned)nvec, nvc, (const T*)x2, cA2, cB2, cC2, mean2, (T*)dx2);
+  });
 }

@@ -119,14 +119,41 @@ extern SlDebugState g_sl_debug;
       return SL_EINVAL;                  \
     }                                    \
   } while (0)
-#define SL_LAUNCH_CHECK(name)                                                \
-  do {                                                                       \
-    hipError_t e__ = hipGetLastError();                                      \
-    if (e__ != hipSuccess) {                                                 \
-      sl_set_error("%s: %s", name, hipGetErrorString(e__));                  \
-      return (int)e__;                                                       \
-    }                                                                        \
+// return at the first failing step of an entry point (a launch, an opt-in, a nested launcher): nothing that depends on it is queued
+#define SL_TRY(expr)                     \
+  do {                                   \
+    const int rc__ = (expr);             \
+    if (rc__) return rc__;               \
   } while (0)
+
+// ---- the one launch path.  `name` is the kernel's own name without template arguments, as a profiler shows it.
+// More than 64 KiB of dynamic LDS needs an opt-in per kernel: sl_lds_opt_in (api.cpp) raises the kernel's limit once per process (again only for a larger request) and
+// CHECKS the runtime's answer; sl_launch calls it right before the launch that needs it, so the first launch of such a kernel is where the opt-in happens.
+int sl_lds_opt_in(const char* name, const void* kernel, size_t lds_bytes);
+
+template <typename T> struct sl_as_is { typedef T type; };      // non-deduced: the kernel's signature alone fixes the argument types, call sites convert implicitly
+
+template <typename... Args>
+static inline int sl_launch(const char* name, void (*kernel)(Args...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, typename sl_as_is<Args>::type... args) {
+  if (lds_bytes > 64 * 1024) SL_TRY(sl_lds_opt_in(name, (const void*)kernel, lds_bytes));
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    sl_set_error("%s: %s", name, hipGetErrorString(e));
+    return (int)e;
+  }
+  return 0;
+}
+
+// f(T()) with the element type of `dtype`; f returns the entry point's code and may use SL_REQUIRE:
+//   return sl_by_dtype(dtype, "entry", [&](auto t) -> int { using T = decltype(t); ... });
+template <typename F>
+static inline int sl_by_dtype(int dtype, const char* entry, F&& f) {
+  if (dtype == SL_BF16) return f(bf16_t());
+  if (dtype == SL_F32) return f(float());
+  sl_set_error("%s: bad dtype", entry);
+  return SL_EINVAL;
+}
 
 __host__ __device__ static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 

@@ -361,9 +361,7 @@ __global__ __launch_bounds__(512) void conv_gemm_p8_kernel(ConvGemmParams p) {
 int launch_splitk_finish(ConvGemmParams& p, hipStream_t st) {
   const size_t nvec = (size_t)p.M * p.N / 8;
   const int blocks = (int)((nvec + 255) / 256 < 4096 ? (nvec + 255) / 256 : 4096);
-  hipLaunchKernelGGL(conv_splitk_finish_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, p);
-  SL_LAUNCH_CHECK("conv_splitk_finish_kernel");
-  return 0;
+  return sl_launch("conv_splitk_finish_kernel", conv_splitk_finish_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, p);
 }
 
 }  // namespace
@@ -373,13 +371,6 @@ int slconv::launch_p8(ConvGemmParams& p, hipStream_t st) {
   p.gridN = p.N / 256;
   p.trace = g_sl_debug.p8_trace;
   p.flags |= 1;                                 // the next tile's first wait is counted past the epilogue's own loads and stores
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* all[6] = {(const void*)conv_gemm_p8_kernel<0, false>, (const void*)conv_gemm_p8_kernel<1, false>, (const void*)conv_gemm_p8_kernel<2, false>,
-                          (const void*)conv_gemm_p8_kernel<0, true>,  (const void*)conv_gemm_p8_kernel<1, true>,  (const void*)conv_gemm_p8_kernel<2, true>};
-    for (const void* f : all) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P8_LDS);
-    attr_set = true;
-  }
   const int ntiles = p.gridM * p.gridN;
   // persistent: min(tiles, 256) blocks walk over the tiles; the instantiation with the gated-statistics store phase only where it is used
   const int epi = p.gate ? 1 : (p.bias || p.scale) && !p.stat_partial ? 2 : 0;
@@ -387,9 +378,7 @@ int slconv::launch_p8(ConvGemmParams& p, hipStream_t st) {
   const bool k1 = g_sl_debug.conv_p8_k1 && p.KH == 1 && p.KW == 1 && p.pad == 0 && p.C2 == 0 && !p.sub;
   void (*const kern[2][3])(ConvGemmParams) = {{conv_gemm_p8_kernel<0, false>, conv_gemm_p8_kernel<1, false>, conv_gemm_p8_kernel<2, false>},
                                               {conv_gemm_p8_kernel<0, true>, conv_gemm_p8_kernel<1, true>, conv_gemm_p8_kernel<2, true>}};
-  hipLaunchKernelGGL(kern[k1][epi], dim3(ntiles > 256 ? 256 : ntiles), dim3(512), P8_LDS, st, p);
-  SL_LAUNCH_CHECK("conv_gemm_p8_kernel");
-  return 0;
+  return sl_launch("conv_gemm_p8_kernel", kern[k1][epi], dim3(ntiles > 256 ? 256 : ntiles), dim3(512), P8_LDS, st, p);
 }
 
 namespace {
@@ -743,23 +732,13 @@ int slconv::launch_p9(ConvGemmParams& p, hipStream_t st) {
   // [EPI][0: generic, 1 / 2 / 3: lean d = 1 / 2 / 4][flipped window]; split-K is planned for forward convs only (splitk_parts), so <2, D, true> is not instantiated
   static const kern_t kern[3][4][2] = {P9_ROW(0, true), P9_ROW(1, true), P9_ROW(2, false)};
 #undef P9_ROW
-  static bool attr_set = false;
-  if (!attr_set) {
-    for (int e = 0; e < 3; ++e)
-      for (int v = 0; v < 4; ++v)
-        for (int f = 0; f < 2; ++f) (void)hipFuncSetAttribute((const void*)kern[e][v][f], hipFuncAttributeMaxDynamicSharedMemorySize, (int)(P9_LDS1 > P9_LDS ? P9_LDS1 : P9_LDS));
-    attr_set = true;
-  }
   // the lean form of the K-tile loop (test hook sl_debug_conv_p9_lean: 0 sends every launch through the generic loop, which gives the same bits); a split-K part holds at least one chunk
   const bool lean = g_sl_debug.conv_p9_lean && !(p.flags & 8) && (p.ksplit <= 1 || (p.mode == 0 && p.ksplit <= p.C1 / 64));
   const int v = !lean ? 0 : p.dil == 1 ? 1 : p.dil == 2 ? 2 : 3, f = lean && p.mode != 0;
   const size_t lds = p.dil == 1 ? P9_LDS1 : P9_LDS;
   if (p.ksplit > 1) {
-    hipLaunchKernelGGL(kern[2][v][f], dim3(p.gridM * p.gridN * p.ksplit), dim3(512), lds, st, p);
-    SL_LAUNCH_CHECK("conv_gemm_p9_kernel (split-K)");
+    SL_TRY(sl_launch("conv_gemm_p9_kernel", kern[2][v][f], dim3(p.gridM * p.gridN * p.ksplit), dim3(512), lds, st, p));
     return launch_splitk_finish(p, st);
   }
-  hipLaunchKernelGGL(kern[p.gate ? 1 : 0][v][f], dim3(p.gridM * p.gridN), dim3(512), lds, st, p);
-  SL_LAUNCH_CHECK("conv_gemm_p9_kernel");
-  return 0;
+  return sl_launch("conv_gemm_p9_kernel", kern[p.gate ? 1 : 0][v][f], dim3(p.gridM * p.gridN), dim3(512), lds, st, p);
 }

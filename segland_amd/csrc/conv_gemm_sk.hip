@@ -189,11 +189,7 @@ bool slconv::c64k3_shape(int dtype, int KH, int KW, int stride, int pad, int dil
 
 int slconv::launch_c64k3(ConvGemmParams& p, hipStream_t st) {
   const int ntiles = p.B * cdiv(p.Hs, C64_T) * cdiv(p.Ws, C64_T);
-  static bool attr_set = false;
-  if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv_c64k3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, C64_LDS); attr_set = true; }
-  hipLaunchKernelGGL(conv_c64k3_kernel, dim3(ntiles < 256 ? ntiles : 256), dim3(256), C64_LDS, st, p, ntiles);
-  SL_LAUNCH_CHECK("conv_c64k3_kernel");
-  return 0;
+  return sl_launch("conv_c64k3_kernel", conv_c64k3_kernel, dim3(ntiles < 256 ? ntiles : 256), dim3(256), C64_LDS, st, p, ntiles);
 }
 
 namespace {
@@ -496,13 +492,9 @@ bool slconv::sk_shape(int dtype, int KH, int KW, int stride, int pad, int Cin, i
 namespace {
 template <int KS, int MODE, bool SKEW>
 int launch_sk_t(ConvGemmParams& p, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv_gemm_sk_kernel<KS, MODE, SKEW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
   const int lds = MODE == 5 ? SkGeom<KS>::LDS + 256 * (p.N / 8 + 16)
                             : (MODE == 2 && p.addend_mask ? SkGeom<KS>::OFF_RED + 256 * (p.N / 8 + 16) : SkGeom<KS>::LDS);      // statistic partials and / or the block's gate bytes behind the staging patches
-  hipLaunchKernelGGL((conv_gemm_sk_kernel<KS, MODE, SKEW>), dim3(p.M / 256), dim3(512), lds, st, p);
-  SL_LAUNCH_CHECK("conv_gemm_sk_kernel");
-  return 0;
+  return sl_launch("conv_gemm_sk_kernel", conv_gemm_sk_kernel<KS, MODE, SKEW>, dim3(p.M / 256), dim3(512), lds, st, p);
 }
 template <int MODE, bool SKEW>
 int launch_sk_k(ConvGemmParams& p, hipStream_t st) {

@@ -370,17 +370,8 @@ int launch_ring_subp(ConvGemmParams& p, hipStream_t st) {
   using RG = RingGeom<bf16_t, 256, BN, WM, WN, 64, 4>;
   p.gridM = p.M / 256;
   p.gridN = p.N / BN;
-  const size_t lds = RG::LDS_BYTES;
-  static bool attr_set = false;
-  if (!attr_set && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute((const void*)conv_gemm_ring_kernel<bf16_t, 256, BN, WM, WN, 64, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)conv_gemm_ring_kernel<bf16_t, 256, BN, WM, WN, 64, 4, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  if (p.gate) hipLaunchKernelGGL((conv_gemm_ring_kernel<bf16_t, 256, BN, WM, WN, 64, 4, true, true>), dim3(p.gridM * p.gridN), dim3(64 * WM * WN), lds, st, p);
-  else        hipLaunchKernelGGL((conv_gemm_ring_kernel<bf16_t, 256, BN, WM, WN, 64, 4, false, true>), dim3(p.gridM * p.gridN), dim3(64 * WM * WN), lds, st, p);
-  SL_LAUNCH_CHECK("conv_gemm_ring_kernel (parity plane)");
-  return 0;
+  return sl_launch("conv_gemm_ring_kernel", p.gate ? conv_gemm_ring_kernel<bf16_t, 256, BN, WM, WN, 64, 4, true, true> : conv_gemm_ring_kernel<bf16_t, 256, BN, WM, WN, 64, 4, false, true>,
+                   dim3(p.gridM * p.gridN), dim3(64 * WM * WN), RG::LDS_BYTES, st, p);
 }
 
 template <typename T, int BM, int BN, int WM, int WN, int RBYTES, int NST>
@@ -388,18 +379,9 @@ int launch_ring(ConvGemmParams& p, hipStream_t st) {
   using RG = RingGeom<T, BM, BN, WM, WN, RBYTES, NST>;
   p.gridM = cdiv(p.M, BM);
   p.gridN = p.N / BN;
-  const size_t lds = RG::LDS_BYTES;
-  static bool attr_set = false;
-  if (!attr_set && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute((const void*)conv_gemm_ring_kernel<T, BM, BN, WM, WN, RBYTES, NST, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)conv_gemm_ring_kernel<T, BM, BN, WM, WN, RBYTES, NST, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
   // like the half-tile and patch kernels: the gated-statistics store phase lives in an instantiation of its own
-  if (p.gate) hipLaunchKernelGGL((conv_gemm_ring_kernel<T, BM, BN, WM, WN, RBYTES, NST, true>), dim3(p.gridM * p.gridN), dim3(64 * WM * WN), lds, st, p);
-  else        hipLaunchKernelGGL((conv_gemm_ring_kernel<T, BM, BN, WM, WN, RBYTES, NST, false>), dim3(p.gridM * p.gridN), dim3(64 * WM * WN), lds, st, p);
-  SL_LAUNCH_CHECK("conv_gemm_ring_kernel");
-  return 0;
+  return sl_launch("conv_gemm_ring_kernel", p.gate ? conv_gemm_ring_kernel<T, BM, BN, WM, WN, RBYTES, NST, true> : conv_gemm_ring_kernel<T, BM, BN, WM, WN, RBYTES, NST, false>,
+                   dim3(p.gridM * p.gridN), dim3(64 * WM * WN), RG::LDS_BYTES, st, p);
 }
 
 
@@ -407,15 +389,7 @@ template <typename T, int BM, int BN, int WM, int WN>
 int launch_glds(ConvGemmParams& p, hipStream_t st) {
   p.gridM = cdiv(p.M, BM);
   p.gridN = p.N / BN;
-  const size_t lds = EpiGeom<T, BM, BN, WM, WN>::LDS_BYTES;
-  static bool attr_set = false;
-  if (!attr_set && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute((const void*)conv_gemm_glds_kernel<T, BM, BN, WM, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_gemm_glds_kernel<T, BM, BN, WM, WN>), dim3(p.gridM * p.gridN), dim3(64 * WM * WN), lds, st, p);
-  SL_LAUNCH_CHECK("conv_gemm_glds_kernel");
-  return 0;
+  return sl_launch("conv_gemm_glds_kernel", conv_gemm_glds_kernel<T, BM, BN, WM, WN>, dim3(p.gridM * p.gridN), dim3(64 * WM * WN), EpiGeom<T, BM, BN, WM, WN>::LDS_BYTES, st, p);
 }
 
 
@@ -490,9 +464,7 @@ int slconv::launch_tile(int cfg, int dtype, ConvGemmParams& p, hipStream_t st) {
   }
   if (dtype == SL_BF16 && cfg == 3032032) {
     p.gridM = 1; p.gridN = p.N / 32;
-    hipLaunchKernelGGL(conv_rows_small_kernel, dim3(p.N / 32), dim3(64), 0, st, p);
-    SL_LAUNCH_CHECK("conv_rows_small_kernel");
-    return 0;
+    return sl_launch("conv_rows_small_kernel", conv_rows_small_kernel, dim3(p.N / 32), dim3(64), 0, st, p);
   }
   if (dtype == SL_BF16 && cfg == 4128064) return launch_ring<bf16_t, 128, 64, 4, 1, 64, 4>(p, st);
   if (dtype == SL_BF16 && cfg == 4128192) return launch_ring<bf16_t, 128, 192, 4, 1, 64, SL_RING192_NST>(p, st);

@@ -89,12 +89,8 @@ extern "C" int sl_weight_prep_batched(const void* table_dev, int n, long long to
   SL_REQUIRE(table_dev && n > 0 && total_tiles > 0, "weight_prep_batched: bad args");
   static_assert(sizeof(PrepEntry) == 48, "table layout is part of the ABI");
   const size_t lds = (size_t)WP_O * (WP_I * 9 + 2) * sizeof(float);      // taps <= 9 (1x1 and 3x3 convs), fp32 worst case
-  static bool attr_set = false;
-  if (!attr_set) { (void)hipFuncSetAttribute((const void*)weight_prep_batched_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
   const int blocks = (int)(total_tiles < 4096 ? total_tiles : 4096);
-  hipLaunchKernelGGL(weight_prep_batched_kernel, dim3(blocks), dim3(256), lds, (hipStream_t)stream, (const PrepEntry*)table_dev, n, total_tiles);
-  SL_LAUNCH_CHECK("weight_prep_batched_kernel");
-  return 0;
+  return sl_launch("weight_prep_batched_kernel", weight_prep_batched_kernel, dim3(blocks), dim3(256), lds, (hipStream_t)stream, (const PrepEntry*)table_dev, n, total_tiles);
 }
 
 namespace {
@@ -129,11 +125,7 @@ extern "C" int sl_ppm_wq_prep(const float* w_oihw, int N, int Ctot, int Cs, int 
   SL_REQUIRE(N % WP_O == 0 && Cs % WP_I == 0, "ppm_wq_prep: N %% 64 == 0 and Cs %% 32 == 0");
   const long long tiles = (long long)(N / WP_O) * (Cs / WP_I);
   const size_t lds = (size_t)WP_O * (WP_I * 9 + 2) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) { (void)hipFuncSetAttribute((const void*)ppm_wq_prep_tiles_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
-  hipLaunchKernelGGL(ppm_wq_prep_tiles_kernel, dim3((unsigned)(tiles < 1024 ? tiles : 1024), nlevels), dim3(256), lds, (hipStream_t)stream, w_oihw, N, Ctot, Cs, wq_f, wq_b, tiles);
-  SL_LAUNCH_CHECK("ppm_wq_prep_tiles_kernel");
-  return 0;
+  return sl_launch("ppm_wq_prep_tiles_kernel", ppm_wq_prep_tiles_kernel, dim3((unsigned)(tiles < 1024 ? tiles : 1024), nlevels), dim3(256), lds, (hipStream_t)stream, w_oihw, N, Ctot, Cs, wq_f, wq_b, tiles);
 }
 
 // GEMM layouts of the input-channel slice [ci_off, ci_off + ci_cnt) of an OIHW weight with CinTot input channels
@@ -154,19 +146,14 @@ extern "C" int sl_weight_prep_slice(int dtype, const float* w_oihw, int Cout, in
     PrepEntry t{w_oihw, w_fwd, w_bwd, Cout, ci_cnt, KH * KW, dtype, 0};
     const long long tiles = (long long)(Cout / WP_O) * (ci_cnt / WP_I);
     const size_t lds = (size_t)WP_O * (WP_I * 9 + 2) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)weight_prep_slice_tiles_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
-    hipLaunchKernelGGL(weight_prep_slice_tiles_kernel, dim3((unsigned)(tiles < 4096 ? tiles : 4096)), dim3(256), lds, (hipStream_t)stream, t, CinTot, ci_off, tiles);
-    SL_LAUNCH_CHECK("weight_prep_slice_tiles_kernel");
-    return 0;
+    return sl_launch("weight_prep_slice_tiles_kernel", weight_prep_slice_tiles_kernel, dim3((unsigned)(tiles < 4096 ? tiles : 4096)), dim3(256), lds, (hipStream_t)stream, t, CinTot, ci_off, tiles);
   }
   const long long n = (long long)Cout * ci_cnt * KH * KW;
   const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-  if (dtype == SL_BF16) hipLaunchKernelGGL(weight_prep_slice_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, Cout, CinTot, ci_off, ci_cnt, KH * KW, (bf16_t*)w_fwd, (bf16_t*)w_bwd);
-  else if (dtype == SL_F32) hipLaunchKernelGGL(weight_prep_slice_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, Cout, CinTot, ci_off, ci_cnt, KH * KW, (float*)w_fwd, (float*)w_bwd);
-  else SL_REQUIRE(false, "weight_prep_slice: bad dtype");
-  SL_LAUNCH_CHECK("weight_prep_slice_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "weight_prep_slice", [&](auto e) -> int {
+    using T = decltype(e);
+    return sl_launch("weight_prep_slice_kernel", weight_prep_slice_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, Cout, CinTot, ci_off, ci_cnt, KH * KW, (T*)w_fwd, (T*)w_bwd);
+  });
 }
 
 extern "C" int sl_weight_prep(int dtype, const float* w_oihw, int Cout, int Cin, int KH, int KW, void* w_fwd,
@@ -174,12 +161,9 @@ extern "C" int sl_weight_prep(int dtype, const float* w_oihw, int Cout, int Cin,
   SL_REQUIRE(w_oihw && (w_fwd || w_bwd), "weight_prep: null buffer");
   const long long n = (long long)Cout * Cin * KH * KW;
   const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-  if (dtype == SL_BF16)
-    hipLaunchKernelGGL(weight_prep_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, Cout, Cin, KH * KW, (bf16_t*)w_fwd, (bf16_t*)w_bwd);
-  else if (dtype == SL_F32)
-    hipLaunchKernelGGL(weight_prep_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, Cout, Cin, KH * KW, (float*)w_fwd, (float*)w_bwd);
-  else SL_REQUIRE(false, "weight_prep: bad dtype");
-  SL_LAUNCH_CHECK("weight_prep_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "weight_prep", [&](auto e) -> int {
+    using T = decltype(e);
+    return sl_launch("weight_prep_kernel", weight_prep_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, Cout, Cin, KH * KW, (T*)w_fwd, (T*)w_bwd);
+  });
 }
 

@@ -937,14 +937,7 @@ WgradPlan plan(const SlConvDesc* d) {
 template <typename T, int BNN, int BCC, int WNN, int WCC, bool TR, bool BIAS>
 int launch_wgrad_glds_as(dim3 grid, WgradParams& p, hipStream_t st) {
   const size_t lds = (size_t)wg_ring_depth<T, BNN, BCC>() * 32 * (BNN + BCC) * sizeof(T);        // ring of 32-row stages
-  static bool attr_set = false;
-  if (!attr_set && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_glds_kernel<T, BNN, BCC, WNN, WCC, TR, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, BNN, BCC, WNN, WCC, TR, BIAS>), grid, dim3(64 * WNN * WCC), lds, st, p);
-  SL_LAUNCH_CHECK(BIAS ? "conv_wgrad_glds_kernel (bias)" : "conv_wgrad_glds_kernel");
-  return 0;
+  return sl_launch("conv_wgrad_glds_kernel", conv_wgrad_glds_kernel<T, BNN, BCC, WNN, WCC, TR, BIAS>, grid, dim3(64 * WNN * WCC), lds, st, p);
 }
 template <typename T, int BNN, int BCC, int WNN, int WCC, bool TR>
 int launch_wgrad_glds(dim3 grid, WgradParams& p, hipStream_t st) {
@@ -962,18 +955,12 @@ int launch_wgrad(const WgradPlan& pl, WgradParams& p, hipStream_t st) {
     if (pl.bcc == 256) return launch_wgrad_glds<T, 128, 256, 2, 4, TR>(grid, p, st);
     return launch_wgrad_glds<T, 128, 128, 2, 2, TR>(grid, p, st);
   }
-#define WG_LAUNCH(BNN, BCC)                                                                                   \
-  do {                                                                                                        \
-    const size_t lds = 2 * KM * ((BNN + BCC) * sizeof(T) + 2 * WPad<T>::v);                                   \
-    hipLaunchKernelGGL((conv_wgrad_kernel<T, BNN, BCC, TR>), grid, dim3(256), lds, st, p);                   \
-  } while (0)
-  if (pl.bnn == 128 && pl.bcc == 128) WG_LAUNCH(128, 128);
-  else if (pl.bnn == 128) WG_LAUNCH(128, 64);
-  else if (pl.bcc == 128) WG_LAUNCH(64, 128);
-  else WG_LAUNCH(64, 64);
+#define WG_LAUNCH(BNN, BCC) sl_launch("conv_wgrad_kernel", conv_wgrad_kernel<T, BNN, BCC, TR>, grid, dim3(256), 2 * KM * ((BNN + BCC) * sizeof(T) + 2 * WPad<T>::v), st, p)
+  if (pl.bnn == 128 && pl.bcc == 128) return WG_LAUNCH(128, 128);
+  if (pl.bnn == 128) return WG_LAUNCH(128, 64);
+  if (pl.bcc == 128) return WG_LAUNCH(64, 128);
+  return WG_LAUNCH(64, 64);
 #undef WG_LAUNCH
-  SL_LAUNCH_CHECK("conv_wgrad_kernel");
-  return 0;
 }
 
 // The plan of one weight-gradient call.  plan_wgrad is the ONLY statement of the path selection: sl_conv2d_wgrad_config, sl_conv2d_bwd_weight_bias_rows and the launch answer
@@ -1019,32 +1006,21 @@ int bias_partials(const WgradLaunch& L, const WgradArgs& a, long long rows, floa
 int run_c64k3(const SlConvDesc* d, const WgradArgs& a) {
   const int nblk = c64k3_blocks(d), ntiles = d->B * cdiv(d->H, C3_T) * cdiv(d->W, C3_T);
   const size_t lds = (size_t)(C3_PW * C3_PW + 256) * C3_PITCH;
-  static bool attr_set = false;
-  if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv_wgrad_c64k3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
-  hipLaunchKernelGGL(conv_wgrad_c64k3_kernel, dim3(nblk), dim3(256), lds, a.st, (const bf16_t*)a.x, (const bf16_t*)a.dy, (float*)a.ws, d->B, d->H, d->W, ntiles);
-  SL_LAUNCH_CHECK("conv_wgrad_c64k3_kernel");
+  SL_TRY(sl_launch("conv_wgrad_c64k3_kernel", conv_wgrad_c64k3_kernel, dim3(nblk), dim3(256), lds, a.st, (const bf16_t*)a.x, (const bf16_t*)a.dy, (float*)a.ws, d->B, d->H, d->W, ntiles));
   float* sum = (float*)a.ws + (size_t)nblk * 64 * 64 * 9;
   if (int e = sl_colsum_finalize((const float*)a.ws, nblk, 64 * 64 * 9, sum, (sl_stream_t)a.st)) return e;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(64), dim3(256), 0, a.st, (const float*)sum, a.dw, 64, 64, 9, 1, 64, 0, 64, 64);      // [n][tap][c] -> OIHW
-  SL_LAUNCH_CHECK("wgrad_reduce_kernel");
-  return 0;
+  return sl_launch("wgrad_reduce_kernel", wgrad_reduce_kernel, dim3(64), dim3(256), 0, a.st, sum, a.dw, 64, 64, 9, 1, 64, 0, 64, 64);      // [n][tap][c] -> OIHW
 }
 
 int run_c64p(const SlConvDesc* d, const WgradArgs& a) {
   const int nblk = c64p_blocks(d), nslab = c64p_slabs(d), ntiles = (int)((long long)d->B * d->H * d->W / CP_T);
   const size_t lds = (size_t)CP_T * (2 * (d->Cout + d->Cin) + 128);
-#define SL_C64P(CA, CB) do { static bool attr_set = false; \
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv_wgrad_c64p_kernel<CA, CB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; } \
-    hipLaunchKernelGGL((conv_wgrad_c64p_kernel<CA, CB>), dim3(nblk), dim3(256), lds, a.st, (const bf16_t*)a.x, (const bf16_t*)a.dy, (float*)a.ws, ntiles); } while (0)
-  if (d->Cout == 256) SL_C64P(256, 64); else if (d->Cin == 256) SL_C64P(64, 256); else if (d->Cout == 128) SL_C64P(128, 128); else SL_C64P(64, 64);
-#undef SL_C64P
-  SL_LAUNCH_CHECK("conv_wgrad_c64p_kernel");
+  const auto kern = d->Cout == 256 ? conv_wgrad_c64p_kernel<256, 64> : d->Cin == 256 ? conv_wgrad_c64p_kernel<64, 256> : d->Cout == 128 ? conv_wgrad_c64p_kernel<128, 128> : conv_wgrad_c64p_kernel<64, 64>;
+  SL_TRY(sl_launch("conv_wgrad_c64p_kernel", kern, dim3(nblk), dim3(256), lds, a.st, (const bf16_t*)a.x, (const bf16_t*)a.dy, (float*)a.ws, ntiles));
   const long long total = (long long)d->Cout * d->Cin;
   float* sum = (float*)a.ws + (size_t)nslab * total;
   if (int e = sl_colsum_finalize((const float*)a.ws, nslab, (int)total, sum, (sl_stream_t)a.st)) return e;          // fixed-order column sums over the slabs (one block per 64 numbers)
-  hipLaunchKernelGGL(wgrad_reduce_flat_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, a.st, (const float*)sum, a.dw, total, 1, d->Cin, a.c.dw_cin_total, a.c.dw_ci_off, a.c.n_valid, a.c.c_valid);
-  SL_LAUNCH_CHECK("wgrad_reduce_flat_kernel");
-  return 0;
+  return sl_launch("wgrad_reduce_flat_kernel", wgrad_reduce_flat_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, a.st, (const float*)sum, a.dw, total, 1, d->Cin, a.c.dw_cin_total, a.c.dw_ci_off, a.c.n_valid, a.c.c_valid);
 }
 
 // the split-K tile kernel; reduce_slabs follows
@@ -1072,36 +1048,31 @@ int reduce_slabs(const SlConvDesc* d, const WgradLaunch& L, const WgradArgs& a) 
   const float* ws = (const float*)a.ws;
   if (pl.pair) {
     const long long total = (long long)d->Cout * d->Cin * pl.taps;
-    hipLaunchKernelGGL(wgrad_reduce_pair_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, a.st, ws, a.dw, d->Cout, d->Cin, pl.taps, pl.splits, c.dw_cin_total, c.dw_ci_off, c.n_valid, c.c_valid);
-  } else if (pl.taps > 1) {
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(d->Cout * (d->Cin / 64)), dim3(256), 0, a.st, ws, a.dw, d->Cout, d->Cin, pl.taps, pl.splits, c.dw_cin_total, c.dw_ci_off, c.n_valid, c.c_valid);
-  } else {
-    const long long total = (long long)d->Cout * d->Cin;
-    const int nred = (int)((total + 255) / 256);
-    float* part = nullptr;                          // column sums of dy: `ncol` blocks behind the nred reduce blocks, `chunk` rows each
-    long long rows = 0, chunk = 0, ncol = 0;
-    if (L.bias == WB_REDUCE) {
-      rows = out_rows(d); chunk = sl_colsum_rows_chunk(rows, d->Cout, d->dtype == SL_BF16 ? 2 : 4); ncol = (rows + chunk - 1) / chunk;
-      if (int e = bias_partials(L, a, ncol, &part)) return e;
-    }
-    if (L.deferred) {
-      SlWgradReduce& t = *a.defer;
-      t.ws = ws; t.dw = a.dw; t.total = total; t.splits = pl.splits; t.Cin = d->Cin; t.dw_cin_total = c.dw_cin_total; t.dw_ci_off = c.dw_ci_off; t.n_valid = c.n_valid; t.c_valid = c.c_valid;
-      t.dtype = d->dtype; t.Cout = d->Cout; t.dy = part ? a.dy : nullptr; t.rows = rows; t.rows_per_block = chunk; t.colsum_part = part; t.ncol = (int)ncol;
-      return 0;
-    }
-    if (part) {
-#define SL_FLAT_COLSUM(T) hipLaunchKernelGGL(wgrad_reduce_flat_colsum_kernel<T>, dim3(nred + (int)ncol), dim3(256), 0, a.st, ws, a.dw, total, pl.splits, d->Cin, c.dw_cin_total, c.dw_ci_off, \
-                                             nred, (const T*)a.dy, rows, d->Cout, chunk, part, c.n_valid, c.c_valid)
-      if (d->dtype == SL_BF16) SL_FLAT_COLSUM(bf16_t); else SL_FLAT_COLSUM(float);
-#undef SL_FLAT_COLSUM
-      SL_LAUNCH_CHECK("wgrad_reduce_flat_colsum_kernel");
-      return 0;
-    }
-    hipLaunchKernelGGL(wgrad_reduce_flat_kernel, dim3((unsigned)nred), dim3(256), 0, a.st, ws, a.dw, total, pl.splits, d->Cin, c.dw_cin_total, c.dw_ci_off, c.n_valid, c.c_valid);
+    return sl_launch("wgrad_reduce_pair_kernel", wgrad_reduce_pair_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, a.st, ws, a.dw, d->Cout, d->Cin, pl.taps, pl.splits, c.dw_cin_total, c.dw_ci_off, c.n_valid, c.c_valid);
   }
-  SL_LAUNCH_CHECK("wgrad_reduce_kernel");
-  return 0;
+  if (pl.taps > 1)
+    return sl_launch("wgrad_reduce_kernel", wgrad_reduce_kernel, dim3(d->Cout * (d->Cin / 64)), dim3(256), 0, a.st, ws, a.dw, d->Cout, d->Cin, pl.taps, pl.splits, c.dw_cin_total, c.dw_ci_off, c.n_valid, c.c_valid);
+  const long long total = (long long)d->Cout * d->Cin;
+  const int nred = (int)((total + 255) / 256);
+  float* part = nullptr;                          // column sums of dy: `ncol` blocks behind the nred reduce blocks, `chunk` rows each
+  long long rows = 0, chunk = 0, ncol = 0;
+  if (L.bias == WB_REDUCE) {
+    rows = out_rows(d); chunk = sl_colsum_rows_chunk(rows, d->Cout, d->dtype == SL_BF16 ? 2 : 4); ncol = (rows + chunk - 1) / chunk;
+    if (int e = bias_partials(L, a, ncol, &part)) return e;
+  }
+  if (L.deferred) {
+    SlWgradReduce& t = *a.defer;
+    t.ws = ws; t.dw = a.dw; t.total = total; t.splits = pl.splits; t.Cin = d->Cin; t.dw_cin_total = c.dw_cin_total; t.dw_ci_off = c.dw_ci_off; t.n_valid = c.n_valid; t.c_valid = c.c_valid;
+    t.dtype = d->dtype; t.Cout = d->Cout; t.dy = part ? a.dy : nullptr; t.rows = rows; t.rows_per_block = chunk; t.colsum_part = part; t.ncol = (int)ncol;
+    return 0;
+  }
+  if (part)
+    return sl_by_dtype(d->dtype, "conv bwd_weight", [&](auto e) -> int {
+      using T = decltype(e);
+      return sl_launch("wgrad_reduce_flat_colsum_kernel", wgrad_reduce_flat_colsum_kernel<T>, dim3(nred + (int)ncol), dim3(256), 0, a.st, ws, a.dw, total, pl.splits, d->Cin, c.dw_cin_total, c.dw_ci_off,
+                       nred, (const T*)a.dy, rows, d->Cout, chunk, part, c.n_valid, c.c_valid);
+    });
+  return sl_launch("wgrad_reduce_flat_kernel", wgrad_reduce_flat_kernel, dim3((unsigned)nred), dim3(256), 0, a.st, ws, a.dw, total, pl.splits, d->Cin, c.dw_cin_total, c.dw_ci_off, c.n_valid, c.c_valid);
 }
 
 // dw may be a wider OIHW tensor [Cout][dw_cin_total][KH][KW]; this conv's Cin channels land at input-channel offset dw_ci_off.  a.c.n_valid / c_valid: 0 = all channels
@@ -1202,7 +1173,5 @@ extern "C" int sl_wgrad_reduce_multi(const SlWgradReduce* items, int n, sl_strea
   }
   if (m == 0) return 0;
   b.start[m] = blocks; b.n = m;
-  hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b);
-  SL_LAUNCH_CHECK("wgrad_reduce_multi_kernel");
-  return 0;
+  return sl_launch("wgrad_reduce_multi_kernel", wgrad_reduce_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b);
 }

@@ -333,11 +333,6 @@ int sl_wgrad3_run(const SlConvDesc* d, const Wg3Plan& pl, const void* x, const v
   p.trace = g_sl_debug.wgrad3_trace;
   const int tiles = pl.tilesN * pl.tilesC;
   const size_t lds = (size_t)W3_NST * W3_STAGE + (size_t)(pl.ppb + 1) * sizeof(int2);
-  static bool attr_set = false;
-  if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv_wgrad3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
-  hipLaunchKernelGGL(conv_wgrad3_kernel, dim3(tiles * pl.splits), dim3(512), lds, st, p);
-  SL_LAUNCH_CHECK("conv_wgrad3_kernel");
-  hipLaunchKernelGGL(wgrad3_reduce_kernel, dim3(tiles * 32), dim3(576), 0, st, (const float*)workspace, dw, pl.tilesN, pl.tilesC, pl.splits, dw_cin_total, dw_ci_off);
-  SL_LAUNCH_CHECK("wgrad3_reduce_kernel");
-  return 0;
+  SL_TRY(sl_launch("conv_wgrad3_kernel", conv_wgrad3_kernel, dim3(tiles * pl.splits), dim3(512), lds, st, p));
+  return sl_launch("wgrad3_reduce_kernel", wgrad3_reduce_kernel, dim3(tiles * 32), dim3(576), 0, st, (const float*)workspace, dw, pl.tilesN, pl.tilesC, pl.splits, dw_cin_total, dw_ci_off);
 }

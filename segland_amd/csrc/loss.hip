@@ -579,10 +579,7 @@ inline int ce_blocks(long long total) { long long b = (total + 255) / 256; retur
 template <bool WT>
 int launch_ce_fwd(const UpGeom& g, const float* logits, const int64_t* target, int ignore_index, float* partial, hipStream_t stream, CeW<WT> cw) {
   const int nblk = ce_blocks((long long)g.B * g.H * g.W);
-  if (g.K <= KNC) hipLaunchKernelGGL((upsample_ce_fwd_kernel<KNC, WT>), dim3(nblk), dim3(256), 0, stream, g, logits, target, ignore_index, partial, cw);
-  else hipLaunchKernelGGL((upsample_ce_fwd_kernel<KMAXC, WT>), dim3(nblk), dim3(256), 0, stream, g, logits, target, ignore_index, partial, cw);
-  SL_LAUNCH_CHECK("upsample_ce_fwd_kernel");
-  return 0;
+  return sl_launch("upsample_ce_fwd_kernel", g.K <= KNC ? upsample_ce_fwd_kernel<KNC, WT> : upsample_ce_fwd_kernel<KMAXC, WT>, dim3(nblk), dim3(256), 0, stream, g, logits, target, ignore_index, partial, cw);
 }
 
 template <bool WT>
@@ -602,11 +599,7 @@ int launch_ce_bwd(const UpGeom& g, const float* logits, const int64_t* target, c
       ut.KS = cdiv(K, ns);
       const size_t lds = (fixed + (size_t)ut.NYmax * CT * ut.KS + (size_t)ut.NYmax * ut.NXmax * ut.KS) * sizeof(float);
       if (lds > 150 * 1024) continue;
-      static bool opted = false;
-      if (!opted) { (void)hipFuncSetAttribute((const void*)upsample_ce_bwd_tiled_wide_kernel<512, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); opted = true; }
-      hipLaunchKernelGGL((upsample_ce_bwd_tiled_wide_kernel<512, WT>), dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(512), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw);
-      SL_LAUNCH_CHECK("upsample_ce_bwd_tiled_wide_kernel");
-      return 0;
+      return sl_launch("upsample_ce_bwd_tiled_wide_kernel", upsample_ce_bwd_tiled_wide_kernel<512, WT>, dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(512), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw);
     }
   } else if (g.sy > 0.f && g.sx > 0.f && g_sl_debug.ce_tiled) {
     UpTile ut;
@@ -614,20 +607,14 @@ int launch_ce_bwd(const UpGeom& g, const float* logits, const int64_t* target, c
     ut.NXmax = (int)ceilf((float)(CT + 1) / g.sx) + 3; if (ut.NXmax > W) ut.NXmax = W;
     const size_t lds = ((size_t)(CT + 2) * (CT + 2) * K + (3 + CT) * (ut.NYmax + ut.NXmax) + (size_t)ut.NYmax * CT * K + (size_t)ut.NYmax * ut.NXmax * K + wl) * sizeof(float);
     if (lds <= 150 * 1024) {
-      static size_t attr = 0;
 #ifndef SL_UPCE_NT
 #define SL_UPCE_NT 512      // threads per block of the tiled kernel (A/B build: 256)
 #endif
-      if (lds > attr) { (void)hipFuncSetAttribute((const void*)upsample_ce_bwd_tiled_kernel<SL_UPCE_NT, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); attr = 150 * 1024; }
-      hipLaunchKernelGGL((upsample_ce_bwd_tiled_kernel<SL_UPCE_NT, WT>), dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(SL_UPCE_NT), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw);
-      SL_LAUNCH_CHECK("upsample_ce_bwd_tiled_kernel");
-      return 0;
+      return sl_launch("upsample_ce_bwd_tiled_kernel", upsample_ce_bwd_tiled_kernel<SL_UPCE_NT, WT>, dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(SL_UPCE_NT), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw);
     }
   }
-  if (K <= KNC) hipLaunchKernelGGL((upsample_ce_bwd_kernel<KNC, WT>), dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, stream, g, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw);
-  else hipLaunchKernelGGL((upsample_ce_bwd_kernel<KMAXC, WT>), dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, stream, g, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw);
-  SL_LAUNCH_CHECK("upsample_ce_bwd_kernel");
-  return 0;
+  return sl_launch("upsample_ce_bwd_kernel", K <= KNC ? upsample_ce_bwd_kernel<KNC, WT> : upsample_ce_bwd_kernel<KMAXC, WT>, dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, stream, g, logits, target,
+                   loss_and_count, gscale, ignore_index, dlogits, cw);
 }
 
 inline CeW<true> make_cew(const float* class_weight, float label_smoothing, int K) {
@@ -658,9 +645,7 @@ extern "C" int sl_upsample_ce_weighted_fwd(const float* logits, const int64_t* t
 
 extern "C" int sl_upsample_ce_finalize(const float* partial, int nblk, float* loss_and_count, sl_stream_t stream) {
   SL_REQUIRE(partial && loss_and_count && nblk > 0, "upsample_ce_finalize: bad args");
-  hipLaunchKernelGGL(upsample_ce_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, nblk, loss_and_count);
-  SL_LAUNCH_CHECK("upsample_ce_finalize_kernel");
-  return 0;
+  return sl_launch("upsample_ce_finalize_kernel", upsample_ce_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, nblk, loss_and_count);
 }
 
 extern "C" int sl_upsample_ce_bwd(const float* logits, const int64_t* target, const float* loss_and_count, const float* gscale,
@@ -688,10 +673,8 @@ extern "C" int sl_pseudo_label(const float* logits, int K2, int h, int w, int64_
   SL_REQUIRE(logits && mask && K2 >= 1 && B > 0, "pseudo_label: bad args");
   SL_REQUIRE(K2 <= KMAXC, "pseudo_label: %d logit channels; this build holds at most %d", K2, KMAXC);
   const UpGeom g = make_up(B, K2, h, w, H, W);
-  if (K2 <= KNC) hipLaunchKernelGGL((upsample_argmax_kernel<true, KNC>), dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, (uint8_t*)nullptr, mask, n_base);
-  else hipLaunchKernelGGL((upsample_argmax_kernel<true, KMAXC>), dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, (uint8_t*)nullptr, mask, n_base);
-  SL_LAUNCH_CHECK("pseudo_label_kernel");
-  return 0;
+  return sl_launch("upsample_argmax_kernel", K2 <= KNC ? upsample_argmax_kernel<true, KNC> : upsample_argmax_kernel<true, KMAXC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream,
+                   g, logits, nullptr, mask, n_base);
 }
 
 extern "C" int sl_upsample_argmax(const float* logits, int B, int K, int h, int w, int H, int W, uint8_t* labels,
@@ -699,75 +682,61 @@ extern "C" int sl_upsample_argmax(const float* logits, int B, int K, int h, int 
   SL_REQUIRE(logits && labels && K >= 1 && B > 0, "upsample_argmax: bad args");
   SL_REQUIRE(K <= KMAXC, "upsample_argmax: %d logit channels; this build holds at most %d", K, KMAXC);
   const UpGeom g = make_up(B, K, h, w, H, W);
-  if (K <= KNC) hipLaunchKernelGGL((upsample_argmax_kernel<false, KNC>), dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, labels, (int64_t*)nullptr, 0);
-  else hipLaunchKernelGGL((upsample_argmax_kernel<false, KMAXC>), dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, labels, (int64_t*)nullptr, 0);
-  SL_LAUNCH_CHECK("upsample_argmax_kernel");
-  return 0;
+  return sl_launch("upsample_argmax_kernel", K <= KNC ? upsample_argmax_kernel<false, KNC> : upsample_argmax_kernel<false, KMAXC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream,
+                   g, logits, labels, nullptr, 0);
 }
 
 extern "C" int sl_upsample_logits(const float* logits, int B, int K, int h, int w, int H, int W, float* out, sl_stream_t stream) {
   SL_REQUIRE(logits && out && K >= 1 && B > 0, "upsample_logits: bad args");
   SL_REQUIRE(K <= KMAXC, "upsample_logits: %d logit channels; this build holds at most %d", K, KMAXC);
   const UpGeom g = make_up(B, K, h, w, H, W);
-  if (K <= KNC) hipLaunchKernelGGL(upsample_logits_kernel<KNC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, out);
-  else hipLaunchKernelGGL(upsample_logits_kernel<KMAXC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, out);
-  SL_LAUNCH_CHECK("upsample_logits_kernel");
-  return 0;
+  return sl_launch("upsample_logits_kernel", K <= KNC ? upsample_logits_kernel<KNC> : upsample_logits_kernel<KMAXC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, out);
 }
 
 extern "C" int sl_fuse_argmax(const void* mats_dev, int n_models, int K, long long hw, uint8_t* labels, sl_stream_t stream) {
   SL_REQUIRE(mats_dev && labels && n_models >= 1 && K >= 1 && K <= 255 && hw > 0, "fuse_argmax: bad args");
-  hipLaunchKernelGGL(fuse_argmax_kernel, dim3(ce_blocks(hw)), dim3(256), 0, (hipStream_t)stream, (const float* const*)mats_dev, n_models, K, hw, labels);
-  SL_LAUNCH_CHECK("fuse_argmax_kernel");
-  return 0;
+  return sl_launch("fuse_argmax_kernel", fuse_argmax_kernel, dim3(ce_blocks(hw)), dim3(256), 0, (hipStream_t)stream, (const float* const*)mats_dev, n_models, K, hw, labels);
 }
 
 extern "C" int sl_iou_hist(const uint8_t* pred, const int64_t* target, long long n, int K, int ignore_index, long long* hist,
                            sl_stream_t stream) {
   SL_REQUIRE(pred && target && hist && n > 0 && K >= 1 && K <= 256, "iou_hist: bad args");
-  hipLaunchKernelGGL(iou_hist_kernel, dim3(ce_blocks(n)), dim3(256), 0, (hipStream_t)stream, pred, target, n, K, ignore_index, (unsigned long long*)hist);
-  SL_LAUNCH_CHECK("iou_hist_kernel");
-  return 0;
+  return sl_launch("iou_hist_kernel", iou_hist_kernel, dim3(ce_blocks(n)), dim3(256), 0, (hipStream_t)stream, pred, target, n, K, ignore_index, (unsigned long long*)hist);
 }
 
 extern "C" int sl_confusion_matrix(const uint8_t* pred, const int64_t* target, long long n, int K, int ignore_index, long long* cm,
                                    sl_stream_t stream) {
   SL_REQUIRE(pred && target && cm && n > 0 && K >= 1 && K <= 64, "confusion_matrix: bad args");
-  hipLaunchKernelGGL(confusion_kernel, dim3(ce_blocks(n)), dim3(256), (size_t)K * K * sizeof(unsigned), (hipStream_t)stream, pred, target, n, K, ignore_index,
-                     (unsigned long long*)cm);
-  SL_LAUNCH_CHECK("confusion_kernel");
-  return 0;
+  return sl_launch("confusion_kernel", confusion_kernel, dim3(ce_blocks(n)), dim3(256), (size_t)K * K * sizeof(unsigned), (hipStream_t)stream, pred, target, n, K, ignore_index,
+                   (unsigned long long*)cm);
 }
 
 extern "C" int sl_masked_avg_pool(int dtype, const void* feature, const float* mask, int B, int h, int w, int C, int H, int W,
                                   float* proto, sl_stream_t stream) {
   SL_REQUIRE(feature && mask && proto && B > 0 && C > 0, "masked_avg_pool: bad args");
   const float sy = ac1_scale(H, h), sx = ac1_scale(W, w);
-  if (dtype == SL_BF16) hipLaunchKernelGGL(masked_avg_pool_kernel<bf16_t>, dim3(cdiv(C, 64)), dim3(64), 0, (hipStream_t)stream, (const bf16_t*)feature, mask, B, h, w, C, H, W, sy, sx, proto);
-  else if (dtype == SL_F32) hipLaunchKernelGGL(masked_avg_pool_kernel<float>, dim3(cdiv(C, 64)), dim3(64), 0, (hipStream_t)stream, (const float*)feature, mask, B, h, w, C, H, W, sy, sx, proto);
-  else SL_REQUIRE(false, "masked_avg_pool: bad dtype");
-  SL_LAUNCH_CHECK("masked_avg_pool_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "masked_avg_pool", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("masked_avg_pool_kernel", masked_avg_pool_kernel<T>, dim3(cdiv(C, 64)), dim3(64), 0, (hipStream_t)stream, (const T*)feature, mask, B, h, w, C, H, W, sy, sx, proto);
+  });
 }
 
 extern "C" int sl_nhwc_to_nchw_f32(int dtype, const void* src, float* dst, int B, int H, int W, int C, sl_stream_t stream) {
   SL_REQUIRE(src && dst && B > 0, "nhwc_to_nchw: bad args");
   const long long total = (long long)B * H * W * C;
   const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  if (dtype == SL_BF16) hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, dst, B, H * W, C);
-  else if (dtype == SL_F32) hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)src, dst, B, H * W, C);
-  else SL_REQUIRE(false, "nhwc_to_nchw: bad dtype");
-  SL_LAUNCH_CHECK("nhwc_to_nchw_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "nhwc_to_nchw", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("nhwc_to_nchw_kernel", nhwc_to_nchw_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)src, dst, B, H * W, C);
+  });
 }
 
 extern "C" int sl_nchw_f32_to_nhwc(int dtype, const float* src, void* dst, int B, int H, int W, int C, sl_stream_t stream) {
   SL_REQUIRE(src && dst && B > 0, "nchw_to_nhwc: bad args");
   const long long total = (long long)B * H * W * C;
   const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  if (dtype == SL_BF16) hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, B, H * W, C);
-  else if (dtype == SL_F32) hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, (float*)dst, B, H * W, C);
-  else SL_REQUIRE(false, "nchw_to_nhwc: bad dtype");
-  SL_LAUNCH_CHECK("nchw_to_nhwc_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "nchw_to_nhwc", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("nchw_to_nhwc_kernel", nchw_to_nhwc_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, (T*)dst, B, H * W, C);
+  });
 }

@@ -66,10 +66,8 @@ extern "C" int sl_adamw_multi(const void* table_dev, int n, long long total_chun
   SL_REQUIRE(table_dev && n > 0 && total_chunks > 0 && (repeat == 1 || repeat == 2), "adamw_multi: bad args");
   SL_REQUIRE(bias_correction1 > 0.f && bias_correction2_sqrt > 0.f, "adamw_multi: bias corrections must be positive (step >= 1)");
   const int blocks = (int)(total_chunks < 8192 ? total_chunks : 8192);
-  hipLaunchKernelGGL(adamw_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const AdamEntry*)table_dev, n, total_chunks, beta1, beta2, eps,
-                     bias_correction1, bias_correction2_sqrt, bias_correction1_next, bias_correction2_sqrt_next, repeat, grad_scale, (const float*)nullptr);
-  SL_LAUNCH_CHECK("adamw_multi_kernel");
-  return 0;
+  return sl_launch("adamw_multi_kernel", adamw_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const AdamEntry*)table_dev, n, total_chunks, beta1, beta2, eps,
+                   bias_correction1, bias_correction2_sqrt, bias_correction1_next, bias_correction2_sqrt_next, repeat, grad_scale, (const float*)nullptr);
 }
 
 // The same step with every step-dependent scalar in DEVICE memory, so that the launch can sit in a captured HIP graph and be replayed:
@@ -79,10 +77,8 @@ extern "C" int sl_adamw_multi_dev(const void* table_dev, int n, long long total_
                                   const float* hyper_dev, int repeat, const float* grad_scale, sl_stream_t stream) {
   SL_REQUIRE(table_dev && hyper_dev && n > 0 && total_chunks > 0 && (repeat == 1 || repeat == 2), "adamw_multi_dev: bad args");
   const int blocks = (int)(total_chunks < 8192 ? total_chunks : 8192);
-  hipLaunchKernelGGL(adamw_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const AdamEntry*)table_dev, n, total_chunks, beta1, beta2, eps,
-                     1.f, 1.f, 1.f, 1.f, repeat, grad_scale, hyper_dev);
-  SL_LAUNCH_CHECK("adamw_multi_kernel");
-  return 0;
+  return sl_launch("adamw_multi_kernel", adamw_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const AdamEntry*)table_dev, n, total_chunks, beta1, beta2, eps,
+                   1.f, 1.f, 1.f, 1.f, repeat, grad_scale, hyper_dev);
 }
 
 
@@ -120,9 +116,7 @@ __global__ void store_floats_kernel(float* __restrict__ dst, int n, FloatPack pk
 extern "C" int sl_sgd_multi(const void* table_dev, int n, long long total_chunks, float momentum, const float* hyper_dev, const float* grad_scale, sl_stream_t stream) {
   SL_REQUIRE(table_dev && n > 0 && total_chunks > 0 && momentum >= 0.f, "sgd_multi: bad args");
   const int blocks = (int)(total_chunks < 4096 ? total_chunks : 4096);
-  hipLaunchKernelGGL(sgd_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const AdamEntry*)table_dev, n, total_chunks, momentum, grad_scale, hyper_dev);
-  SL_LAUNCH_CHECK("sgd_multi_kernel");
-  return 0;
+  return sl_launch("sgd_multi_kernel", sgd_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const AdamEntry*)table_dev, n, total_chunks, momentum, grad_scale, hyper_dev);
 }
 
 // up to 16 floats into device memory as KERNEL ARGUMENTS (no host -> device copy: a small upload in front of a graph launch sat on the critical path of every step,
@@ -131,9 +125,7 @@ extern "C" int sl_store_floats(float* dst_dev, int n, const float* values_host, 
   SL_REQUIRE(dst_dev && values_host && n >= 1 && n <= 16, "store_floats: 1..16 values");
   FloatPack pk;
   for (int i = 0; i < 16; ++i) pk.v[i] = i < n ? values_host[i] : 0.f;
-  hipLaunchKernelGGL(store_floats_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, dst_dev, n, pk);
-  SL_LAUNCH_CHECK("store_floats_kernel");
-  return 0;
+  return sl_launch("store_floats_kernel", store_floats_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, dst_dev, n, pk);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------
@@ -161,9 +153,7 @@ __global__ __launch_bounds__(256) void copy2d_multi_kernel(const CopyEntry* __re
 extern "C" int sl_copy2d_multi(const void* table_dev, int n, long long total_chunks, sl_stream_t stream) {
   SL_REQUIRE(table_dev && n > 0 && total_chunks > 0, "copy2d_multi: bad args");
   const int blocks = (int)(total_chunks < 4096 ? total_chunks : 4096);
-  hipLaunchKernelGGL(copy2d_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const CopyEntry*)table_dev, n, total_chunks);
-  SL_LAUNCH_CHECK("copy2d_multi_kernel");
-  return 0;
+  return sl_launch("copy2d_multi_kernel", copy2d_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const CopyEntry*)table_dev, n, total_chunks);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------
@@ -185,9 +175,7 @@ __global__ __launch_bounds__(256) void relpos_gather_multi_kernel(const RelGathe
 
 extern "C" int sl_relpos_gather_multi(const void* table_dev, int n, sl_stream_t stream) {
   SL_REQUIRE(table_dev && n > 0, "relpos_gather_multi: bad args");
-  hipLaunchKernelGGL(relpos_gather_multi_kernel, dim3(4 * n), dim3(256), 0, (hipStream_t)stream, (const RelGatherEntry*)table_dev);
-  SL_LAUNCH_CHECK("relpos_gather_multi_kernel");
-  return 0;
+  return sl_launch("relpos_gather_multi_kernel", relpos_gather_multi_kernel, dim3(4 * n), dim3(256), 0, (hipStream_t)stream, (const RelGatherEntry*)table_dev);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------
@@ -234,13 +222,9 @@ __global__ __launch_bounds__(1024) void grad_norm_finalize_kernel(const float* _
 
 extern "C" int sl_grad_sqnorm_multi(const SlNormBatch* batch, float* partial, sl_stream_t stream) {
   SL_REQUIRE(batch && partial && batch->n > 0 && batch->n <= SL_NORM_MAX && batch->chunk0[0] == 0 && batch->chunk0[batch->n] > 0, "grad_sqnorm_multi: bad batch");
-  hipLaunchKernelGGL(grad_sqnorm_multi_kernel, dim3(batch->chunk0[batch->n]), dim3(256), 0, (hipStream_t)stream, *batch, partial);
-  SL_LAUNCH_CHECK("grad_sqnorm_multi_kernel");
-  return 0;
+  return sl_launch("grad_sqnorm_multi_kernel", grad_sqnorm_multi_kernel, dim3(batch->chunk0[batch->n]), dim3(256), 0, (hipStream_t)stream, *batch, partial);
 }
 extern "C" int sl_grad_norm_finalize(const float* partial, int nchunks, float max_norm, float inv_div, float* out, sl_stream_t stream) {
   SL_REQUIRE(partial && out && nchunks > 0 && max_norm > 0.f && inv_div > 0.f, "grad_norm_finalize: bad args");
-  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, partial, nchunks, max_norm, inv_div, out);
-  SL_LAUNCH_CHECK("grad_norm_finalize_kernel");
-  return 0;
+  return sl_launch("grad_norm_finalize_kernel", grad_norm_finalize_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, partial, nchunks, max_norm, inv_div, out);
 }

@@ -760,26 +760,14 @@ extern "C" int sl_pop_decompose_fwd(int dtype, const void* feats, const float* S
   // 16 rows per block (four per wave) until 2048 blocks: every block first brings the prototypes (up to 32 KB) into the LDS and its registers, which four rows per block
   // (2048 blocks for the fine-tune pair's 8 192 rows: 60 us) do not repay; from 32 768 rows on the cap binds and nothing changes
   const int blocks = row_blocks(R * 4, 2048);
-  if (Kt > KCH) {          // wide head: chunked kernel, every prototype row resident (64 KiB at 512 channels: exactly the default allowance, the opt-in is a formality)
-    const size_t wlds = (size_t)KMAXP * C * sizeof(float);
-    if (int e = pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) {
-          using T = decltype(t);
-          auto kern = pop_decompose_fwd_wide_kernel<T, decltype(nv)::value, decltype(lpr)::value>;
-          static bool opted = false;        // per instantiation
-          if (!opted) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds); opted = true; }
-          hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), wlds, st, (const T*)feats, S, Kt, proj, (T*)bg, R, C);
-          return 0; })) return e;
-    SL_LAUNCH_CHECK("pop_decompose_fwd_wide_kernel");
-    return 0;
-  }
-  const size_t lds = (size_t)KCH * C * sizeof(float);
-  if (int e = pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) {
-        using T = decltype(t);
-        if (Kt <= 8) hipLaunchKernelGGL((pop_decompose_fwd_kernel<T, decltype(nv)::value, decltype(lpr)::value, 8>), dim3(blocks), dim3(256), lds, st, (const T*)feats, S, Kt, proj, (T*)bg, R, C);
-        else hipLaunchKernelGGL((pop_decompose_fwd_kernel<T, decltype(nv)::value, decltype(lpr)::value, 16>), dim3(blocks), dim3(256), lds, st, (const T*)feats, S, Kt, proj, (T*)bg, R, C);
-        return 0; })) return e;
-  SL_LAUNCH_CHECK("pop_decompose_fwd_kernel");
-  return 0;
+  return pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) -> int {
+    using T = decltype(t);
+    constexpr int NV = decltype(nv)::value, LPR = decltype(lpr)::value;
+    if (Kt > KCH)          // wide head: chunked kernel, every prototype row resident (64 KiB at 512 channels: exactly the default allowance)
+      return sl_launch("pop_decompose_fwd_wide_kernel", pop_decompose_fwd_wide_kernel<T, NV, LPR>, dim3(blocks), dim3(256), (size_t)KMAXP * C * sizeof(float), st, (const T*)feats, S, Kt, proj, (T*)bg, R, C);
+    return sl_launch("pop_decompose_fwd_kernel", Kt <= 8 ? pop_decompose_fwd_kernel<T, NV, LPR, 8> : pop_decompose_fwd_kernel<T, NV, LPR, 16>, dim3(blocks), dim3(256), (size_t)KCH * C * sizeof(float), st,
+                     (const T*)feats, S, Kt, proj, (T*)bg, R, C);
+  });
 }
 
 
@@ -800,9 +788,7 @@ extern "C" int sl_pop_proto_fwd(const float* Ea, int Ka, const float* Eb, int Kb
   SL_REQUIRE(Ea && Sa && inv_norm && G && orth && Ka >= 1 && Kb >= 0 && Ka + Kb <= PP_KMAX && C > 0 && (Kb == 0 || (Eb && Sb)), "pop_proto_fwd: bad args");
   const size_t lds = ((size_t)(Ka + Kb) * C + (size_t)Ka * (Ka + Kb)) * sizeof(float);
   SL_REQUIRE(pp_fits(Ka, Kb, C), "pop_proto_fwd: %d prototypes of %d channels do not fit one block (forward + backward; sl_pop_proto_ok)", Ka + Kb, C);
-  hipLaunchKernelGGL(pop_proto_fwd_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, Ea, Ka, Eb, Kb, C, Sa, Sb, inv_norm, G, orth);
-  SL_LAUNCH_CHECK("pop_proto_fwd_kernel");
-  return 0;
+  return sl_launch("pop_proto_fwd_kernel", pop_proto_fwd_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, Ea, Ka, Eb, Kb, C, Sa, Sb, inv_norm, G, orth);
 }
 
 extern "C" int sl_pop_proto_bwd(const float* Sa, int Ka, const float* Sb, int Kb, int C, const float* inv_norm, const float* G, const float* dSa,
@@ -810,31 +796,25 @@ extern "C" int sl_pop_proto_bwd(const float* Sa, int Ka, const float* Sb, int Kb
   SL_REQUIRE(Sa && inv_norm && G && Ka >= 1 && Kb >= 0 && Ka + Kb <= PP_KMAX && C > 0 && (Kb == 0 || Sb), "pop_proto_bwd: bad args");
   const size_t lds = 2 * (size_t)(Ka + Kb) * C * sizeof(float);
   SL_REQUIRE(pp_fits(Ka, Kb, C), "pop_proto_bwd: %d prototypes of %d channels do not fit one block (sl_pop_proto_ok)", Ka + Kb, C);
-  hipLaunchKernelGGL(pop_proto_bwd_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, Sa, Ka, Sb, Kb, C, inv_norm, G, dSa, dSb, dorth, dEa, dEb);
-  SL_LAUNCH_CHECK("pop_proto_bwd_kernel");
-  return 0;
+  return sl_launch("pop_proto_bwd_kernel", pop_proto_bwd_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, Sa, Ka, Sb, Kb, C, inv_norm, G, dSa, dSb, dorth, dEa, dEb);
 }
 
 extern "C" int sl_pop_proto_rows(int dtype, const float* S, int Kt, int C, void* dst, sl_stream_t stream) {
   SL_REQUIRE(S && dst && Kt >= 1 && C > 0, "pop_proto_rows: bad args");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SL_BF16) hipLaunchKernelGGL(pop_proto_rows_kernel<bf16_t>, dim3(cdiv(Kt * C, 256)), dim3(256), 0, st, S, Kt, C, (bf16_t*)dst);
-  else if (dtype == SL_F32) hipLaunchKernelGGL(pop_proto_rows_kernel<float>, dim3(cdiv(Kt * C, 256)), dim3(256), 0, st, S, Kt, C, (float*)dst);
-  else SL_REQUIRE(false, "pop_proto_rows: bad dtype");
-  SL_LAUNCH_CHECK("pop_proto_rows_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "pop_proto_rows", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("pop_proto_rows_kernel", pop_proto_rows_kernel<T>, dim3(cdiv(Kt * C, 256)), dim3(256), 0, (hipStream_t)stream, S, Kt, C, (T*)dst);
+  });
 }
 
 extern "C" int sl_rowdot_fwd(int dtype, const void* h, const float* w, float* z, long long R, int C, sl_stream_t stream) {
   SL_REQUIRE(h && w && z && R > 0, "rowdot_fwd: bad args");
   hipStream_t st = (hipStream_t)stream;
   const int blocks = row_blocks(R * 16, 2048);
-  if (int e = pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) {
-        using T = decltype(t);
-        hipLaunchKernelGGL((rowdot_fwd_kernel<T, decltype(nv)::value, decltype(lpr)::value>), dim3(blocks), dim3(256), 0, st, (const T*)h, w, z, R, C);
-        return 0; })) return e;
-  SL_LAUNCH_CHECK("rowdot_fwd_kernel");
-  return 0;
+  return pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) -> int {
+    using T = decltype(t);
+    return sl_launch("rowdot_fwd_kernel", rowdot_fwd_kernel<T, decltype(nv)::value, decltype(lpr)::value>, dim3(blocks), dim3(256), 0, st, (const T*)h, w, z, R, C);
+  });
 }
 
 extern "C" int sl_rowdot_bwd_rows(long long R, int C) { (void)C; return row_blocks(R, 512); }
@@ -846,12 +826,10 @@ extern "C" int sl_rowdot_bwd(int dtype, const void* h, const float* w, const flo
   const int nblk = row_blocks(R, 512);
   const long long rpb = (R + nblk - 1) / nblk;
   const size_t lds = 4 * (size_t)C * sizeof(float);
-  if (int e = pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) {
-        using T = decltype(t);
-        hipLaunchKernelGGL((rowdot_bwd_kernel<T, decltype(nv)::value, decltype(lpr)::value>), dim3(nblk), dim3(256), lds, st, (const T*)h, w, dz, (T*)dh, partial, R, C, rpb);
-        return 0; })) return e;
-  SL_LAUNCH_CHECK("rowdot_bwd_kernel");
-  return 0;
+  return pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) -> int {
+    using T = decltype(t);
+    return sl_launch("rowdot_bwd_kernel", rowdot_bwd_kernel<T, decltype(nv)::value, decltype(lpr)::value>, dim3(nblk), dim3(256), lds, st, (const T*)h, w, dz, (T*)dh, partial, R, C, rpb);
+  });
 }
 
 
@@ -864,18 +842,15 @@ extern "C" int sl_colsum_rows_partial(int dtype, const void* x, long long rows, 
   SL_REQUIRE(x && partial && rows > 0 && C > 0 && (dtype == SL_BF16 ? C % 8 == 0 : C % 4 == 0), "colsum_rows_partial: bad args");
   const long long ch = sl_colsum_rows_chunk(rows, C, dtype == SL_BF16 ? 2 : 4);
   const int nblk = (int)((rows + ch - 1) / ch);
-  if (dtype == SL_BF16) hipLaunchKernelGGL(colsum_rows_partial_kernel<bf16_t>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, rows, C, ch, partial);
-  else if (dtype == SL_F32) hipLaunchKernelGGL(colsum_rows_partial_kernel<float>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const float*)x, rows, C, ch, partial);
-  else SL_REQUIRE(false, "colsum_rows_partial: bad dtype");
-  SL_LAUNCH_CHECK("colsum_rows_partial_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "colsum_rows_partial", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("colsum_rows_partial_kernel", colsum_rows_partial_kernel<T>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const T*)x, rows, C, ch, partial);
+  });
 }
 
 extern "C" int sl_colsum_finalize(const float* partial, int nblk, int C, float* out, sl_stream_t stream) {
   SL_REQUIRE(partial && out && nblk > 0 && C > 0, "colsum_finalize: bad args");
-  hipLaunchKernelGGL(colsum_finalize_kernel, dim3(cdiv(C, 64)), dim3(1024), 0, (hipStream_t)stream, partial, nblk, C, out);
-  SL_LAUNCH_CHECK("colsum_finalize_kernel");
-  return 0;
+  return sl_launch("colsum_finalize_kernel", colsum_finalize_kernel, dim3(cdiv(C, 64)), dim3(1024), 0, (hipStream_t)stream, partial, nblk, C, out);
 }
 
 extern "C" int sl_colsum_finalize_multi(const SlColsumBatch* batch, sl_stream_t stream) {
@@ -889,23 +864,17 @@ extern "C" int sl_colsum_finalize_multi(const SlColsumBatch* batch, sl_stream_t 
     blocks += cdiv(batch->C[i], 64);
   }
   b.first[batch->n] = blocks;
-  hipLaunchKernelGGL(colsum_finalize_multi_kernel, dim3(blocks), dim3(1024), 0, (hipStream_t)stream, b);
-  SL_LAUNCH_CHECK("colsum_finalize_multi_kernel");
-  return 0;
+  return sl_launch("colsum_finalize_multi_kernel", colsum_finalize_multi_kernel, dim3(blocks), dim3(1024), 0, (hipStream_t)stream, b);
 }
 
 extern "C" int sl_colsum_f64(const float* partial, int nblk, int C, double* out, sl_stream_t stream) {
   SL_REQUIRE(partial && out && nblk > 0 && C > 0, "colsum_f64: bad args");
-  hipLaunchKernelGGL(colsum_f64_kernel, dim3(cdiv(C, 64)), dim3(1024), 0, (hipStream_t)stream, partial, nblk, C, out);
-  SL_LAUNCH_CHECK("colsum_f64_kernel");
-  return 0;
+  return sl_launch("colsum_f64_kernel", colsum_f64_kernel, dim3(cdiv(C, 64)), dim3(1024), 0, (hipStream_t)stream, partial, nblk, C, out);
 }
 
 extern "C" int sl_f64_split(const double* totals, int n, float* hi_lo, sl_stream_t stream) {
   SL_REQUIRE(totals && hi_lo && n > 0, "f64_split: bad args");
-  hipLaunchKernelGGL(f64_split_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, totals, n, hi_lo);
-  SL_LAUNCH_CHECK("f64_split_kernel");
-  return 0;
+  return sl_launch("f64_split_kernel", f64_split_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, totals, n, hi_lo);
 }
 
 extern "C" int sl_pop_combine_fwd(const float* proj, const float* z_bg, const float* a, const float* b, int Kt, float* preds,
@@ -914,9 +883,7 @@ extern "C" int sl_pop_combine_fwd(const float* proj, const float* z_bg, const fl
   SL_REQUIRE(Kt <= KMAXP, "pop_combine_fwd: %d prototypes; this build holds at most %d", Kt, KMAXP);
   const long long R = (long long)B * N;
   const int blocks = (int)((R + 255) / 256 < 4096 ? (R + 255) / 256 : 4096);
-  hipLaunchKernelGGL(pop_combine_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, proj, z_bg, a, b, Kt, preds, B, N);
-  SL_LAUNCH_CHECK("pop_combine_fwd_kernel");
-  return 0;
+  return sl_launch("pop_combine_fwd_kernel", pop_combine_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, proj, z_bg, a, b, Kt, preds, B, N);
 }
 
 extern "C" int sl_pop_combine_bwd_rows(int B, int N) { return row_blocks((long long)B * N / 4, 256); }
@@ -928,10 +895,8 @@ extern "C" int sl_pop_combine_bwd(const float* dpreds, const float* proj, const 
   const long long R = (long long)B * N;
   const int nblk = sl_pop_combine_bwd_rows(B, N);
   const long long rpb = (R + nblk - 1) / nblk;
-  if (Kt <= KCH) hipLaunchKernelGGL(pop_combine_bwd_kernel<KCH>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, dpreds, proj, a, b, Kt, dz_bg, dproj, dab_partial, B, N, rpb);
-  else hipLaunchKernelGGL(pop_combine_bwd_kernel<KMAXP>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, dpreds, proj, a, b, Kt, dz_bg, dproj, dab_partial, B, N, rpb);
-  SL_LAUNCH_CHECK("pop_combine_bwd_kernel");
-  return 0;
+  return sl_launch("pop_combine_bwd_kernel", Kt <= KCH ? pop_combine_bwd_kernel<KCH> : pop_combine_bwd_kernel<KMAXP>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, dpreds, proj, a, b, Kt, dz_bg, dproj,
+                   dab_partial, B, N, rpb);
 }
 
 static int dec_bwd_cap() { return 1024; }     // measured 180 / 160 / 161 us for 512 / 1024 / 2048 blocks at 65 536 rows
@@ -949,31 +914,12 @@ extern "C" int sl_pop_decompose_bwd(int dtype, const void* dg, const void* feats
   hipStream_t st = (hipStream_t)stream;
   const int nblk = dec_bwd_blocks(R);
   const long long rpb = (R + nblk - 1) / nblk;
-  if (Kt > KCH) {          // wide head: one pass over the block's rows per chunk of KCH prototypes
-    const size_t lds = (size_t)KMAXP * C * sizeof(float);
-    if (int e = pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) {
-          using T = decltype(t);
-          auto kern = pop_decompose_bwd_wide_kernel<T, decltype(nv)::value, decltype(lpr)::value>;
-          static bool opted = false;        // per instantiation
-          if (!opted) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); opted = true; }
-          hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, (const T*)dg, (const T*)feats, S, proj, dproj, Kt, (T*)dq, dS_partial, R, C, rpb);
-          return 0; })) return e;
-    SL_LAUNCH_CHECK("pop_decompose_bwd_wide_kernel");
-    return 0;
-  }
-  if (Kt <= 8) {
-    const size_t lds = 8 * (size_t)C * sizeof(float);
-    if (int e = pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) {
-          using T = decltype(t);
-          hipLaunchKernelGGL((pop_decompose_bwd_kernel<T, decltype(nv)::value, 8, decltype(lpr)::value>), dim3(nblk), dim3(256), lds, st, (const T*)dg, (const T*)feats, S, proj, dproj, Kt, (T*)dq, dS_partial, R, C, rpb);
-          return 0; })) return e;
-  } else {
-    const size_t lds = 16 * (size_t)C * sizeof(float);
-    if (int e = pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) {
-          using T = decltype(t);
-          hipLaunchKernelGGL((pop_decompose_bwd_kernel<T, decltype(nv)::value, 16, decltype(lpr)::value>), dim3(nblk), dim3(256), lds, st, (const T*)dg, (const T*)feats, S, proj, dproj, Kt, (T*)dq, dS_partial, R, C, rpb);
-          return 0; })) return e;
-  }
-  SL_LAUNCH_CHECK("pop_decompose_bwd_kernel");
-  return 0;
+  return pop_dispatch(dtype, C, [&](auto t, auto nv, auto lpr) -> int {
+    using T = decltype(t);
+    constexpr int NV = decltype(nv)::value, LPR = decltype(lpr)::value;
+    // wide head: one pass over the block's rows per chunk of KCH prototypes, every prototype row resident; otherwise 8 or 16 rows
+    const auto kern = Kt > KCH ? pop_decompose_bwd_wide_kernel<T, NV, LPR> : Kt <= 8 ? pop_decompose_bwd_kernel<T, NV, 8, LPR> : pop_decompose_bwd_kernel<T, NV, 16, LPR>;
+    const size_t lds = (size_t)(Kt > KCH ? KMAXP : Kt <= 8 ? 8 : 16) * C * sizeof(float);
+    return sl_launch(Kt > KCH ? "pop_decompose_bwd_wide_kernel" : "pop_decompose_bwd_kernel", kern, dim3(nblk), dim3(256), lds, st, (const T*)dg, (const T*)feats, S, proj, dproj, Kt, (T*)dq, dS_partial, R, C, rpb);
+  });
 }

@@ -641,19 +641,15 @@ extern "C" int sl_ppm_pool_fwd(const SlPpmDesc* d, const void* x, float* pooled,
   if (workspace_bytes < need) { sl_set_error("ppm_pool_fwd: workspace %zu < %zu", workspace_bytes, need); return SL_EWORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
   float* cells = (float*)workspace;
-  if (d->dtype == SL_BF16) {
-    const long long cell_vecs = (long long)g.B * g.ncy * g.ncx * (g.C / 8);
-    if (cell_vecs < 256 * 1024)      // fewer than 1024 blocks of the one-thread-per-cell kernel (batch < 16 at 64 x 64 x 2048): rows of a cell in parallel
-      hipLaunchKernelGGL(ppm_cells_rows_kernel<bf16_t>, dim3((unsigned)(g.B * g.ncy * g.ncx * ((g.C / 8 + 31) / 32))), dim3(256), 0, st, g, (const bf16_t*)x, cells);
-    else
-      hipLaunchKernelGGL(ppm_cells_kernel<bf16_t>, dim3(gs_blocks(cell_vecs)), dim3(256), 0, st, g, (const bf16_t*)x, cells);
-    hipLaunchKernelGGL(ppm_bins_kernel, dim3(gs_blocks((long long)g.rowoff[4] * g.C)), dim3(256), 0, st, g, cells, (float*)pooled);
-  } else if (d->dtype == SL_F32) {
-    hipLaunchKernelGGL(ppm_cells_kernel<float>, dim3(gs_blocks((long long)g.B * g.ncy * g.ncx * g.C / 4)), dim3(256), 0, st, g, (const float*)x, cells);
-    hipLaunchKernelGGL(ppm_bins_kernel, dim3(gs_blocks((long long)g.rowoff[4] * g.C)), dim3(256), 0, st, g, cells, (float*)pooled);
-  } else SL_REQUIRE(false, "ppm_pool_fwd: bad dtype");
-  SL_LAUNCH_CHECK("ppm_pool_fwd");
-  return 0;
+  const long long cell_vecs = (long long)g.B * g.ncy * g.ncx * (g.C / 8);
+  if (d->dtype == SL_BF16 && cell_vecs < 256 * 1024)      // fewer than 1024 blocks of the one-thread-per-cell kernel (batch < 16 at 64 x 64 x 2048): rows of a cell in parallel
+    SL_TRY(sl_launch("ppm_cells_rows_kernel", ppm_cells_rows_kernel<bf16_t>, dim3((unsigned)(g.B * g.ncy * g.ncx * ((g.C / 8 + 31) / 32))), dim3(256), 0, st, g, (const bf16_t*)x, cells));
+  else
+    SL_TRY(sl_by_dtype(d->dtype, "ppm_pool_fwd", [&](auto t) -> int {
+      using T = decltype(t);
+      return sl_launch("ppm_cells_kernel", ppm_cells_kernel<T>, dim3(gs_blocks((long long)g.B * g.ncy * g.ncx * g.C / Vec16<T>::N)), dim3(256), 0, st, g, (const T*)x, cells);
+    }));
+  return sl_launch("ppm_bins_kernel", ppm_bins_kernel, dim3(gs_blocks((long long)g.rowoff[4] * g.C)), dim3(256), 0, st, g, cells, pooled);
 }
 
 extern "C" int sl_ppm_pool_bwd(const SlPpmDesc* d, const float* dpooled, const void* dcat, int cat_pitch, int cat_off, void* dx,
@@ -667,28 +663,21 @@ extern "C" int sl_ppm_pool_bwd(const SlPpmDesc* d, const float* dpooled, const v
   if (workspace_bytes < need) { sl_set_error("ppm_pool_bwd: workspace %zu < %zu", workspace_bytes, need); return SL_EWORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
   float* gcell = (float*)workspace;
-  hipLaunchKernelGGL(ppm_pool_bwd_cells_kernel, dim3(gs_blocks((long long)g.B * g.ncy * g.ncx * g.C)), dim3(256), 0, st, g, (const float*)dpooled, gcell);
-  if (d->dtype == SL_BF16)
-    hipLaunchKernelGGL(ppm_pool_bwd_kernel<bf16_t>, dim3(g.B * g.H), dim3(256), 0, st, g, (const float*)gcell, (const bf16_t*)dcat, cat_pitch, cat_off, (bf16_t*)dx);
-  else if (d->dtype == SL_F32)
-    hipLaunchKernelGGL(ppm_pool_bwd_kernel<float>, dim3(g.B * g.H), dim3(256), 0, st, g, (const float*)gcell, (const float*)dcat, cat_pitch, cat_off, (float*)dx);
-  else SL_REQUIRE(false, "ppm_pool_bwd: bad dtype");
-  SL_LAUNCH_CHECK("ppm_pool_bwd_kernel");
-  return 0;
+  return sl_by_dtype(d->dtype, "ppm_pool_bwd", [&](auto t) -> int {
+    using T = decltype(t);
+    SL_TRY(sl_launch("ppm_pool_bwd_cells_kernel", ppm_pool_bwd_cells_kernel, dim3(gs_blocks((long long)g.B * g.ncy * g.ncx * g.C)), dim3(256), 0, st, g, dpooled, gcell));
+    return sl_launch("ppm_pool_bwd_kernel", ppm_pool_bwd_kernel<T>, dim3(g.B * g.H), dim3(256), 0, st, g, gcell, (const T*)dcat, cat_pitch, cat_off, (T*)dx);
+  });
 }
 
 extern "C" int sl_ppm_upsample_fwd(const SlPpmDesc* d, int Cs, const float* stage, void* priors, sl_stream_t stream) {
   PpmGeom g;
   if (int e = make_geom(d, g)) return e;
   SL_REQUIRE(stage && priors && Cs > 0 && Cs % 8 == 0, "ppm_upsample_fwd: bad args");
-  hipStream_t st = (hipStream_t)stream;
-  if (d->dtype == SL_BF16)
-    hipLaunchKernelGGL(ppm_upsample_fwd_kernel<bf16_t>, dim3(gs_blocks((long long)g.B * g.H * g.W * g.nlevels * Cs / 8)), dim3(256), 0, st, g, Cs, (const float*)stage, (bf16_t*)priors);
-  else if (d->dtype == SL_F32)
-    hipLaunchKernelGGL(ppm_upsample_fwd_kernel<float>, dim3(gs_blocks((long long)g.B * g.H * g.W * g.nlevels * Cs / 4)), dim3(256), 0, st, g, Cs, (const float*)stage, (float*)priors);
-  else SL_REQUIRE(false, "ppm_upsample_fwd: bad dtype");
-  SL_LAUNCH_CHECK("ppm_upsample_fwd_kernel");
-  return 0;
+  return sl_by_dtype(d->dtype, "ppm_upsample_fwd", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("ppm_upsample_fwd_kernel", ppm_upsample_fwd_kernel<T>, dim3(gs_blocks((long long)g.B * g.H * g.W * g.nlevels * Cs / Vec16<T>::N)), dim3(256), 0, (hipStream_t)stream, g, Cs, stage, (T*)priors);
+  });
 }
 
 extern "C" int sl_ppm_upsample_bwd(const SlPpmDesc* d, int Cs, const void* dcat, int cat_pitch, float* dstage, void* workspace,
@@ -701,23 +690,17 @@ extern "C" int sl_ppm_upsample_bwd(const SlPpmDesc* d, int Cs, const void* dcat,
   if (workspace_bytes < need) { sl_set_error("ppm_upsample_bwd: workspace %zu < %zu", workspace_bytes, need); return SL_EWORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
   float* tmp = (float*)workspace;
-  if (d->dtype == SL_BF16) {
-    hipLaunchKernelGGL(ppm_upsample_bwd_x_kernel<bf16_t>, dim3(gs_blocks((long long)g.B * g.H * nlj * Cs / 8)), dim3(256), 0, st, g, Cs, (const bf16_t*)dcat, cat_pitch, tmp, nlj);
-    hipLaunchKernelGGL(ppm_upsample_bwd_y_kernel, dim3(gs_blocks((long long)g.rowoff[4] * Cs)), dim3(256), 0, st, g, Cs, tmp, (float*)dstage, nlj);
-  } else if (d->dtype == SL_F32) {
-    hipLaunchKernelGGL(ppm_upsample_bwd_x_kernel<float>, dim3(gs_blocks((long long)g.B * g.H * nlj * Cs / 4)), dim3(256), 0, st, g, Cs, (const float*)dcat, cat_pitch, tmp, nlj);
-    hipLaunchKernelGGL(ppm_upsample_bwd_y_kernel, dim3(gs_blocks((long long)g.rowoff[4] * Cs)), dim3(256), 0, st, g, Cs, tmp, (float*)dstage, nlj);
-  } else SL_REQUIRE(false, "ppm_upsample_bwd: bad dtype");
-  SL_LAUNCH_CHECK("ppm_upsample_bwd");
-  return 0;
+  SL_TRY(sl_by_dtype(d->dtype, "ppm_upsample_bwd", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("ppm_upsample_bwd_x_kernel", ppm_upsample_bwd_x_kernel<T>, dim3(gs_blocks((long long)g.B * g.H * nlj * Cs / Vec16<T>::N)), dim3(256), 0, st, g, Cs, (const T*)dcat, cat_pitch, tmp, nlj);
+  }));
+  return sl_launch("ppm_upsample_bwd_y_kernel", ppm_upsample_bwd_y_kernel, dim3(gs_blocks((long long)g.rowoff[4] * Cs)), dim3(256), 0, st, g, Cs, tmp, dstage, nlj);
 }
 
 // ---- factorised prior path (see the comment block above ppm_wq_prep_kernel)
 extern "C" int sl_ppm_dwq_scatter(const float* dwq, int N, int Ctot, int Cs, int nlevels, float* dw_oihw, sl_stream_t stream) {
   SL_REQUIRE(dwq && dw_oihw && N > 0 && Cs > 0 && nlevels >= 1 && nlevels * Cs <= Ctot, "ppm_dwq_scatter: bad args");
-  hipLaunchKernelGGL(ppm_dwq_scatter_kernel, dim3(gs_blocks((long long)nlevels * 9 * N * Cs)), dim3(256), 0, (hipStream_t)stream, dwq, N, Ctot, Cs, nlevels, dw_oihw);
-  SL_LAUNCH_CHECK("ppm_dwq_scatter_kernel");
-  return 0;
+  return sl_launch("ppm_dwq_scatter_kernel", ppm_dwq_scatter_kernel, dim3(gs_blocks((long long)nlevels * 9 * N * Cs)), dim3(256), 0, (hipStream_t)stream, dwq, N, Ctot, Cs, nlevels, dw_oihw);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -872,10 +855,10 @@ extern "C" int sl_ppm_rows_gemm_levels(const SlPpmDesc* d, int K, int N, const f
   SL_REQUIRE(ks == 1 || (workspace && workspace_bytes >= (size_t)ks * mm.slab_stride * sizeof(float)), "ppm_rows_gemm: workspace too small");
   mm.x = x; mm.out = ks > 1 ? (float*)workspace : y;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(ppm_rows_gemm_kernel, dim3(N / 64, mtiles, ks), dim3(256), 0, st, mm);
+  SL_TRY(sl_launch("ppm_rows_gemm_kernel", ppm_rows_gemm_kernel, dim3(N / 64, mtiles, ks), dim3(256), 0, st, mm));
   if (ks > 1 || stat_partial)
-    hipLaunchKernelGGL(ppm_rows_finish_kernel, dim3(N / 64, groups), dim3(256), 0, st, (const float*)mm.out, ks, mm.slab_stride, y, N, fin, stat_partial);
-  return (int)hipGetLastError();
+    return sl_launch("ppm_rows_finish_kernel", ppm_rows_finish_kernel, dim3(N / 64, groups), dim3(256), 0, st, mm.out, ks, mm.slab_stride, y, N, fin, stat_partial);
+  return 0;
 }
 
 extern "C" int sl_ppm_rows_gemm(const SlPpmDesc* d, int K, int N, const float* x, const float* w, float* y, float* stat_partial,
@@ -948,9 +931,7 @@ extern "C" int sl_ppm_rows_wgrad(const SlPpmDesc* d, int N, int K, const float* 
     p.dw[l] = dw[l];
     p.row_off[l + 1] = p.row_off[l] + d->B * d->sizes[l] * d->sizes[l];
   }
-  hipLaunchKernelGGL(ppm_rows_wgrad_kernel, dim3(N / 64, K / 64, d->nlevels), dim3(256), 0, (hipStream_t)stream, p);
-  SL_LAUNCH_CHECK("ppm_rows_wgrad_kernel");
-  return 0;
+  return sl_launch("ppm_rows_wgrad_kernel", ppm_rows_wgrad_kernel, dim3(N / 64, K / 64, d->nlevels), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 extern "C" size_t sl_ppm_fact_workspace(const SlPpmDesc* d, int N) {
@@ -968,12 +949,11 @@ extern "C" int sl_ppm_fact_gather(const SlPpmDesc* d, int N, const float* q, voi
   if (workspace_bytes < need) { sl_set_error("ppm_fact_gather: workspace %zu < %zu", workspace_bytes, need); return SL_EWORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
   float* t = (float*)workspace;
-  hipLaunchKernelGGL(ppm_fact_gather1_kernel, dim3(gs_blocks((long long)g.B * g.H * 3 * nlj * N / 4)), dim3(256), 0, st, g, N, q, t, nlj);
-  if (d->dtype == SL_BF16) hipLaunchKernelGGL(ppm_fact_gather2_kernel<bf16_t>, dim3(gs_blocks((long long)g.B * g.H * g.W * N / 8)), dim3(256), 0, st, g, N, t, (bf16_t*)gout, nlj);
-  else if (d->dtype == SL_F32) hipLaunchKernelGGL(ppm_fact_gather2_kernel<float>, dim3(gs_blocks((long long)g.B * g.H * g.W * N / 4)), dim3(256), 0, st, g, N, t, (float*)gout, nlj);
-  else SL_REQUIRE(false, "ppm_fact_gather: bad dtype");
-  SL_LAUNCH_CHECK("ppm_fact_gather");
-  return 0;
+  return sl_by_dtype(d->dtype, "ppm_fact_gather", [&](auto e) -> int {
+    using T = decltype(e);
+    SL_TRY(sl_launch("ppm_fact_gather1_kernel", ppm_fact_gather1_kernel, dim3(gs_blocks((long long)g.B * g.H * 3 * nlj * N / 4)), dim3(256), 0, st, g, N, q, t, nlj));
+    return sl_launch("ppm_fact_gather2_kernel", ppm_fact_gather2_kernel<T>, dim3(gs_blocks((long long)g.B * g.H * g.W * N / Vec16<T>::N)), dim3(256), 0, st, g, N, t, (T*)gout, nlj);
+  });
 }
 
 extern "C" int sl_ppm_fact_scatter(const SlPpmDesc* d, int N, const void* dcb, float* gq, void* workspace, size_t workspace_bytes, sl_stream_t stream) {
@@ -989,20 +969,15 @@ extern "C" int sl_ppm_fact_scatter(const SlPpmDesc* d, int N, const void* dcb, f
   // weight table; anything else takes the two general kernels.  Test hook: sl_debug_ppm_fact_walk(0).
   bool walk = g_sl_debug.ppm_fact_walk && g.W <= 64 && g.H >= 1 && N % 2 == 0;
   for (int l = 0; l < g.nlevels; ++l) walk = walk && g.sizes[l] <= g.W && g.sizes[l] <= g.H;
-  if (walk) {
-    if (d->dtype == SL_BF16) hipLaunchKernelGGL(ppm_fact_scatterA2_kernel<bf16_t>, dim3(g.B * g.H), dim3(256), 0, st, g, N, (const bf16_t*)dcb, sa, nlj);
-    else if (d->dtype == SL_F32) hipLaunchKernelGGL(ppm_fact_scatterA2_kernel<float>, dim3(g.B * g.H), dim3(256), 0, st, g, N, (const float*)dcb, sa, nlj);
-    else SL_REQUIRE(false, "ppm_fact_scatter: bad dtype");
-    hipLaunchKernelGGL(ppm_fact_scatterB2_kernel, dim3(gs_blocks((long long)g.B * 3 * nlj * (N / 2))), dim3(256), 0, st, g, N, sa, gq, nlj);
-    SL_LAUNCH_CHECK("ppm_fact_scatter (walk)");
-    return 0;
-  }
-  if (d->dtype == SL_BF16) hipLaunchKernelGGL(ppm_fact_scatterA_kernel<bf16_t>, dim3(gs_blocks((long long)g.B * g.H * 3 * nlj * N / 8)), dim3(256), 0, st, g, N, (const bf16_t*)dcb, sa, nlj);
-  else if (d->dtype == SL_F32) hipLaunchKernelGGL(ppm_fact_scatterA_kernel<float>, dim3(gs_blocks((long long)g.B * g.H * 3 * nlj * N / 4)), dim3(256), 0, st, g, N, (const float*)dcb, sa, nlj);
-  else SL_REQUIRE(false, "ppm_fact_scatter: bad dtype");
-  hipLaunchKernelGGL(ppm_fact_scatterB_kernel, dim3(gs_blocks((long long)g.rowoff[4] * 9 * N)), dim3(256), 0, st, g, N, sa, gq, nlj);
-  SL_LAUNCH_CHECK("ppm_fact_scatter");
-  return 0;
+  return sl_by_dtype(d->dtype, "ppm_fact_scatter", [&](auto e) -> int {
+    using T = decltype(e);
+    if (walk) {
+      SL_TRY(sl_launch("ppm_fact_scatterA2_kernel", ppm_fact_scatterA2_kernel<T>, dim3(g.B * g.H), dim3(256), 0, st, g, N, (const T*)dcb, sa, nlj));
+      return sl_launch("ppm_fact_scatterB2_kernel", ppm_fact_scatterB2_kernel, dim3(gs_blocks((long long)g.B * 3 * nlj * (N / 2))), dim3(256), 0, st, g, N, sa, gq, nlj);
+    }
+    SL_TRY(sl_launch("ppm_fact_scatterA_kernel", ppm_fact_scatterA_kernel<T>, dim3(gs_blocks((long long)g.B * g.H * 3 * nlj * N / Vec16<T>::N)), dim3(256), 0, st, g, N, (const T*)dcb, sa, nlj));
+    return sl_launch("ppm_fact_scatterB_kernel", ppm_fact_scatterB_kernel, dim3(gs_blocks((long long)g.rowoff[4] * 9 * N)), dim3(256), 0, st, g, N, sa, gq, nlj);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1073,7 +1048,5 @@ extern "C" int sl_ppm_stage_bn_bwd(const SlPpmDesc* d, int C, const float* dy, c
     q.row0[l] = row; row += d->B * d->sizes[l] * d->sizes[l];
   }
   q.row0[d->nlevels] = row;
-  hipLaunchKernelGGL(ppm_stage_bn_bwd_kernel, dim3(d->nlevels * (C / 32)), dim3(32 * SBN_RL), 0, (hipStream_t)stream, dy, y, x, dx, C, q);
-  SL_LAUNCH_CHECK("ppm_stage_bn_bwd_kernel");
-  return 0;
+  return sl_launch("ppm_stage_bn_bwd_kernel", ppm_stage_bn_bwd_kernel, dim3(d->nlevels * (C / 32)), dim3(32 * SBN_RL), 0, (hipStream_t)stream, dy, y, x, dx, C, q);
 }

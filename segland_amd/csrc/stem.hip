@@ -528,21 +528,17 @@ extern "C" size_t sl_stem_conv_fwd_workspace(int dtype) { return dtype == SL_BF1
 extern "C" int sl_stem_conv_fwd(int dtype, const float* img_nchw, const float* w_oihw, void* y, float* stat_partial, int B,
                                 int H, int W, void* workspace, sl_stream_t stream) {
   SL_REQUIRE(img_nchw && w_oihw && y && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "stem_conv_fwd: bad args");
-  const size_t lds = (NTAP * 64 + 3 * PS * PS) * sizeof(float);
   dim3 grid(stem_tiles(B, H, W));
   if (dtype == SL_BF16) {
     SL_REQUIRE(workspace && ((size_t)workspace & 15) == 0, "stem_conv_fwd: bf16 needs the 16-byte aligned workspace of sl_stem_conv_fwd_workspace()");
     uint4* wfrag = (uint4*)workspace;                                           // the weights in MFMA fragment order, rebuilt on every call (20 KiB)
-    hipLaunchKernelGGL(stem_weight_frag_kernel, dim3(cdiv(2 * KSTEPS * 64, 256)), dim3(256), 0, (hipStream_t)stream, w_oihw, wfrag);
+    SL_TRY(sl_launch("stem_weight_frag_kernel", stem_weight_frag_kernel, dim3(cdiv(2 * KSTEPS * 64, 256)), dim3(256), 0, (hipStream_t)stream, w_oihw, wfrag));
     const size_t l2 = 256 * 72 * sizeof(bf16_t) + 4 * 2 * 64 * sizeof(float);   // staging tile + statistic scratch (the patch, 8.4 KB, lives in the tile's place first)
-    hipLaunchKernelGGL(stem_conv_fwd_mfma_kernel, grid, dim3(256), l2, (hipStream_t)stream, img_nchw, (const uint4*)wfrag, (bf16_t*)y, stat_partial, B, H, W);
-    SL_LAUNCH_CHECK("stem_conv_fwd_mfma_kernel");
-    return 0;
+    return sl_launch("stem_conv_fwd_mfma_kernel", stem_conv_fwd_mfma_kernel, grid, dim3(256), l2, (hipStream_t)stream, img_nchw, (const uint4*)wfrag, (bf16_t*)y, stat_partial, B, H, W);
   }
-  if (dtype == SL_F32) hipLaunchKernelGGL(stem_conv_fwd_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, img_nchw, w_oihw, (float*)y, stat_partial, B, H, W);
-  else SL_REQUIRE(false, "stem_conv_fwd: bad dtype");
-  SL_LAUNCH_CHECK("stem_conv_fwd_kernel");
-  return 0;
+  SL_REQUIRE(dtype == SL_F32, "stem_conv_fwd: bad dtype");
+  const size_t lds = (NTAP * 64 + 3 * PS * PS) * sizeof(float);
+  return sl_launch("stem_conv_fwd_kernel", stem_conv_fwd_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, img_nchw, w_oihw, (float*)y, stat_partial, B, H, W);
 }
 
 // ---- BN + ReLU + maxpool and its backward for C channels (C = 64: the 7x7 stem; C = 128: behind the deep stem's conv3, resnet.py:189-190)
@@ -557,21 +553,28 @@ inline int pool_bwd_stat_rows(int B, int Hc, int Wc, int C) {
   return (int)(blocks < 2048 ? blocks : 2048);
 }
 
-template <typename T>
-void launch_pool_fwd(const void* c0, const float* scale, const float* shift, void* pooled, uint8_t* argmax, int B, int Hc, int Wc, int C, hipStream_t st) {
-  const long long total = (long long)B * ((Hc + 1) / 2) * ((Wc + 1) / 2) * (C / Vec16<T>::N);
-  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  if (C == 64) hipLaunchKernelGGL((stem_bn_relu_pool_fwd_kernel<T, 64>), dim3(blocks), dim3(256), 0, st, (const T*)c0, scale, shift, (T*)pooled, argmax, B, Hc, Wc, C);
-  else if (C == 128) hipLaunchKernelGGL((stem_bn_relu_pool_fwd_kernel<T, 128>), dim3(blocks), dim3(256), 0, st, (const T*)c0, scale, shift, (T*)pooled, argmax, B, Hc, Wc, C);
-  else hipLaunchKernelGGL((stem_bn_relu_pool_fwd_kernel<T, 0>), dim3(blocks), dim3(256), 0, st, (const T*)c0, scale, shift, (T*)pooled, argmax, B, Hc, Wc, C);
+// 64 and 128 channels have instantiations of their own, every other count runs the generic one
+int launch_pool_fwd(const char* entry, int dtype, const void* c0, const float* scale, const float* shift, void* pooled, uint8_t* argmax, int B, int Hc, int Wc, int C, sl_stream_t stream) {
+  return sl_by_dtype(dtype, entry, [&](auto t) -> int {
+    using T = decltype(t);
+    const long long total = (long long)B * ((Hc + 1) / 2) * ((Wc + 1) / 2) * (C / Vec16<T>::N);
+    const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    const auto kern = C == 64 ? stem_bn_relu_pool_fwd_kernel<T, 64> : C == 128 ? stem_bn_relu_pool_fwd_kernel<T, 128> : stem_bn_relu_pool_fwd_kernel<T, 0>;
+    return sl_launch("stem_bn_relu_pool_fwd_kernel", kern, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)c0, scale, shift, (T*)pooled, argmax, B, Hc, Wc, C);
+  });
 }
 
 template <typename T, bool STAT>
-void launch_pool_bwd(int blocks, int threads, const void* dp, const uint8_t* argmax, const void* c0, const float* scale, const float* shift, void* g0, int B, int Hc, int Wc, int C,
-                     const float* mean, const float* invstd, float* part, hipStream_t st) {
-  if (C == 64) hipLaunchKernelGGL((stem_pool_relu_bwd_kernel<T, STAT, 64>), dim3(blocks), dim3(threads), 0, st, (const T*)dp, argmax, (const T*)c0, scale, shift, (T*)g0, B, Hc, Wc, mean, invstd, part, C);
-  else if (C == 128) hipLaunchKernelGGL((stem_pool_relu_bwd_kernel<T, STAT, 128>), dim3(blocks), dim3(threads), 0, st, (const T*)dp, argmax, (const T*)c0, scale, shift, (T*)g0, B, Hc, Wc, mean, invstd, part, C);
-  else hipLaunchKernelGGL((stem_pool_relu_bwd_kernel<T, STAT, 0>), dim3(blocks), dim3(threads), 0, st, (const T*)dp, argmax, (const T*)c0, scale, shift, (T*)g0, B, Hc, Wc, mean, invstd, part, C);
+auto pool_bwd_kernel(int C) { return C == 64 ? stem_pool_relu_bwd_kernel<T, STAT, 64> : C == 128 ? stem_pool_relu_bwd_kernel<T, STAT, 128> : stem_pool_relu_bwd_kernel<T, STAT, 0>; }
+
+// part != nullptr: the instantiation that also writes the column sums of the BatchNorm backward
+int launch_pool_bwd(const char* entry, int dtype, int blocks, int threads, const void* dp, const uint8_t* argmax, const void* c0, const float* scale, const float* shift, void* g0, int B, int Hc, int Wc,
+                    int C, const float* mean, const float* invstd, float* part, sl_stream_t stream) {
+  return sl_by_dtype(dtype, entry, [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("stem_pool_relu_bwd_kernel", part ? pool_bwd_kernel<T, true>(C) : pool_bwd_kernel<T, false>(C), dim3(blocks), dim3(threads), 0, (hipStream_t)stream, (const T*)dp, argmax, (const T*)c0,
+                     scale, shift, (T*)g0, B, Hc, Wc, mean, invstd, part, C);
+  });
 }
 
 }  // namespace
@@ -581,33 +584,21 @@ extern "C" int sl_stem_bn_relu_pool_fwd_c(int dtype, const void* c0, const float
   SL_REQUIRE(c0 && scale && shift && pooled && B > 0 && Hc > 0 && Wc > 0, "stem_bn_relu_pool_fwd_c: bad args");
   SL_REQUIRE(pool_c_ok(C), "stem_bn_relu_pool_fwd_c: C = %d is not a multiple of 64 in 64..1024", C);
   SL_REQUIRE((long long)B * Hc * Wc * C < (1ll << 31), "stem_bn_relu_pool_fwd_c: more than 2^31 elements");
-  if (dtype == SL_BF16) launch_pool_fwd<bf16_t>(c0, scale, shift, pooled, argmax, B, Hc, Wc, C, (hipStream_t)stream);
-  else if (dtype == SL_F32) launch_pool_fwd<float>(c0, scale, shift, pooled, argmax, B, Hc, Wc, C, (hipStream_t)stream);
-  else SL_REQUIRE(false, "stem_bn_relu_pool_fwd_c: bad dtype");
-  SL_LAUNCH_CHECK("stem_bn_relu_pool_fwd_kernel");
-  return 0;
+  return launch_pool_fwd("stem_bn_relu_pool_fwd_c", dtype, c0, scale, shift, pooled, argmax, B, Hc, Wc, C, stream);
 }
 
 extern "C" int sl_stem_bn_relu_pool_fwd(int dtype, const void* c0, const float* scale, const float* shift, void* pooled,
                                         uint8_t* argmax, int B, int Hc, int Wc, sl_stream_t stream) {
   SL_REQUIRE(c0 && scale && shift && pooled && B > 0 && Hc % 2 == 0 && Wc % 2 == 0, "stem_bn_relu_pool_fwd: bad args");
-  SL_REQUIRE(dtype == SL_BF16 || dtype == SL_F32, "stem_bn_relu_pool_fwd: bad dtype");
-  if (dtype == SL_BF16) launch_pool_fwd<bf16_t>(c0, scale, shift, pooled, argmax, B, Hc, Wc, 64, (hipStream_t)stream);
-  else launch_pool_fwd<float>(c0, scale, shift, pooled, argmax, B, Hc, Wc, 64, (hipStream_t)stream);
-  SL_LAUNCH_CHECK("stem_bn_relu_pool_fwd_kernel");
-  return 0;
+  return launch_pool_fwd("stem_bn_relu_pool_fwd", dtype, c0, scale, shift, pooled, argmax, B, Hc, Wc, 64, stream);
 }
 
 extern "C" int sl_stem_pool_relu_bwd(int dtype, const void* dpooled, const uint8_t* argmax, const void* c0, const float* scale,
                                      const float* shift, void* g0, int B, int Hc, int Wc, sl_stream_t stream) {
   SL_REQUIRE(dpooled && argmax && c0 && scale && shift && g0 && B > 0 && Hc % 2 == 0 && Wc % 2 == 0, "stem_pool_relu_bwd: bad args");
-  SL_REQUIRE(dtype == SL_BF16 || dtype == SL_F32, "stem_pool_relu_bwd: bad dtype");
   const long long total = (long long)B * Hc * Wc * (dtype == SL_BF16 ? 8 : 16);
   const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  if (dtype == SL_BF16) launch_pool_bwd<bf16_t, false>(blocks, 256, dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, 64, nullptr, nullptr, nullptr, (hipStream_t)stream);
-  else launch_pool_bwd<float, false>(blocks, 256, dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, 64, nullptr, nullptr, nullptr, (hipStream_t)stream);
-  SL_LAUNCH_CHECK("stem_pool_relu_bwd_kernel");
-  return 0;
+  return launch_pool_bwd("stem_pool_relu_bwd", dtype, blocks, 256, dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, 64, nullptr, nullptr, nullptr, stream);
 }
 
 // The same + the column sums of bn1's backward: stat_partial [sl_stem_pool_relu_bwd_bnstat_rows(B, Hc, Wc)][2][64] (consumed by sl_bn_bwd_finalize like bn_bwd_reduce's)
@@ -615,12 +606,7 @@ extern "C" int sl_stem_pool_relu_bwd_bnstat_rows(int B, int Hc, int Wc) { return
 extern "C" int sl_stem_pool_relu_bwd_bnstat(int dtype, const void* dpooled, const uint8_t* argmax, const void* c0, const float* scale, const float* shift,
                                             const float* mean, const float* invstd, void* g0, float* stat_partial, int B, int Hc, int Wc, sl_stream_t stream) {
   SL_REQUIRE(dpooled && argmax && c0 && scale && shift && mean && invstd && g0 && stat_partial && B > 0 && Hc % 2 == 0 && Wc % 2 == 0, "stem_pool_relu_bwd_bnstat: bad args");
-  SL_REQUIRE(dtype == SL_BF16 || dtype == SL_F32, "stem_pool_relu_bwd_bnstat: bad dtype");
-  const int blocks = pool_bwd_stat_rows(B, Hc, Wc, 64);
-  if (dtype == SL_BF16) launch_pool_bwd<bf16_t, true>(blocks, 256, dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, 64, mean, invstd, stat_partial, (hipStream_t)stream);
-  else launch_pool_bwd<float, true>(blocks, 256, dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, 64, mean, invstd, stat_partial, (hipStream_t)stream);
-  SL_LAUNCH_CHECK("stem_pool_relu_bwd_kernel");
-  return 0;
+  return launch_pool_bwd("stem_pool_relu_bwd_bnstat", dtype, pool_bwd_stat_rows(B, Hc, Wc, 64), 256, dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, 64, mean, invstd, stat_partial, stream);
 }
 
 // C channels (a multiple of 64, at most 1024): stat_partial [sl_stem_pool_relu_bwd_bnstat_c_rows(B, Hc, Wc, C)][2][C]
@@ -631,11 +617,7 @@ extern "C" int sl_stem_pool_relu_bwd_bnstat_c(int dtype, const void* dpooled, co
   SL_REQUIRE(pool_c_ok(C), "stem_pool_relu_bwd_bnstat_c: C = %d is not a multiple of 64 in 64..1024", C);
   SL_REQUIRE(dtype == SL_BF16 || dtype == SL_F32, "stem_pool_relu_bwd_bnstat_c: bad dtype");
   SL_REQUIRE((long long)B * Hc * Wc * C < (1ll << 31), "stem_pool_relu_bwd_bnstat_c: more than 2^31 elements");
-  const int blocks = pool_bwd_stat_rows(B, Hc, Wc, C), threads = pool_bwd_threads(dtype, C);
-  if (dtype == SL_BF16) launch_pool_bwd<bf16_t, true>(blocks, threads, dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, C, mean, invstd, stat_partial, (hipStream_t)stream);
-  else launch_pool_bwd<float, true>(blocks, threads, dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, C, mean, invstd, stat_partial, (hipStream_t)stream);
-  SL_LAUNCH_CHECK("stem_pool_relu_bwd_kernel");
-  return 0;
+  return launch_pool_bwd("stem_pool_relu_bwd_bnstat_c", dtype, pool_bwd_stat_rows(B, Hc, Wc, C), pool_bwd_threads(dtype, C), dpooled, argmax, c0, scale, shift, g0, B, Hc, Wc, C, mean, invstd, stat_partial, stream);
 }
 
 extern "C" size_t sl_stem_conv_bwd_weight_workspace(int B, int H, int W) {
@@ -647,15 +629,14 @@ extern "C" int sl_stem_conv_bwd_weight(int dtype, const float* img_nchw, const v
   SL_REQUIRE(img_nchw && dc0 && dw_oihw && workspace && B > 0 && H % 2 == 0 && W % 2 == 0, "stem_conv_bwd_weight: bad args");
   const int ntiles = stem_tiles(B, H, W), nblk = stem_wgrad_blocks(ntiles), tpb = cdiv(ntiles, nblk);
   if (workspace_bytes < (size_t)nblk * 64 * NTAP * sizeof(float)) { sl_set_error("stem_conv_bwd_weight: workspace too small"); return SL_EWORKSPACE; }
-  const size_t lds = (256 * 64 + 3 * PS * PS) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == SL_BF16) {
     const size_t l2 = (size_t)(3 * PS * MP + 6) * sizeof(bf16_t) + 256 * 72 * sizeof(bf16_t);
-    hipLaunchKernelGGL(stem_wgrad_mfma_kernel, dim3(nblk), dim3(256), l2, st, img_nchw, (const bf16_t*)dc0, (float*)workspace, B, H, W, ntiles);
-    SL_LAUNCH_CHECK("stem_wgrad_mfma_kernel");
-  } else if (dtype == SL_F32) hipLaunchKernelGGL(stem_wgrad_kernel<float>, dim3(nblk), dim3(256), lds, st, img_nchw, (const float*)dc0, (float*)workspace, B, H, W, tpb, ntiles);
-  else SL_REQUIRE(false, "stem_conv_bwd_weight: bad dtype");
-  SL_LAUNCH_CHECK("stem_wgrad_kernel");
+    SL_TRY(sl_launch("stem_wgrad_mfma_kernel", stem_wgrad_mfma_kernel, dim3(nblk), dim3(256), l2, st, img_nchw, (const bf16_t*)dc0, (float*)workspace, B, H, W, ntiles));
+  } else if (dtype == SL_F32) {
+    const size_t lds = (256 * 64 + 3 * PS * PS) * sizeof(float);
+    SL_TRY(sl_launch("stem_wgrad_kernel", stem_wgrad_kernel<float>, dim3(nblk), dim3(256), lds, st, img_nchw, (const float*)dc0, (float*)workspace, B, H, W, tpb, ntiles));
+  } else SL_REQUIRE(false, "stem_conv_bwd_weight: bad dtype");
   return sl_colsum_finalize((const float*)workspace, nblk, 64 * NTAP, dw_oihw, stream);       // fixed-order sum of the block partials (64 x 16 lanes per block of columns)
 }
 
@@ -663,9 +644,8 @@ extern "C" int sl_stem_im2col(int dtype, const float* img_nchw, void* col, int B
   SL_REQUIRE(img_nchw && col && B > 0 && H % 2 == 0 && W % 2 == 0, "stem_im2col: bad args");
   const long long total = (long long)B * (H / 2) * (W / 2) * (dtype == SL_BF16 ? 24 : 48);
   const int blocks = (int)((total + 255) / 256 < 32768 ? (total + 255) / 256 : 32768);
-  if (dtype == SL_BF16) hipLaunchKernelGGL(stem_im2col_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, img_nchw, (bf16_t*)col, B, H, W);
-  else if (dtype == SL_F32) hipLaunchKernelGGL(stem_im2col_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, img_nchw, (float*)col, B, H, W);
-  else SL_REQUIRE(false, "stem_im2col: bad dtype");
-  SL_LAUNCH_CHECK("stem_im2col_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "stem_im2col", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("stem_im2col_kernel", stem_im2col_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, img_nchw, (T*)col, B, H, W);
+  });
 }

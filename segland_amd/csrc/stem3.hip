@@ -423,14 +423,10 @@ extern "C" int sl_stem3_conv_fwd(int dtype, const float* img_nchw, const float* 
   if (dtype == SL_BF16) {
     SL_REQUIRE(workspace && ((size_t)workspace & 15) == 0, "stem3_conv_fwd: bf16 needs the 16-byte aligned workspace of sl_stem3_conv_fwd_workspace()");
     uint4* wfrag = (uint4*)workspace;                                           // the weights in MFMA fragment order, rebuilt on every call (8 KiB)
-    hipLaunchKernelGGL(stem3_weight_frag_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, w_oihw, wfrag);
-    hipLaunchKernelGGL(stem3_conv_fwd_mfma_kernel, grid, dim3(256), 0, (hipStream_t)stream, img_nchw, (const uint4*)wfrag, (bf16_t*)y, stat_partial, scale, shift, B, H, W);
-    SL_LAUNCH_CHECK("stem3_conv_fwd_mfma_kernel");
-    return 0;
+    SL_TRY(sl_launch("stem3_weight_frag_kernel", stem3_weight_frag_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, w_oihw, wfrag));
+    return sl_launch("stem3_conv_fwd_mfma_kernel", stem3_conv_fwd_mfma_kernel, grid, dim3(256), 0, (hipStream_t)stream, img_nchw, (const uint4*)wfrag, (bf16_t*)y, stat_partial, scale, shift, B, H, W);
   }
-  hipLaunchKernelGGL(stem3_conv_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, img_nchw, w_oihw, (float*)y, stat_partial, scale, shift, B, H, W);
-  SL_LAUNCH_CHECK("stem3_conv_fwd_kernel");
-  return 0;
+  return sl_launch("stem3_conv_fwd_kernel", stem3_conv_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, img_nchw, w_oihw, (float*)y, stat_partial, scale, shift, B, H, W);
 }
 
 extern "C" size_t sl_stem3_conv_bwd_weight_workspace(int B, int H, int W) {
@@ -447,14 +443,10 @@ extern "C" int sl_stem3_conv_bwd_weight(int dtype, const float* img_nchw, const 
   if (workspace_bytes < (size_t)nblk * 64 * NTAP * sizeof(float)) { sl_set_error("stem3_conv_bwd_weight: workspace too small"); return SL_EWORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
   if (dtype == SL_BF16) {
-    hipLaunchKernelGGL(stem3_wgrad_mfma_kernel, dim3(nblk), dim3(256), 0, st, img_nchw, (const bf16_t*)dc1, (float*)workspace, B, H, W, ntiles);
-    SL_LAUNCH_CHECK("stem3_wgrad_mfma_kernel");
+    SL_TRY(sl_launch("stem3_wgrad_mfma_kernel", stem3_wgrad_mfma_kernel, dim3(nblk), dim3(256), 0, st, img_nchw, (const bf16_t*)dc1, (float*)workspace, B, H, W, ntiles));
   } else {
     const size_t lds = (256 * 64 + 3 * PS * PS) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)stem3_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
-    hipLaunchKernelGGL(stem3_wgrad_kernel, dim3(nblk), dim3(256), lds, st, img_nchw, (const float*)dc1, (float*)workspace, B, H, W, tpb, ntiles);
-    SL_LAUNCH_CHECK("stem3_wgrad_kernel");
+    SL_TRY(sl_launch("stem3_wgrad_kernel", stem3_wgrad_kernel, dim3(nblk), dim3(256), lds, st, img_nchw, (const float*)dc1, (float*)workspace, B, H, W, tpb, ntiles));
   }
   return sl_colsum_finalize((const float*)workspace, nblk, 64 * NTAP, dw_oihw, stream);       // fixed-order sum of the block partials
 }

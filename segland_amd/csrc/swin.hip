@@ -1391,13 +1391,6 @@ int check_geom(const SlWinDesc* d, WinGeom& g) {
 
 }  // namespace
 
-#define BY_DTYPE(dtype, CALL_BF, CALL_F32, what)             \
-  do {                                                       \
-    if ((dtype) == SL_BF16) { CALL_BF; }                     \
-    else if ((dtype) == SL_F32) { CALL_F32; }                \
-    else SL_REQUIRE(false, what ": bad dtype");              \
-  } while (0)
-
 extern "C" int sl_patch_embed_fwd(int dtype, const float* img, const float* w, const float* bias, void* out, int B, int H, int W, int C,
                                   int out_pitch, sl_stream_t stream) {
   SL_REQUIRE(img && w && bias && out && B > 0 && H > 0 && W > 0, "patch_embed_fwd: bad args");
@@ -1405,36 +1398,32 @@ extern "C" int sl_patch_embed_fwd(int dtype, const float* img, const float* w, c
   const int Ho = cdiv(H, 4), Wo = cdiv(W, 4);
   const long long ntok = (long long)B * Ho * Wo;
   const size_t lds = (size_t)(48 * C + 64 * 49) * sizeof(float);
-  hipStream_t st = (hipStream_t)stream;
-  BY_DTYPE(dtype,
-           hipLaunchKernelGGL(patch_embed_fwd_kernel<bf16_t>, dim3(cdiv(ntok, 64)), dim3(256), lds, st, img, w, bias, (bf16_t*)out, B, H, W, Ho, Wo, C, out_pitch),
-           hipLaunchKernelGGL(patch_embed_fwd_kernel<float>, dim3(cdiv(ntok, 64)), dim3(256), lds, st, img, w, bias, (float*)out, B, H, W, Ho, Wo, C, out_pitch),
-           "patch_embed_fwd");
-  SL_LAUNCH_CHECK("patch_embed_fwd_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "patch_embed_fwd", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("patch_embed_fwd_kernel", patch_embed_fwd_kernel<T>, dim3(cdiv(ntok, 64)), dim3(256), lds, (hipStream_t)stream, img, w, bias, (T*)out, B, H, W, Ho, Wo, C, out_pitch);
+  });
 }
 
 extern "C" int sl_patch_im2col(int dtype, const float* img, void* col, int B, int H, int W, sl_stream_t stream) {
   SL_REQUIRE(img && col && B > 0 && H > 0 && W > 0, "patch_im2col: bad args");
   const int Ho = cdiv(H, 4), Wo = cdiv(W, 4);
   const long long n = (long long)B * Ho * Wo * 16;
-  hipStream_t st = (hipStream_t)stream;
-  BY_DTYPE(dtype, hipLaunchKernelGGL(patch_im2col_kernel<bf16_t>, dim3(ew_grid(n)), dim3(256), 0, st, img, (bf16_t*)col, B, H, W, Ho, Wo),
-           hipLaunchKernelGGL(patch_im2col_kernel<float>, dim3(ew_grid(n)), dim3(256), 0, st, img, (float*)col, B, H, W, Ho, Wo), "patch_im2col");
-  SL_LAUNCH_CHECK("patch_im2col_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "patch_im2col", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("patch_im2col_kernel", patch_im2col_kernel<T>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, img, (T*)col, B, H, W, Ho, Wo);
+  });
 }
 
+// the instantiation by lanes per row and channel vectors per lane, and its grid
 template <typename T>
 static int launch_ln_fwd(const void* x, const float* gamma, const float* beta, void* y, float* stats, long long rows, int C, int px, int py, float eps, hipStream_t st) {
   constexpr int V = Vec16<T>::N;
   const int nvec = C / V, nvp = py / V > nvec ? py / V : nvec;      // vectors of a row incl. the zero pad of the output pitch
   // one row group per wave where the map is small (a grid of rows / 16 blocks left 2 048 rows x 768 channels to 129 blocks: four dependent rows per wave)
   auto grid_of = [&](int lpr) { const long long g = (rows + 4 * (64 / lpr) - 1) / (4 * (64 / lpr)); return (int)(g > 16384 ? 16384 : (g < 1 ? 1 : g)); };
-#define LN_FWD(LPR, NVL) hipLaunchKernelGGL((layernorm_fwd_kernel<T, LPR, NVL>), dim3(grid_of(LPR)), dim3(256), 0, st, (const T*)x, gamma, beta, (T*)y, stats, rows, C, px, py, eps)
-  if (nvp <= 16) LN_FWD(16, 1); else if (nvp <= 32) LN_FWD(32, 1); else if (nvp <= 64) LN_FWD(64, 1); else if (nvp <= 128) LN_FWD(64, 2); else if (nvp <= 192) LN_FWD(64, 3); else LN_FWD(64, 0);
+#define LN_FWD(LPR, NVL) sl_launch("layernorm_fwd_kernel", layernorm_fwd_kernel<T, LPR, NVL>, dim3(grid_of(LPR)), dim3(256), 0, st, (const T*)x, gamma, beta, (T*)y, stats, rows, C, px, py, eps)
+  return nvp <= 16 ? LN_FWD(16, 1) : nvp <= 32 ? LN_FWD(32, 1) : nvp <= 64 ? LN_FWD(64, 1) : nvp <= 128 ? LN_FWD(64, 2) : nvp <= 192 ? LN_FWD(64, 3) : LN_FWD(64, 0);
 #undef LN_FWD
-  return 0;
 }
 
 extern "C" int sl_layernorm_fwd(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* mean_rstd, long long rows,
@@ -1442,11 +1431,7 @@ extern "C" int sl_layernorm_fwd(int dtype, const void* x, const float* gamma, co
   SL_REQUIRE(x && gamma && beta && y && rows > 0 && C > 0, "layernorm_fwd: bad args");
   const int vb = dtype == SL_BF16 ? 8 : 4;
   SL_REQUIRE(C % vb == 0 && x_pitch >= C && y_pitch >= C && x_pitch % vb == 0 && y_pitch % vb == 0, "layernorm_fwd: C / pitches must be multiples of a 16-byte vector");
-  hipStream_t st = (hipStream_t)stream;
-  BY_DTYPE(dtype, launch_ln_fwd<bf16_t>(x, gamma, beta, y, mean_rstd, rows, C, x_pitch, y_pitch, eps, st),
-           launch_ln_fwd<float>(x, gamma, beta, y, mean_rstd, rows, C, x_pitch, y_pitch, eps, st), "layernorm_fwd");
-  SL_LAUNCH_CHECK("layernorm_fwd_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "layernorm_fwd", [&](auto t) -> int { return launch_ln_fwd<decltype(t)>(x, gamma, beta, y, mean_rstd, rows, C, x_pitch, y_pitch, eps, (hipStream_t)stream); });
 }
 
 constexpr int LN_BWD_BLOCKS = 2048;     // partial rows of the fused column sums (grid-stride over the rows)
@@ -1465,21 +1450,17 @@ static int ln_bwd_fused_blocks(long long rows, int nvp) {
 
 template <typename T>
 static int launch_ln_bwd(const void* dy, const void* x, const float* gamma, const float* stats, const void* addend, void* dx, float* part, long long rows, int C,
-                         int pdy, int px, int pdx, hipStream_t st, void* dx2 = nullptr, const float* rscale = nullptr, long long rps = 1) {
+                         int pdy, int px, int pdx, hipStream_t st, void* dx2, const float* rscale, long long rps) {
   constexpr int V = Vec16<T>::N;
   const int nvec = C / V, nvp = pdx / V;
   long long want = rows / 16 + 1;
   const bool fused = part != nullptr && nvp <= 192;
   const int grid = (int)(fused ? ln_bwd_fused_blocks(rows, nvp) : (want > 8192 ? 8192 : want));
   const size_t lds = fused ? (size_t)8 * C * sizeof(float) : 0;
-#define LN_BWD(LPR, NV) hipLaunchKernelGGL((layernorm_bwd_kernel<T, LPR, NV>), dim3(grid), dim3(256), lds, st, (const T*)dy, (const T*)x, gamma, stats, (const T*)addend, (T*)dx, part, rows, C, pdy, px, pdx, (T*)dx2, rscale, rps)
-  if (fused) {
-    if (nvp <= 16) LN_BWD(16, 1); else if (nvp <= 32) LN_BWD(32, 1); else if (nvp <= 64) LN_BWD(64, 1); else if (nvp <= 128) LN_BWD(64, 2); else LN_BWD(64, 3);
-  } else {
-    if (nvec <= 16) LN_BWD(16, 0); else if (nvec <= 32) LN_BWD(32, 0); else LN_BWD(64, 0);
-  }
+#define LN_BWD(LPR, NV) sl_launch("layernorm_bwd_kernel", layernorm_bwd_kernel<T, LPR, NV>, dim3(grid), dim3(256), lds, st, (const T*)dy, (const T*)x, gamma, stats, (const T*)addend, (T*)dx, part, rows, C, pdy, px, pdx, (T*)dx2, rscale, rps)
+  if (fused) return nvp <= 16 ? LN_BWD(16, 1) : nvp <= 32 ? LN_BWD(32, 1) : nvp <= 64 ? LN_BWD(64, 1) : nvp <= 128 ? LN_BWD(64, 2) : LN_BWD(64, 3);
+  return nvec <= 16 ? LN_BWD(16, 0) : nvec <= 32 ? LN_BWD(32, 0) : LN_BWD(64, 0);
 #undef LN_BWD
-  return fused ? grid : 0;
 }
 
 extern "C" int sl_layernorm_bwd_rows(int dtype, long long rows, int C, int dx_pitch) {
@@ -1498,19 +1479,14 @@ static int layernorm_bwd_run(int dtype, const void* dy, const void* x, const flo
   SL_REQUIRE(C % vb == 0 && dy_pitch >= C && x_pitch >= C && dx_pitch >= C && dy_pitch % vb == 0 && x_pitch % vb == 0 && dx_pitch % vb == 0, "layernorm_bwd: bad pitches");
   hipStream_t st = (hipStream_t)stream;
   const bool fused = dgamma_dbeta_partial && dx_pitch / vb <= 192;
-  if (dtype == SL_BF16) launch_ln_bwd<bf16_t>(dy, x, gamma, mean_rstd, addend, dx, fused ? dgamma_dbeta_partial : nullptr, rows, C, dy_pitch, x_pitch, dx_pitch, st, dx2, rscale, rps);
-  else launch_ln_bwd<float>(dy, x, gamma, mean_rstd, addend, dx, fused ? dgamma_dbeta_partial : nullptr, rows, C, dy_pitch, x_pitch, dx_pitch, st, dx2, rscale, rps);
-  SL_LAUNCH_CHECK("layernorm_bwd_kernel");
-  if (dgamma_dbeta_partial && !fused) {
+  return sl_by_dtype(dtype, "layernorm_bwd", [&](auto t) -> int {
+    using T = decltype(t);
+    SL_TRY(launch_ln_bwd<T>(dy, x, gamma, mean_rstd, addend, dx, fused ? dgamma_dbeta_partial : nullptr, rows, C, dy_pitch, x_pitch, dx_pitch, st, dx2, rscale, rps));
+    if (!dgamma_dbeta_partial || fused) return 0;
     const int nblk = sl_layernorm_bwd_rows(dtype, rows, C, dx_pitch);
     const long long rpb = (rows + nblk - 1) / nblk;
-    BY_DTYPE(dtype,
-             hipLaunchKernelGGL(layernorm_bwd_cols_kernel<bf16_t>, dim3(nblk), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, mean_rstd, dgamma_dbeta_partial, rows, C, dy_pitch, x_pitch, rpb),
-             hipLaunchKernelGGL(layernorm_bwd_cols_kernel<float>, dim3(nblk), dim3(256), 0, st, (const float*)dy, (const float*)x, mean_rstd, dgamma_dbeta_partial, rows, C, dy_pitch, x_pitch, rpb),
-             "layernorm_bwd");
-    SL_LAUNCH_CHECK("layernorm_bwd_cols_kernel");
-  }
-  return 0;
+    return sl_launch("layernorm_bwd_cols_kernel", layernorm_bwd_cols_kernel<T>, dim3(nblk), dim3(256), 0, st, (const T*)dy, (const T*)x, mean_rstd, dgamma_dbeta_partial, rows, C, dy_pitch, x_pitch, rpb);
+  });
 }
 
 extern "C" int sl_layernorm_bwd(int dtype, const void* dy, const void* x, const float* gamma, const float* mean_rstd, const void* addend, void* dx,
@@ -1527,40 +1503,38 @@ extern "C" int sl_layernorm_bwd_scaled(int dtype, const void* dy, const void* x,
 
 extern "C" int sl_gelu_fwd(int dtype, const void* h, void* y, long long n, sl_stream_t stream) {
   SL_REQUIRE(h && y && n > 0 && n % 8 == 0, "gelu_fwd: bad args");
-  hipStream_t st = (hipStream_t)stream;
-  BY_DTYPE(dtype, hipLaunchKernelGGL(gelu_fwd_kernel<bf16_t>, dim3(ew_grid(n / 8)), dim3(256), 0, st, (const bf16_t*)h, (bf16_t*)y, n / 8),
-           hipLaunchKernelGGL(gelu_fwd_kernel<float>, dim3(ew_grid(n / 4)), dim3(256), 0, st, (const float*)h, (float*)y, n / 4), "gelu_fwd");
-  SL_LAUNCH_CHECK("gelu_fwd_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "gelu_fwd", [&](auto t) -> int {
+    using T = decltype(t);
+    const long long nvec = n / Vec16<T>::N;
+    return sl_launch("gelu_fwd_kernel", gelu_fwd_kernel<T>, dim3(ew_grid(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)h, (T*)y, nvec);
+  });
 }
 
 extern "C" int sl_gelu_bwd(int dtype, const void* h, const void* dy, void* dh, long long n, sl_stream_t stream) {
   SL_REQUIRE(h && dy && dh && n > 0 && n % 8 == 0, "gelu_bwd: bad args");
-  hipStream_t st = (hipStream_t)stream;
-  BY_DTYPE(dtype, hipLaunchKernelGGL(gelu_bwd_kernel<bf16_t>, dim3(ew_grid(n / 8)), dim3(256), 0, st, (const bf16_t*)h, (const bf16_t*)dy, (bf16_t*)dh, n / 8),
-           hipLaunchKernelGGL(gelu_bwd_kernel<float>, dim3(ew_grid(n / 4)), dim3(256), 0, st, (const float*)h, (const float*)dy, (float*)dh, n / 4), "gelu_bwd");
-  SL_LAUNCH_CHECK("gelu_bwd_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "gelu_bwd", [&](auto t) -> int {
+    using T = decltype(t);
+    const long long nvec = n / Vec16<T>::N;
+    return sl_launch("gelu_bwd_kernel", gelu_bwd_kernel<T>, dim3(ew_grid(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)h, (const T*)dy, (T*)dh, nvec);
+  });
 }
 
 extern "C" int sl_patch_merge_gather(int dtype, const void* x, void* xm, int B, int H, int W, int C, int x_pitch, sl_stream_t stream) {
   SL_REQUIRE(x && xm && B > 0 && H > 0 && W > 0 && C % 8 == 0 && x_pitch >= C && x_pitch % 8 == 0, "patch_merge_gather: bad args");
-  hipStream_t st = (hipStream_t)stream;
   const long long n = (long long)B * ((H + 1) / 2) * ((W + 1) / 2) * 4 * C;
-  BY_DTYPE(dtype, hipLaunchKernelGGL(merge_gather_kernel<bf16_t>, dim3(ew_grid(n / 8)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)xm, B, H, W, C, x_pitch),
-           hipLaunchKernelGGL(merge_gather_kernel<float>, dim3(ew_grid(n / 4)), dim3(256), 0, st, (const float*)x, (float*)xm, B, H, W, C, x_pitch), "patch_merge_gather");
-  SL_LAUNCH_CHECK("merge_gather_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "patch_merge_gather", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("merge_gather_kernel", merge_gather_kernel<T>, dim3(ew_grid(n / Vec16<T>::N)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)xm, B, H, W, C, x_pitch);
+  });
 }
 
 extern "C" int sl_patch_merge_scatter(int dtype, const void* dxm, void* dx, int B, int H, int W, int C, int dx_pitch, sl_stream_t stream) {
   SL_REQUIRE(dxm && dx && B > 0 && H > 0 && W > 0 && C % 8 == 0 && dx_pitch >= C && dx_pitch % 8 == 0, "patch_merge_scatter: bad args");
-  hipStream_t st = (hipStream_t)stream;
   const long long n = (long long)B * H * W * dx_pitch;
-  BY_DTYPE(dtype, hipLaunchKernelGGL(merge_scatter_kernel<bf16_t>, dim3(ew_grid(n / 8)), dim3(256), 0, st, (const bf16_t*)dxm, (bf16_t*)dx, B, H, W, C, dx_pitch),
-           hipLaunchKernelGGL(merge_scatter_kernel<float>, dim3(ew_grid(n / 4)), dim3(256), 0, st, (const float*)dxm, (float*)dx, B, H, W, C, dx_pitch), "patch_merge_scatter");
-  SL_LAUNCH_CHECK("merge_scatter_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "patch_merge_scatter", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("merge_scatter_kernel", merge_scatter_kernel<T>, dim3(ew_grid(n / Vec16<T>::N)), dim3(256), 0, (hipStream_t)stream, (const T*)dxm, (T*)dx, B, H, W, C, dx_pitch);
+  });
 }
 
 static int check_resize(const SlResizeDesc* d) {
@@ -1572,14 +1546,20 @@ static int check_resize(const SlResizeDesc* d) {
   return 0;
 }
 
+// f(T(), S()): T the element type of the large map, S of the small one (fp32 under a bf16 map with src_f32); check_resize has seen the dtype
+template <typename F>
+static int by_resize_types(const SlResizeDesc* d, F&& f) {
+  if (d->dtype == SL_BF16) return d->src_f32 ? f(bf16_t(), float()) : f(bf16_t(), bf16_t());
+  return f(float(), float());
+}
+
 static int bilinear_fwd_launch(const SlResizeDesc* d, const void* src, const void* add, void* dst, hipStream_t st) {
   const long long n = (long long)d->B * d->H * d->W * d->C;
 #define BL_ARGS d->B, d->h, d->w, d->H, d->W, d->C, d->src_pitch, d->src_off, d->dst_pitch, d->dst_off, d->align_corners
-  if (d->dtype == SL_BF16 && d->src_f32) hipLaunchKernelGGL((bilinear_fwd_kernel<bf16_t, float>), dim3(ew_grid(n / 8)), dim3(256), 0, st, (const float*)src, (bf16_t*)dst, BL_ARGS, (const bf16_t*)add);
-  else if (d->dtype == SL_BF16) hipLaunchKernelGGL((bilinear_fwd_kernel<bf16_t, bf16_t>), dim3(ew_grid(n / 8)), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, BL_ARGS, (const bf16_t*)add);
-  else hipLaunchKernelGGL((bilinear_fwd_kernel<float, float>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const float*)src, (float*)dst, BL_ARGS, (const float*)add);
-  SL_LAUNCH_CHECK("bilinear_fwd_kernel");
-  return 0;
+  return by_resize_types(d, [&](auto t, auto s) -> int {
+    using T = decltype(t); using S = decltype(s);
+    return sl_launch("bilinear_fwd_kernel", bilinear_fwd_kernel<T, S>, dim3(ew_grid(n / Vec16<T>::N)), dim3(256), 0, st, (const S*)src, (T*)dst, BL_ARGS, (const T*)add);
+  });
 }
 
 extern "C" int sl_bilinear_fwd(const SlResizeDesc* d, const void* src, void* dst, sl_stream_t stream) {
@@ -1601,31 +1581,22 @@ extern "C" int sl_bilinear_bwd(const SlResizeDesc* d, const void* ddst, void* ds
   hipStream_t st = (hipStream_t)stream;
   const long long n = (long long)d->B * d->h * d->w * d->C;
   const int nsrc = d->B * d->h * d->w, nv = d->C / (d->dtype == SL_BF16 ? 8 : 4);
-  if (nsrc <= 2048 && (long long)d->H * d->W >= 4LL * d->h * d->w && nv <= 128 && 256 % nv == 0) {       // few source pixels under a large map: a block per source pixel
-    if (d->dtype == SL_BF16 && d->src_f32) hipLaunchKernelGGL((bilinear_bwd_small_kernel<bf16_t, float>), dim3(nsrc), dim3(256), 0, st, (const bf16_t*)ddst, (float*)dsrc, BL_ARGS, d->accumulate);
-    else if (d->dtype == SL_BF16) hipLaunchKernelGGL((bilinear_bwd_small_kernel<bf16_t, bf16_t>), dim3(nsrc), dim3(256), 0, st, (const bf16_t*)ddst, (bf16_t*)dsrc, BL_ARGS, d->accumulate);
-    else hipLaunchKernelGGL((bilinear_bwd_small_kernel<float, float>), dim3(nsrc), dim3(256), 0, st, (const float*)ddst, (float*)dsrc, BL_ARGS, d->accumulate);
-    SL_LAUNCH_CHECK("bilinear_bwd_small_kernel");
-    return 0;
-  }
-  if (d->dtype == SL_BF16 && d->src_f32) hipLaunchKernelGGL((bilinear_bwd_kernel<bf16_t, float>), dim3(ew_grid(n / 8)), dim3(256), 0, st, (const bf16_t*)ddst, (float*)dsrc, BL_ARGS, d->accumulate);
-  else if (d->dtype == SL_BF16) hipLaunchKernelGGL((bilinear_bwd_kernel<bf16_t, bf16_t>), dim3(ew_grid(n / 8)), dim3(256), 0, st, (const bf16_t*)ddst, (bf16_t*)dsrc, BL_ARGS, d->accumulate);
-  else hipLaunchKernelGGL((bilinear_bwd_kernel<float, float>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const float*)ddst, (float*)dsrc, BL_ARGS, d->accumulate);
-  SL_LAUNCH_CHECK("bilinear_bwd_kernel");
-  return 0;
+  const bool small = nsrc <= 2048 && (long long)d->H * d->W >= 4LL * d->h * d->w && nv <= 128 && 256 % nv == 0;       // few source pixels under a large map: a block per source pixel
+  return by_resize_types(d, [&](auto t, auto s) -> int {
+    using T = decltype(t); using S = decltype(s);
+    if (small) return sl_launch("bilinear_bwd_small_kernel", bilinear_bwd_small_kernel<T, S>, dim3(nsrc), dim3(256), 0, st, (const T*)ddst, (S*)dsrc, BL_ARGS, d->accumulate);
+    return sl_launch("bilinear_bwd_kernel", bilinear_bwd_kernel<T, S>, dim3(ew_grid(n / Vec16<T>::N)), dim3(256), 0, st, (const T*)ddst, (S*)dsrc, BL_ARGS, d->accumulate);
+  });
 }
 
 extern "C" int sl_scale_add(int dtype, const void* x, const float* scale, const void* addend, void* out, int B, long long rows_per_sample, int C,
                             int pitch, int per_channel, sl_stream_t stream) {
   SL_REQUIRE(x && scale && out && B > 0 && rows_per_sample > 0 && C > 0 && pitch >= C && pitch % 8 == 0, "scale_add: bad args");
-  hipStream_t st = (hipStream_t)stream;
-  const long long n = (long long)B * rows_per_sample * pitch;
-  BY_DTYPE(dtype,
-           hipLaunchKernelGGL(scale_add_kernel<bf16_t>, dim3(ew_grid(n / 8)), dim3(256), 0, st, (const bf16_t*)x, scale, (const bf16_t*)addend, (bf16_t*)out, rows_per_sample, C, pitch, per_channel, n / 8),
-           hipLaunchKernelGGL(scale_add_kernel<float>, dim3(ew_grid(n / 4)), dim3(256), 0, st, (const float*)x, scale, (const float*)addend, (float*)out, rows_per_sample, C, pitch, per_channel, n / 4),
-           "scale_add");
-  SL_LAUNCH_CHECK("scale_add_kernel");
-  return 0;
+  return sl_by_dtype(dtype, "scale_add", [&](auto t) -> int {
+    using T = decltype(t);
+    const long long nvec = (long long)B * rows_per_sample * pitch / Vec16<T>::N;
+    return sl_launch("scale_add_kernel", scale_add_kernel<T>, dim3(ew_grid(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)x, scale, (const T*)addend, (T*)out, rows_per_sample, C, pitch, per_channel, nvec);
+  });
 }
 
 // test hook (not part of the public ABI): 1 = the fp32-arithmetic VALU kernels (what float32 tensors always run on) also for bf16, 0 / -1 = MFMA kernels for bf16
@@ -1638,16 +1609,12 @@ extern "C" int sl_window_attention_fwd(const SlWinDesc* d, const void* qkv, cons
   SL_REQUIRE(qkv && qkv_bias && rel_bias && out, "window_attention_fwd: null buffer");
   hipStream_t st = (hipStream_t)stream;
   const int nwin = g.B * g.nWy * g.nWx;
-  if (use_attn_mfma(d->dtype)) {
-    hipLaunchKernelGGL(window_attention_fwd_mfma_kernel, dim3(cdiv(nwin, 4) * g.heads), dim3(256), 0, st, g, (const bf16_t*)qkv, qkv_bias, rel_bias, (bf16_t*)out, nwin);
-    SL_LAUNCH_CHECK("window_attention_fwd_mfma_kernel");
-    return 0;
-  }
-  const int grid = nwin * g.heads;
-  BY_DTYPE(d->dtype, hipLaunchKernelGGL(window_attention_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, g, (const bf16_t*)qkv, qkv_bias, rel_bias, (bf16_t*)out),
-           hipLaunchKernelGGL(window_attention_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, g, (const float*)qkv, qkv_bias, rel_bias, (float*)out), "window_attention_fwd");
-  SL_LAUNCH_CHECK("window_attention_fwd_kernel");
-  return 0;
+  if (use_attn_mfma(d->dtype))
+    return sl_launch("window_attention_fwd_mfma_kernel", window_attention_fwd_mfma_kernel, dim3(cdiv(nwin, 4) * g.heads), dim3(256), 0, st, g, (const bf16_t*)qkv, qkv_bias, rel_bias, (bf16_t*)out, nwin);
+  return sl_by_dtype(d->dtype, "window_attention_fwd", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("window_attention_fwd_kernel", window_attention_fwd_kernel<T>, dim3(nwin * g.heads), dim3(256), 0, st, g, (const T*)qkv, qkv_bias, rel_bias, (T*)out);
+  });
 }
 
 // windows per block of the backward (more when there are many windows: fewer partial rows of the bias gradient)
@@ -1690,20 +1657,16 @@ __global__ void relpos_table_grad_kernel(const float* __restrict__ dbias, const 
 extern "C" int sl_relpos_table_grad(const float* dbias, const int* pairs, int rows, int m, int heads, int npair, float* dtable, sl_stream_t stream) {
   SL_REQUIRE(dbias && pairs && dtable && rows > 0 && m > 0 && heads > 0 && npair > 0, "relpos_table_grad: bad args");
   const int nrel = cdiv(rows * heads * 8, 256);
-  hipLaunchKernelGGL(relpos_table_grad_kernel, dim3(nrel), dim3(256), 0, (hipStream_t)stream, dbias, pairs, rows, m, heads, npair, dtable, nrel, (const float*)nullptr,
-                     (const float*)nullptr, (float*)nullptr);
-  SL_LAUNCH_CHECK("relpos_table_grad_kernel");
-  return 0;
+  return sl_launch("relpos_table_grad_kernel", relpos_table_grad_kernel, dim3(nrel), dim3(256), 0, (hipStream_t)stream, dbias, pairs, rows, m, heads, npair, dtable, nrel, (const float*)nullptr,
+                   (const float*)nullptr, (float*)nullptr);
 }
 
 extern "C" int sl_relpos_table_grad_bias(const float* dbias, const int* pairs, int rows, int m, int heads, int npair, float* dtable, const float* dbq_colsum,
                                          const float* dpad, float* dbq, sl_stream_t stream) {
   SL_REQUIRE(dbias && pairs && dtable && rows > 0 && m > 0 && heads > 0 && npair > 0 && dbq_colsum && dpad && dbq, "relpos_table_grad_bias: bad args");
   const int nrel = cdiv(rows * heads * 8, 256);
-  hipLaunchKernelGGL(relpos_table_grad_kernel, dim3(nrel + cdiv(3 * heads * 32, 256)), dim3(256), 0, (hipStream_t)stream, dbias, pairs, rows, m, heads, npair, dtable, nrel,
-                     dbq_colsum, dpad, dbq);
-  SL_LAUNCH_CHECK("relpos_table_grad_kernel");
-  return 0;
+  return sl_launch("relpos_table_grad_kernel", relpos_table_grad_kernel, dim3(nrel + cdiv(3 * heads * 32, 256)), dim3(256), 0, (hipStream_t)stream, dbias, pairs, rows, m, heads, npair, dtable, nrel,
+                   dbq_colsum, dpad, dbq);
 }
 
 extern "C" int sl_window_attention_bwd_chunks(const SlWinDesc* d) {
@@ -1730,27 +1693,15 @@ extern "C" int sl_window_attention_bwd(const SlWinDesc* d, const void* qkv, cons
   if (use_attn_bwd_mfma(d->dtype)) {
     const int wpw = win_wpw(g), chunks = cdiv(nwin, 4 * wpw);
     const size_t lds2 = (size_t)(WN * BLP + 16) * sizeof(float) + (size_t)4 * 3 * WB2_TILE + (size_t)4 * 256 * sizeof(float) + (size_t)WN * WB2_AP * sizeof(float);
-    static bool attr2 = false;
-    if (!attr2) {
-      (void)hipFuncSetAttribute((const void*)window_attention_bwd_mfma2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-      (void)hipFuncSetAttribute((const void*)window_attention_bwd_mfma2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-      attr2 = true;
-    }
-    if (g_sl_debug.attn_trace)      // debug instantiation (the stamps cost 8 registers and 6 spills: not in the production kernel)
-      hipLaunchKernelGGL(window_attention_bwd_mfma2_kernel<true>, dim3(chunks * g.heads), dim3(256), lds2, st, g, (const bf16_t*)qkv, qkv_bias, rel_bias, (const bf16_t*)dout,
-                         (bf16_t*)dqkv, drel_partial, pad_partial, wpw, nwin, g_sl_debug.attn_trace);
-    else
-      hipLaunchKernelGGL(window_attention_bwd_mfma2_kernel<false>, dim3(chunks * g.heads), dim3(256), lds2, st, g, (const bf16_t*)qkv, qkv_bias, rel_bias, (const bf16_t*)dout,
-                         (bf16_t*)dqkv, drel_partial, pad_partial, wpw, nwin, nullptr);
-    SL_LAUNCH_CHECK("window_attention_bwd_mfma2_kernel");
-    return 0;
+    // the debug instantiation takes the stamps (they cost 8 registers and 6 spills: not in the production kernel)
+    return sl_launch("window_attention_bwd_mfma2_kernel", g_sl_debug.attn_trace ? window_attention_bwd_mfma2_kernel<true> : window_attention_bwd_mfma2_kernel<false>, dim3(chunks * g.heads), dim3(256), lds2, st,
+                     g, (const bf16_t*)qkv, qkv_bias, rel_bias, (const bf16_t*)dout, (bf16_t*)dqkv, drel_partial, pad_partial, wpw, nwin, g_sl_debug.attn_trace);
   }
   const int wpb = win_wpb(g);
   const int chunks = cdiv(nwin, wpb);
-  BY_DTYPE(d->dtype,
-           hipLaunchKernelGGL(window_attention_bwd_kernel<bf16_t>, dim3(chunks * g.heads), dim3(256), 0, st, g, (const bf16_t*)qkv, qkv_bias, rel_bias, (const bf16_t*)dout, (bf16_t*)dqkv, drel_partial, pad_partial, wpb, nwin),
-           hipLaunchKernelGGL(window_attention_bwd_kernel<float>, dim3(chunks * g.heads), dim3(256), 0, st, g, (const float*)qkv, qkv_bias, rel_bias, (const float*)dout, (float*)dqkv, drel_partial, pad_partial, wpb, nwin),
-           "window_attention_bwd");
-  SL_LAUNCH_CHECK("window_attention_bwd_kernel");
-  return 0;
+  return sl_by_dtype(d->dtype, "window_attention_bwd", [&](auto t) -> int {
+    using T = decltype(t);
+    return sl_launch("window_attention_bwd_kernel", window_attention_bwd_kernel<T>, dim3(chunks * g.heads), dim3(256), 0, st, g, (const T*)qkv, qkv_bias, rel_bias, (const T*)dout, (T*)dqkv, drel_partial,
+                     pad_partial, wpb, nwin);
+  });
 }
