@@ -441,6 +441,29 @@ int sl_upsample_ce_weighted_fwd(const float* logits, const int64_t* target, cons
 int sl_upsample_ce_weighted_bwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing,
                                 const float* loss_and_count, const float* gscale, int B, int K, int h, int w, int H, int W,
                                 int ignore_index, float* dlogits, sl_stream_t stream);
+/* Hybrid criterion: the cross-entropy above (plain, or weighted + smoothed) plus multiclass soft Dice with softmax (the MulticlassHybridLoss swap commented out at
+ * loss/criterion.py:34), from ONE evaluation of every pixel's softmax.  With p = softmax of the upsampled logits and the valid pixels of sample b (label != ignore_index
+ * and inside [0, K)):  I[b][c] = sum p_c [t == c],  P[b][c] = sum p_c,  T[b][c] = sum [t == c],
+ *   dice = mean_b sum_c w_c (1 - (2 I + smooth) / (P + T + smooth));  ignored pixels enter none of the three sums (a sample without a valid pixel has Dice 0).
+ * class_weight: K floats on the device or NULL (weights of one; with label_smoothing == 0 the cross-entropy part then runs the plain arithmetic).
+ * All four: 1 <= K <= 33, 0 <= label_smoothing <= 1, smooth finite and > 0, no NULL buffer but class_weight, else SL_EINVAL before any launch.  No atomics: two runs
+ * give the same bits.
+ * sl_upsample_ce_dice_rows: rows of the partial buffer, B * (rows per sample); a row holds 2 + 3 K floats and never mixes samples:
+ *   partial[b * rows/B + j][2 + 3K] = (cross-entropy numerator, denominator, I[0..K), P[0..K), T[0..K)) of block j of sample b */
+int sl_upsample_ce_dice_rows(int B, int H, int W);
+int sl_upsample_ce_dice_fwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing,
+                            int B, int K, int h, int w, int H, int W, int ignore_index, float* partial, sl_stream_t stream);
+/* One block, in double, in a fixed order: loss3 = (cross-entropy, its denominator, dice) and the backward's table coef[B][K][2] = (a, g),
+ * a = -2 w_c / (B D), g = w_c N / (B D^2), N = 2 I + smooth, D = P + T + smooth. */
+int sl_upsample_ce_dice_finalize(const float* partial, const float* class_weight, float smooth, int B, int K, int H, int W,
+                                 float* loss3, float* coef, sl_stream_t stream);
+/* dlogits = transposed bilinear weights applied to  gscale[0] / loss3[1] * (cross-entropy gradient of the pixel) + gscale[1] * p_k (q_k - sum_c p_c q_c),
+ * q_c = g[b][c] + a[b][c] [c == t]: one launch for both upstream gradients (gscale: 2 floats on the device), the Dice weight never enters a kernel.
+ * Same three kernel routes (and sl_debug_ce_tiled hook) as sl_upsample_ce_bwd; the tiled kernels keep the 2 K coefficients of the block's sample in the LDS and the
+ * channel-sliced one a fourth word per footprint pixel (sum_c p_c q_c); where that passes 150 KiB the plan takes more slices, then the gather kernel. */
+int sl_upsample_ce_dice_bwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing,
+                            const float* loss3, const float* coef, const float* gscale, int B, int K, int h, int w, int H, int W,
+                            int ignore_index, float* dlogits, sl_stream_t stream);
 /* pspnet_pop.py:221-231: argmax of the upsampled (align_corners=True) [K2][h][w] logits of tile b, ids > 0 shifted
  * by n_base, written into mask[b] where mask == 0 (in place, int64). */
 int sl_pseudo_label(const float* logits, int K2, int h, int w, int64_t* mask, int B, int H, int W, int n_base,

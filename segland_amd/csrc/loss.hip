@@ -18,6 +18,21 @@ struct UpGeom { int B, K, h, w, H, W; float sy, sx; };
 template <bool WT> struct CeW {};
 template <> struct CeW<true> { const float* w; float keep, epsk; };   // w[K] on the device, keep = 1 - eps, epsk = eps / K
 
+// The hybrid form (cross-entropy + multiclass soft Dice with softmax, the MulticlassHybridLoss swap of loss/criterion.py:34) of the backward kernels: <DC = true>.
+// Over the valid pixels of sample b:  I_c = sum p_c [t == c],  P_c = sum p_c,  T_c = sum [t == c],  dice = mean_b sum_c w_c (1 - N_c / D_c),  N = 2 I + smooth,
+// D = P + T + smooth.  With the table coef[b][c] = (a, g) = (-2 w_c / (B D), w_c N / (B D^2)) of the finalize kernel and q_c = g_c + a_c [c == t]
+//   d dice / d v_k = p_k (q_k - sum_c p_c q_c),
+// added to the pixel's cross-entropy gradient BEFORE the bilinear scatter: per-pixel gradient = f0 * (cross-entropy form) + f1 * (Dice form), f0 = gscale[0] / denominator,
+// f1 = gscale[1].  CeD<false> is empty and every statement of the hybrid form sits under `if constexpr (DC)`: the <DC = false> instantiations are the kernels as they were.
+// In the hybrid kernels the class-weight pointer may be null (weights of one): cew_at.
+template <bool DC> struct CeD {};
+template <> struct CeD<true> { const float* coef; };                  // [B][K][2] on the device
+template <bool DC>
+__device__ __forceinline__ float cew_at(const CeW<true>& cw, int k) {
+  if constexpr (DC) return cw.w ? cw.w[k] : 1.f;
+  else return cw.w[k];
+}
+
 __host__ inline float ac1_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 
 // ATen upsample_bilinear2d source index, align_corners = True
@@ -101,12 +116,126 @@ __global__ void upsample_ce_finalize_kernel(const float* __restrict__ part, int 
   if (threadIdx.x == 0) { out[0] = (float)(rs[0] / rc[0]); out[1] = (float)rc[0]; }
 }
 
+// Forward of the hybrid form.  Block blockIdx.x = b * nbs + j strides over the H * W pixels of sample b alone (a row of partials never mixes samples), evaluates each
+// pixel's softmax once and reduces the cross-entropy partials (the arithmetic of upsample_ce_fwd_kernel) and the per-class Dice sums:
+//   part[blk][2 + 3K] = (cross-entropy numerator, denominator, I[0..K), P[0..K), T[0..K))
+template <int KW, bool WT>
+__global__ __launch_bounds__(256) void upsample_ce_dice_fwd_kernel(UpGeom g, int nbs, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
+                                                                   int ignore, float* __restrict__ part, CeW<WT> cw) {
+  __shared__ float red[4][2 + 3 * KW];
+  const int b = blockIdx.x / nbs, jb = blockIdx.x - b * nbs;
+  const int hw = g.H * g.W;
+  const int64_t* tb = tgt + (size_t)b * hw;
+  float loss = 0.f, cnt = 0.f;
+  float si[KW], sp[KW], st[KW];
+#pragma unroll
+  for (int k = 0; k < KW; ++k) { si[k] = 0.f; sp[k] = 0.f; st[k] = 0.f; }
+  const int stride = nbs * 256;
+  int i = jb * 256 + (int)threadIdx.x;
+  long long tn = i < hw ? tb[i] : -1;                  // the next label is in flight while this pixel is evaluated
+  for (; i < hw; i += stride) {
+    const long long t = tn;
+    tn = i + stride < hw ? tb[i + stride] : -1;
+    if (t == ignore || t < 0 || t >= g.K) continue;
+    const int Y = i / g.W, X = i - Y * g.W;
+    float v[KW], e[KW];
+    pixel_logits<KW>(g, lg, b, Y, X, v);
+    float m = v[0], vt = 0.f;
+#pragma unroll
+    for (int k = 0; k < KW; ++k) { m = fmaxf(m, v[k]); if (k == (int)t) vt = v[k]; }
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < KW; ++k) { e[k] = k < g.K ? expf(v[k] - m) : 0.f; if (k < g.K) s += e[k]; }
+    if constexpr (WT) {
+      const float lse = logf(s) + m, wt = cew_at<true>(cw, (int)t);
+      float sm = 0.f;                                   // sum_k w_k (-logp_k), in index order
+#pragma unroll
+      for (int k = 0; k < KW; ++k) if (k < g.K) sm += cew_at<true>(cw, k) * (lse - v[k]);
+      loss += cw.keep * wt * (lse - vt) + cw.epsk * sm;
+      cnt += wt;
+    } else {
+      loss += logf(s) + m - vt;
+      cnt += 1.f;
+    }
+    const float inv = 1.f / s;
+#pragma unroll
+    for (int k = 0; k < KW; ++k) {
+      const float p = e[k] * inv;
+      sp[k] += p;
+      si[k] += k == (int)t ? p : 0.f;
+      st[k] += k == (int)t ? 1.f : 0.f;
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  loss = wave_sum(loss); cnt = wave_sum(cnt);
+  if (lane == 0) { red[wave][0] = loss; red[wave][1] = cnt; }
+#pragma unroll
+  for (int k = 0; k < KW; ++k) {
+    if (k < g.K) {                                      // uniform: every lane of the wave takes the shuffles
+      const float a = wave_sum(si[k]), p = wave_sum(sp[k]), c = wave_sum(st[k]);
+      if (lane == 0) { red[wave][2 + k] = a; red[wave][2 + g.K + k] = p; red[wave][2 + 2 * g.K + k] = c; }
+    }
+  }
+  __syncthreads();
+  const int ncol = 2 + 3 * g.K;
+  if ((int)threadIdx.x < ncol) part[(size_t)blockIdx.x * ncol + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// One block of 1024 threads sums the partial rows in double, in a fixed order (no atomics), CB samples at a time: thread (sample, q, c) adds the rows q, q + RS, ... of
+// column c, threads (sample, c) add the RS strands, threads (sample, k) turn (I, P, T) into the sample's Dice terms and the backward's coefficients, thread 0 keeps the
+// running sums over the samples in index order.  out = (cross-entropy, its denominator, dice);  coef[b][k] = (a, g) = (-2 w_k / (B D), w_k N / (B D^2)).
+__global__ __launch_bounds__(1024) void upsample_ce_dice_finalize_kernel(const float* __restrict__ part, int B, int K, int nbs, const float* __restrict__ w, double smooth,
+                                                                         float* __restrict__ out, float* __restrict__ coef) {
+  __shared__ double sh[1024], col[256], term[85];
+  const int tid = threadIdx.x, ncol = 2 + 3 * K;
+  const int RS = ncol <= 64 ? 4 : 1024 / ncol;         // four strands and 4 .. 51 samples per round (CB * ncol <= 256, CB * K <= 84); above 20 channels all threads on one sample (ncol <= 101)
+  const int per = RS * ncol, CB = 1024 / per;
+  double ce_n = 0.0, ce_d = 0.0, dice = 0.0;
+  for (int b0 = 0; b0 < B; b0 += CB) {
+    const int nb = min(CB, B - b0);
+    {
+      const int sb = tid / per, rem = tid - sb * per, q = rem / ncol, c = rem - q * ncol;
+      double s = 0.0;
+      if (sb < nb) for (int r = q; r < nbs; r += RS) s += (double)part[((size_t)(b0 + sb) * nbs + r) * ncol + c];
+      sh[tid] = s;
+    }
+    __syncthreads();
+    if (tid < nb * ncol) {
+      const int sb = tid / ncol, c = tid - sb * ncol;
+      double a = 0.0;
+      for (int q = 0; q < RS; ++q) a += sh[sb * per + q * ncol + c];
+      col[tid] = a;
+    }
+    __syncthreads();
+    if (tid < nb * K) {
+      const int sb = tid / K, k = tid - sb * K, b = b0 + sb;
+      const double* cs = col + sb * ncol;
+      const double wk = w ? (double)w[k] : 1.0;
+      const double N = 2.0 * cs[2 + k] + smooth, D = cs[2 + K + k] + cs[2 + 2 * K + k] + smooth;
+      term[tid] = wk * (1.0 - N / D);
+      coef[((size_t)b * K + k) * 2 + 0] = (float)(-2.0 * wk / ((double)B * D));
+      coef[((size_t)b * K + k) * 2 + 1] = (float)(wk * N / ((double)B * D * D));
+    }
+    __syncthreads();
+    if (tid == 0) {
+      for (int sb = 0; sb < nb; ++sb) {
+        ce_n += col[sb * ncol]; ce_d += col[sb * ncol + 1];
+        double d = 0.0;
+        for (int k = 0; k < K; ++k) d += term[sb * K + k];
+        dice += d;
+      }
+    }
+    // the next round writes sh first (last read before the second barrier), col after its first barrier and term after its second: thread 0 is past its reads by then
+  }
+  if (tid == 0) { out[0] = (float)(ce_n / ce_d); out[1] = (float)ce_d; out[2] = (float)(dice / (double)B); }
+}
+
 // four lanes per low-resolution cell (each takes every 4th footprint row), gather over the pixels whose bilinear
 // footprint touches the cell, then a 4-lane shuffle reduction: deterministic, no atomics.
-template <int KW, bool WT>
+template <int KW, bool WT, bool DC>
 __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
                                                               const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
-                                                              int ignore, float* __restrict__ dlg, CeW<WT> cw) {
+                                                              int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd) {
   const long long cells = (long long)g.B * g.h * g.w;
   const long long ci = (blockIdx.x * 256LL + threadIdx.x) >> 2;
   const int sub = threadIdx.x & 3;
@@ -124,7 +253,16 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
   float wsum = 0.f;
   if constexpr (WT) {
 #pragma unroll
-    for (int k = 0; k < KW; ++k) if (k < g.K) wsum += cw.w[k];
+    for (int k = 0; k < KW; ++k) if (k < g.K) wsum += cew_at<DC>(cw, k);
+  }
+  float qa[DC ? KW : 1], qg[DC ? KW : 1], f0 = 0.f, f1 = 0.f;      // DC: the (a, g) of this cell's sample and the two scales
+  if constexpr (DC) {
+    f0 = gscale[0] / loss_cnt[1]; f1 = gscale[1];
+#pragma unroll
+    for (int k = 0; k < KW; ++k) {
+      qa[k] = k < g.K ? cd.coef[((size_t)b * g.K + k) * 2] : 0.f;
+      qg[k] = k < g.K ? cd.coef[((size_t)b * g.K + k) * 2 + 1] : 0.f;
+    }
   }
   if (live) {
     for (int Y = Ylo + sub; Y <= Yhi; Y += 4) {
@@ -148,7 +286,22 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
 #pragma unroll
         for (int k = 0; k < KW; ++k) { v[k] = k < g.K ? expf(v[k] - m) : 0.f; s += v[k]; }
         const float wgt = wy * wx, inv = 1.f / s;
-        if constexpr (WT) {
+        if constexpr (DC) {
+          float sq = 0.f;                                 // sum_c p_c q_c, in index order
+#pragma unroll
+          for (int k = 0; k < KW; ++k) { v[k] *= inv; sq += v[k] * (qg[k] + (k == (int)t ? qa[k] : 0.f)); }
+          float hit = 1.f, ct = 1.f;
+          if constexpr (WT) { hit = cw.keep * cew_at<DC>(cw, (int)t); ct = hit + cw.epsk * wsum; }
+#pragma unroll
+          for (int k = 0; k < KW; ++k) {
+            if (k < g.K) {
+              float ce;
+              if constexpr (WT) ce = v[k] * ct - ((k == (int)t ? hit : 0.f) + cw.epsk * cew_at<DC>(cw, k));
+              else ce = v[k] - (k == (int)t ? 1.f : 0.f);
+              acc[k] += wgt * (f0 * ce + f1 * (v[k] * ((qg[k] + (k == (int)t ? qa[k] : 0.f)) - sq)));
+            }
+          }
+        } else if constexpr (WT) {
           const float hit = cw.keep * cw.w[t], ct = hit + cw.epsk * wsum;
 #pragma unroll
           for (int k = 0; k < KW; ++k) if (k < g.K) acc[k] += wgt * (v[k] * inv * ct - ((k == (int)t ? hit : 0.f) + cw.epsk * cw.w[k]));
@@ -159,7 +312,8 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
       }
     }
   }
-  const float f = gscale[0] / loss_cnt[1];
+  float f = 1.f;                                        // DC: the scales are inside the pixel gradients
+  if constexpr (!DC) f = gscale[0] / loss_cnt[1];
 #pragma unroll
   for (int k = 0; k < KW; ++k) {
     float a = acc[k];
@@ -175,10 +329,10 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
 // Sums run in a fixed order (deterministic); they are associated differently from the gather kernel (last-bit differences).
 constexpr int CT = 4;
 struct UpTile { int NYmax, NXmax; };
-template <int NT, bool WT>
+template <int NT, bool WT, bool DC>
 __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpTile ut, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
                                                                     const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
-                                                                    int ignore, float* __restrict__ dlg, CeW<WT> cw) {
+                                                                    int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int KW = KNC;                            // this kernel serves K <= KNC (G holds all K channels of every footprint pixel)
   const int K = g.K;
@@ -191,6 +345,8 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
   float* G = H1 + ut.NYmax * CT * K;                 // [NY][NX][K]
   float* wl = nullptr;                               // WT: [K] class weights behind G (the host adds K floats to the launch's LDS)
   if constexpr (WT) wl = G + (size_t)ut.NYmax * ut.NXmax * K;
+  float* cf = nullptr;                               // DC: [K][2] Dice coefficients (a, g) of this block's sample behind G / wl (the host adds 2 K floats)
+  if constexpr (DC) cf = G + (size_t)ut.NYmax * ut.NXmax * K + (WT ? K : 0);
   const int tid = threadIdx.x;
   const int tw = cdiv(g.w, CT), th = cdiv(g.h, CT);
   int blk = blockIdx.x;
@@ -209,7 +365,8 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
     const int yy = min(max(i0 - 1 + cy, 0), g.h - 1), xx = min(max(j0 - 1 + cx, 0), g.w - 1);
     lgt[e] = lb[((size_t)k * g.h + yy) * g.w + xx];
   }
-  if constexpr (WT) for (int e = tid; e < K; e += NT) wl[e] = cw.w[e];
+  if constexpr (WT) for (int e = tid; e < K; e += NT) wl[e] = cew_at<DC>(cw, e);
+  if constexpr (DC) for (int e = tid; e < 2 * K; e += NT) cf[e] = cd.coef[(size_t)b * K * 2 + e];
   for (int e = tid; e < NY; e += NT) {
     int y0, y1; float ly; src_index_ac1(Ylo + e, g.h, g.sy, y0, y1, ly);
     wy0[3 * e] = __int_as_float(y0); wy0[3 * e + 1] = __int_as_float(y1); wy0[3 * e + 2] = ly;
@@ -235,6 +392,8 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
   }
   float wsum = 0.f;
   if constexpr (WT) for (int k = 0; k < K; ++k) wsum += wl[k];
+  float f0 = 0.f, f1 = 0.f;
+  if constexpr (DC) { f0 = gscale[0] / loss_cnt[1]; f1 = gscale[1]; }
 #pragma unroll 1
   for (int u = 0; tid + NT * u < NY * NX; ++u) {
     const int pix = tid + NT * u;
@@ -272,7 +431,22 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
 #pragma unroll
     for (int k = 0; k < KW; ++k) { v[k] = k < K ? __expf(v[k] - m) : 0.f; ssum += v[k]; }      // hardware exp2-based: 2 ulp, the gradient's tolerance is 1e-3
     const float inv = 1.f / ssum;
-    if constexpr (WT) {
+    if constexpr (DC) {
+      float sq = 0.f;                                  // sum_c p_c q_c, in index order
+#pragma unroll
+      for (int k = 0; k < KW; ++k) if (k < K) { v[k] *= inv; sq += v[k] * (cf[2 * k + 1] + (k == (int)t ? cf[2 * k] : 0.f)); }
+      float hit = 1.f, ct = 1.f;
+      if constexpr (WT) { hit = cw.keep * wl[t]; ct = hit + cw.epsk * wsum; }
+#pragma unroll
+      for (int k = 0; k < KW; ++k) {
+        if (k < K) {
+          float ce;
+          if constexpr (WT) ce = v[k] * ct - ((k == (int)t ? hit : 0.f) + cw.epsk * wl[k]);
+          else ce = v[k] - (k == (int)t ? 1.f : 0.f);
+          out[k] = f0 * ce + f1 * (v[k] * ((cf[2 * k + 1] + (k == (int)t ? cf[2 * k] : 0.f)) - sq));
+        }
+      }
+    } else if constexpr (WT) {
       const float hit = cw.keep * wl[t], ct = hit + cw.epsk * wsum;
 #pragma unroll
       for (int k = 0; k < KW; ++k) if (k < K) out[k] = v[k] * inv * ct - ((k == (int)t ? hit : 0.f) + cw.epsk * wl[k]);
@@ -296,7 +470,8 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
   }
   __syncthreads();
   // ---- pass 2b: along Y, scale, store
-  const float f = gscale[0] / loss_cnt[1];
+  float f = 1.f;                                     // DC: the scales are inside G
+  if constexpr (!DC) f = gscale[0] / loss_cnt[1];
   for (int e = tid; e < CT * CT * K; e += NT) {
     const int k = e % K, c = e / K, ir = c / CT, jr = c - ir * CT;
     const int i = i0 + ir, j = j0 + jr;
@@ -331,22 +506,25 @@ __device__ __forceinline__ UpTap up_tap(const float* lgt, const float* wy0, cons
   t.q10 = lgt + (ry1 * (CT + 2) + rx0) * K; t.q11 = lgt + (ry1 * (CT + 2) + rx1) * K;
   return t;
 }
-template <int NT, bool WT>
+template <int NT, bool WT, bool DC>
 __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g, UpTileW ut, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
                                                                          const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
-                                                                         int ignore, float* __restrict__ dlg, CeW<WT> cw) {
+                                                                         int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
+  constexpr int SW = DC ? 4 : 3;                     // statistics words per footprint pixel; DC: the fourth is sum_c p_c q_c over ALL K channels
   const int K = g.K, KS = ut.KS;
   float* lgt = sm;                                   // [(CT+2)^2][K]
   float* wy0 = lgt + (CT + 2) * (CT + 2) * K;        // as in the one-pass kernel
   float* wx0 = wy0 + 3 * ut.NYmax;
   float* wxj = wx0 + 3 * ut.NXmax;                   // [NX][CT]
   float* wyi = wxj + CT * ut.NXmax;                  // [NY][CT]
-  float* st = wyi + CT * ut.NYmax;                   // [NY][NX][3]: max, 1 / sum, label as int (-1: the pixel does not count)
-  float* H1 = st + 3 * ut.NYmax * ut.NXmax;          // [NY][CT][KS]
+  float* st = wyi + CT * ut.NYmax;                   // [NY][NX][SW]: max, 1 / sum, label as int (-1: the pixel does not count)
+  float* H1 = st + SW * ut.NYmax * ut.NXmax;         // [NY][CT][KS]
   float* G = H1 + ut.NYmax * CT * KS;                // [NY][NX][KS]
   float* wl = nullptr;                               // WT: [K] class weights behind G (the host adds K floats to the launch's LDS)
   if constexpr (WT) wl = G + (size_t)ut.NYmax * ut.NXmax * KS;
+  float* cf = nullptr;                               // DC: [K][2] Dice coefficients (a, g) of this block's sample behind G / wl (the host adds 2 K floats)
+  if constexpr (DC) cf = G + (size_t)ut.NYmax * ut.NXmax * KS + (WT ? K : 0);
   const int tid = threadIdx.x;
   const int tw = cdiv(g.w, CT), th = cdiv(g.h, CT);
   int blk = blockIdx.x;
@@ -365,7 +543,8 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
     const int yy = min(max(i0 - 1 + cy, 0), g.h - 1), xx = min(max(j0 - 1 + cx, 0), g.w - 1);
     lgt[e] = lb[((size_t)k * g.h + yy) * g.w + xx];
   }
-  if constexpr (WT) for (int e = tid; e < K; e += NT) wl[e] = cw.w[e];
+  if constexpr (WT) for (int e = tid; e < K; e += NT) wl[e] = cew_at<DC>(cw, e);
+  if constexpr (DC) for (int e = tid; e < 2 * K; e += NT) cf[e] = cd.coef[(size_t)b * K * 2 + e];
   for (int e = tid; e < NY; e += NT) {
     int y0, y1; float ly; src_index_ac1(Ylo + e, g.h, g.sy, y0, y1, ly);
     wy0[3 * e] = __int_as_float(y0); wy0[3 * e + 1] = __int_as_float(y1); wy0[3 * e + 2] = ly;
@@ -383,17 +562,25 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
   for (int pix = tid; pix < NY * NX; pix += NT) {
     const int yr = pix / NX, xr = pix - yr * NX;
     const long long t = tgt[((size_t)b * g.H + Ylo + yr) * g.W + Xlo + xr];
-    float* s = st + 3 * pix;
+    float* s = st + SW * pix;
     if (t == ignore || t < 0 || t >= K) { s[2] = __int_as_float(-1); continue; }
     const UpTap tap = up_tap(lgt, wy0, wx0, yr, xr, i0, j0, K);
     float m = -INFINITY;
     for (int k = 0; k < K; ++k) m = fmaxf(m, tap.at(k));
     float ssum = 0.f;
-    for (int k = 0; k < K; ++k) ssum += __expf(tap.at(k) - m);
+    if constexpr (DC) {
+      float sq = 0.f;                                  // sum_c e_c q_c from the same exponentials, in index order
+      for (int k = 0; k < K; ++k) { const float e = __expf(tap.at(k) - m); ssum += e; sq += e * (cf[2 * k + 1] + (k == (int)t ? cf[2 * k] : 0.f)); }
+      s[3] = sq * (1.f / ssum);
+    } else {
+      for (int k = 0; k < K; ++k) ssum += __expf(tap.at(k) - m);
+    }
     s[0] = m; s[1] = 1.f / ssum; s[2] = __int_as_float((int)t);
   }
   __syncthreads();
-  const float f = gscale[0] / loss_cnt[1];
+  const float f = gscale[0] / loss_cnt[1];           // DC: f0, applied per pixel with f1 before the separable passes
+  float f1 = 0.f;
+  if constexpr (DC) f1 = gscale[1];
   float wsum = 0.f;
   if constexpr (WT) for (int k = 0; k < K; ++k) wsum += wl[k];
   for (int k0 = 0; k0 < K; k0 += KS) {
@@ -401,7 +588,7 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
     // ---- pass 1: softmax - onehot of the slice's channels
     for (int pix = tid; pix < NY * NX; pix += NT) {
       const int yr = pix / NX, xr = pix - yr * NX;
-      const float* s = st + 3 * pix;
+      const float* s = st + SW * pix;
       float* out = G + (size_t)pix * KS;
       const int t = __float_as_int(s[2]);
       if (t < 0) {
@@ -410,7 +597,19 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
       }
       const UpTap tap = up_tap(lgt, wy0, wx0, yr, xr, i0, j0, K);
       const float m = s[0], inv = s[1];
-      if constexpr (WT) {
+      if constexpr (DC) {
+        const float sq = s[3];
+        float hit = 1.f, ct = 1.f;
+        if constexpr (WT) { hit = cw.keep * wl[t]; ct = hit + cw.epsk * wsum; }
+        for (int kk = 0; kk < kn; ++kk) {
+          const int k = k0 + kk;
+          const float p = __expf(tap.at(k) - m) * inv;
+          float ce;
+          if constexpr (WT) ce = p * ct - ((k == t ? hit : 0.f) + cw.epsk * wl[k]);
+          else ce = p - (k == t ? 1.f : 0.f);
+          out[kk] = f * ce + f1 * (p * ((cf[2 * k + 1] + (k == t ? cf[2 * k] : 0.f)) - sq));
+        }
+      } else if constexpr (WT) {
         const float hit = cw.keep * wl[t], ct = hit + cw.epsk * wsum;
         for (int kk = 0; kk < kn; ++kk) out[kk] = __expf(tap.at(k0 + kk) - m) * inv * ct - ((k0 + kk == t ? hit : 0.f) + cw.epsk * wl[k0 + kk]);
       } else {
@@ -439,7 +638,8 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
       const int ya = g.sy > 0.f ? max(Ylo, (int)floorf((float)(i - 1) / g.sy)) : Ylo, yb = g.sy > 0.f ? min(Yhi, (int)ceilf((float)(i + 1) / g.sy)) : Yhi;
       float acc = 0.f;
       for (int yr = ya - Ylo; yr <= yb - Ylo; ++yr) acc += wyi[yr * CT + ir] * H1[(yr * CT + jr) * KS + kk];
-      dlg[(((size_t)b * K + k0 + kk) * g.h + i) * g.w + j] = acc * f;
+      if constexpr (DC) dlg[(((size_t)b * K + k0 + kk) * g.h + i) * g.w + j] = acc;
+      else dlg[(((size_t)b * K + k0 + kk) * g.h + i) * g.w + j] = acc * f;
     }
   }
 }
@@ -582,24 +782,42 @@ int launch_ce_fwd(const UpGeom& g, const float* logits, const int64_t* target, i
   return sl_launch("upsample_ce_fwd_kernel", g.K <= KNC ? upsample_ce_fwd_kernel<KNC, WT> : upsample_ce_fwd_kernel<KMAXC, WT>, dim3(nblk), dim3(256), 0, stream, g, logits, target, ignore_index, partial, cw);
 }
 
+// nbs: blocks per sample of the hybrid forward (its partial buffer has B * nbs rows).  About 1024 blocks in all, a quarter of the plain forward's: a block ends in 3 K wave
+// reductions and the one finalize block reads every row, so a thread takes ~16 pixels at the bench shape instead of 4.
+inline int ce_dice_blocks(int B, long long hw) {
+  const long long need = (hw + 255) / 256, cap = 1024 / B;
+  return (int)(need < 1 ? 1 : (need > cap ? (cap < 1 ? 1 : cap) : need));
+}
+
 template <bool WT>
+int launch_ce_dice_fwd(const UpGeom& g, const float* logits, const int64_t* target, int ignore_index, float* partial, hipStream_t stream, CeW<WT> cw) {
+  const int nbs = ce_dice_blocks(g.B, (long long)g.H * g.W);
+  // three per-thread accumulators per channel: a width of 8 (the bench head) keeps the kernel at twice the waves per SIMD of the width of 16
+  return sl_launch("upsample_ce_dice_fwd_kernel", g.K <= 8 ? upsample_ce_dice_fwd_kernel<8, WT> : g.K <= KNC ? upsample_ce_dice_fwd_kernel<KNC, WT> : upsample_ce_dice_fwd_kernel<KMAXC, WT>,
+                   dim3((unsigned)(g.B * nbs)), dim3(256), 0, stream,
+                   g, nbs, logits, target, ignore_index, partial, cw);
+}
+
+// DC (the hybrid form): the tiled kernels keep 2 K coefficients more in the LDS and the channel-sliced one a fourth word per footprint pixel; the same 150 KiB limit decides
+// (more slices, then the gather kernel).  loss_and_count is then the finalize's (cross-entropy, denominator, dice) and gscale holds two values.
+template <bool WT, bool DC = false>
 int launch_ce_bwd(const UpGeom& g, const float* logits, const int64_t* target, const float* loss_and_count, const float* gscale, int ignore_index, float* dlogits,
-                  hipStream_t stream, CeW<WT> cw) {
+                  hipStream_t stream, CeW<WT> cw, CeD<DC> cd = CeD<DC>()) {
   const int B = g.B, K = g.K, h = g.h, w = g.w, H = g.H, W = g.W;
   const long long cells = (long long)B * h * w;
-  const size_t wl = WT ? (size_t)K : 0;              // the weighted kernels keep the K class weights behind G
+  const size_t wl = (WT ? (size_t)K : 0) + (DC ? 2 * (size_t)K : 0);              // the weighted kernels keep the K class weights behind G, the hybrid ones 2 K coefficients
   // tiled kernel when the joint footprint of a CT x CT cell tile fits the LDS (always for an upsampling factor <= ~12 at K <= 16); test hook sl_debug_ce_tiled(0): never
   if (g.sy > 0.f && g.sx > 0.f && g_sl_debug.ce_tiled && K > KNC) {
     // channel-sliced form: the fewest slices (of at most KNC channels) whose G and H1 fit next to the per-pixel statistics
     UpTileW ut;
     ut.NYmax = (int)ceilf((float)(CT + 1) / g.sy) + 3; if (ut.NYmax > H) ut.NYmax = H;
     ut.NXmax = (int)ceilf((float)(CT + 1) / g.sx) + 3; if (ut.NXmax > W) ut.NXmax = W;
-    const size_t fixed = (size_t)(CT + 2) * (CT + 2) * K + (3 + CT) * (ut.NYmax + ut.NXmax) + 3 * (size_t)ut.NYmax * ut.NXmax + wl;
+    const size_t fixed = (size_t)(CT + 2) * (CT + 2) * K + (3 + CT) * (ut.NYmax + ut.NXmax) + (DC ? 4 : 3) * (size_t)ut.NYmax * ut.NXmax + wl;
     for (int ns = cdiv(K, KNC); ns <= K; ++ns) {
       ut.KS = cdiv(K, ns);
       const size_t lds = (fixed + (size_t)ut.NYmax * CT * ut.KS + (size_t)ut.NYmax * ut.NXmax * ut.KS) * sizeof(float);
       if (lds > 150 * 1024) continue;
-      return sl_launch("upsample_ce_bwd_tiled_wide_kernel", upsample_ce_bwd_tiled_wide_kernel<512, WT>, dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(512), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw);
+      return sl_launch("upsample_ce_bwd_tiled_wide_kernel", upsample_ce_bwd_tiled_wide_kernel<512, WT, DC>, dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(512), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw, cd);
     }
   } else if (g.sy > 0.f && g.sx > 0.f && g_sl_debug.ce_tiled) {
     UpTile ut;
@@ -610,11 +828,11 @@ int launch_ce_bwd(const UpGeom& g, const float* logits, const int64_t* target, c
 #ifndef SL_UPCE_NT
 #define SL_UPCE_NT 512      // threads per block of the tiled kernel (A/B build: 256)
 #endif
-      return sl_launch("upsample_ce_bwd_tiled_kernel", upsample_ce_bwd_tiled_kernel<SL_UPCE_NT, WT>, dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(SL_UPCE_NT), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw);
+      return sl_launch("upsample_ce_bwd_tiled_kernel", upsample_ce_bwd_tiled_kernel<SL_UPCE_NT, WT, DC>, dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(SL_UPCE_NT), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw, cd);
     }
   }
-  return sl_launch("upsample_ce_bwd_kernel", K <= KNC ? upsample_ce_bwd_kernel<KNC, WT> : upsample_ce_bwd_kernel<KMAXC, WT>, dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, stream, g, logits, target,
-                   loss_and_count, gscale, ignore_index, dlogits, cw);
+  return sl_launch("upsample_ce_bwd_kernel", K <= KNC ? upsample_ce_bwd_kernel<KNC, WT, DC> : upsample_ce_bwd_kernel<KMAXC, WT, DC>, dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, stream, g, logits, target,
+                   loss_and_count, gscale, ignore_index, dlogits, cw, cd);
 }
 
 inline CeW<true> make_cew(const float* class_weight, float label_smoothing, int K) {
@@ -666,6 +884,45 @@ extern "C" int sl_upsample_ce_weighted_bwd(const float* logits, const int64_t* t
   SL_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, "upsample_ce_weighted_bwd: label_smoothing %g outside [0, 1]", (double)label_smoothing);
   return launch_ce_bwd<true>(make_up(B, K, h, w, H, W), logits, target, loss_and_count, gscale, ignore_index, dlogits, (hipStream_t)stream,
                              make_cew(class_weight, label_smoothing, K));
+}
+
+// ---- hybrid cross-entropy + soft Dice (loss/criterion.py:34).  class_weight may be null: weights of one; with label_smoothing == 0 the cross-entropy part is then the plain form.
+#define SL_CE_DICE_COMMON(what)                                                                                                                  \
+  SL_REQUIRE(K >= 1 && K <= KMAXC, what ": %d logit channels; this build holds at most %d", K, KMAXC);                                          \
+  SL_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, what ": label_smoothing %g outside [0, 1]", (double)label_smoothing);             \
+  SL_REQUIRE(B > 0 && h > 0 && w > 0 && H > 0 && W > 0 && (long long)H * W < (1LL << 30), what ": bad shape")
+
+extern "C" int sl_upsample_ce_dice_rows(int B, int H, int W) { return B > 0 && H > 0 && W > 0 ? B * ce_dice_blocks(B, (long long)H * W) : 0; }
+
+extern "C" int sl_upsample_ce_dice_fwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing,
+                                       int B, int K, int h, int w, int H, int W, int ignore_index, float* partial, sl_stream_t stream) {
+  SL_CE_DICE_COMMON("upsample_ce_dice_fwd");
+  SL_REQUIRE(logits && target && partial, "upsample_ce_dice_fwd: null buffer");
+  const UpGeom g = make_up(B, K, h, w, H, W);
+  if (!class_weight && label_smoothing == 0.f) return launch_ce_dice_fwd<false>(g, logits, target, ignore_index, partial, (hipStream_t)stream, CeW<false>());
+  return launch_ce_dice_fwd<true>(g, logits, target, ignore_index, partial, (hipStream_t)stream, make_cew(class_weight, label_smoothing, K));
+}
+
+extern "C" int sl_upsample_ce_dice_finalize(const float* partial, const float* class_weight, float smooth, int B, int K, int H, int W,
+                                            float* loss3, float* coef, sl_stream_t stream) {
+  SL_REQUIRE(K >= 1 && K <= KMAXC, "upsample_ce_dice_finalize: %d logit channels; this build holds at most %d", K, KMAXC);
+  SL_REQUIRE(smooth > 0.f && smooth <= 3.402823466e38f, "upsample_ce_dice_finalize: smooth %g is not a finite value > 0", (double)smooth);
+  SL_REQUIRE(B > 0 && H > 0 && W > 0, "upsample_ce_dice_finalize: bad shape");
+  SL_REQUIRE(partial && loss3 && coef, "upsample_ce_dice_finalize: null buffer");
+  return sl_launch("upsample_ce_dice_finalize_kernel", upsample_ce_dice_finalize_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, partial, B, K, ce_dice_blocks(B, (long long)H * W),
+                   class_weight, (double)smooth, loss3, coef);
+}
+
+extern "C" int sl_upsample_ce_dice_bwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing,
+                                       const float* loss3, const float* coef, const float* gscale, int B, int K, int h, int w, int H, int W,
+                                       int ignore_index, float* dlogits, sl_stream_t stream) {
+  SL_CE_DICE_COMMON("upsample_ce_dice_bwd");
+  SL_REQUIRE(logits && target && loss3 && coef && gscale && dlogits, "upsample_ce_dice_bwd: null buffer");
+  const UpGeom g = make_up(B, K, h, w, H, W);
+  CeD<true> cd; cd.coef = coef;
+  if (!class_weight && label_smoothing == 0.f)
+    return launch_ce_bwd<false, true>(g, logits, target, loss3, gscale, ignore_index, dlogits, (hipStream_t)stream, CeW<false>(), cd);
+  return launch_ce_bwd<true, true>(g, logits, target, loss3, gscale, ignore_index, dlogits, (hipStream_t)stream, make_cew(class_weight, label_smoothing, K), cd);
 }
 
 extern "C" int sl_pseudo_label(const float* logits, int K2, int h, int w, int64_t* mask, int B, int H, int W, int n_base,

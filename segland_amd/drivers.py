@@ -44,12 +44,23 @@ def label_smoothing(v):
     return eps
 
 
+def dice_weight(v):
+    try:
+        lam = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError('float expected (got %r)' % (v,))
+    if not (np.isfinite(lam) and lam >= 0.0):
+        raise argparse.ArgumentTypeError('the Dice weight must be finite and >= 0 (got %r)' % (v,))
+    return lam
+
+
 def log_loss_options(args):
-    """One line at start: the two controls of the segmentation criterion (loss.get_loss reads the same fields)."""
+    """One line at start: the controls of the segmentation criterion (loss.get_loss reads the same fields); the Dice weight only where it is on."""
     import logging
     w = class_weights(getattr(args, 'class_weights', ()) or ())
-    logging.getLogger('Segmentation').info('segmentation loss: class weights %s, label smoothing %g',
-                                           ','.join('%g' % x for x in w) if w else 'none', float(getattr(args, 'label_smoothing', 0.0)))
+    lam = float(getattr(args, 'dice_weight', 0.0))
+    logging.getLogger('Segmentation').info('segmentation loss: class weights %s, label smoothing %g' + (', dice weight %g' if lam > 0.0 else ''),
+                                           ','.join('%g' % x for x in w) if w else 'none', float(getattr(args, 'label_smoothing', 0.0)), *((lam,) if lam > 0.0 else ()))
 
 
 # (flag, kwargs) -- common to both drivers
@@ -86,6 +97,8 @@ _COMMON = [
     ('--class-weights', dict(type=class_weights, default='', help='comma-separated class weights of the segmentation cross-entropy, one per logit channel '
                                                                   '(1 + base classes; 1 + base + novel classes when fine-tuning); default: none.')),
     ('--label-smoothing', dict(type=label_smoothing, default=0.0, help='label smoothing of the segmentation cross-entropy, in [0, 1]; default 0.')),
+    ('--dice-weight', dict(type=dice_weight, default=0.0, help='weight of the multiclass soft Dice term added to the segmentation cross-entropy (main and auxiliary '
+                                                               'head; class weights scale its per-class terms, ignored pixels are left out); default 0: cross-entropy only.')),
     ('--fp16', dict(action='store_true', default=False, help='mixed precision: bf16 MFMA with fp32 accumulate on MI355X '
                                                                 '(the reference uses fp16 autocast + GradScaler); default is exact-fp32 MFMA.')),
 ]

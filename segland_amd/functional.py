@@ -1002,3 +1002,25 @@ class UpsampleCEFn(torch.autograd.Function):
         logits, target, out, weight = ctx.saved_tensors
         gs = g.detach().reshape(1).float().contiguous()
         return ops.upsample_ce_bwd(logits, target, out, gs, ctx.ignore, weight, ctx.eps), None, None, None, None
+
+
+class UpsampleCEDiceFn(torch.autograd.Function):
+    """(cross-entropy, multiclass soft Dice loss) of the upsampled logits from one pass over the pixels: the hybrid criterion the reference keeps commented out at
+    loss/criterion.py:34 (softmax Dice, sum over classes, mean over samples, `smooth` in numerator and denominator; ignored pixels enter neither term).  Two scalars, so
+    the caller weighs them; the backward is one launch that takes both upstream gradients from a device buffer."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, weight=None, label_smoothing=0.0, smooth=1.0):
+        logits = logits.contiguous()
+        out, coef = ops.upsample_ce_dice_fwd(logits, target, ignore_index, weight, label_smoothing, smooth)
+        ctx.ignore = ignore_index
+        ctx.eps = label_smoothing
+        ctx.save_for_backward(logits, target, out, coef, weight)
+        return out[0].clone(), out[2].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_ce, g_dice):
+        logits, target, out, coef, weight = ctx.saved_tensors
+        gs = torch.stack([g_ce.detach().reshape(()).float(), g_dice.detach().reshape(()).float()])
+        return ops.upsample_ce_dice_bwd(logits, target, out, coef, gs, ctx.ignore, weight, ctx.eps), None, None, None, None, None

@@ -3,7 +3,7 @@ kernel pair (the H x W logits are never materialised).  Returns the same dict of
 import torch
 import torch.nn as nn
 
-from ..functional import UpsampleCEFn
+from ..functional import UpsampleCEDiceFn, UpsampleCEFn
 
 
 class OrthTerm:
@@ -18,15 +18,26 @@ class OrthLoss(nn.Module):
     """`weight` and `label_smoothing` are those of the nn.CrossEntropyLoss the reference builds its segmentation criterion from (loss/criterion.py:33), with torch's
     semantics; the main and the auxiliary loss both use them.  `weight` (one value per logit channel; 1 + n_base + n_novel of them in fine-tune mode) is kept as a float32
     NON-persistent buffer: it follows .to() / .cuda() and adds no key to a state_dict.  The kernels read the buffer itself, so an in-place update
-    (criterion.weight.copy_(...)) reaches a captured training step without a new capture."""
+    (criterion.weight.copy_(...)) reaches a captured training step without a new capture.
 
-    def __init__(self, ignore_index=255, reduction='mean', weight=None, label_smoothing=0.0):
+    `dice_weight` > 0 makes the segmentation criterion the hybrid one the reference keeps commented out beside its CrossEntropyLoss (loss/criterion.py:34,
+    MulticlassHybridLoss): seg_loss = cross-entropy + dice_weight * Dice, with multiclass soft Dice on the softmax of the upsampled logits (sum over classes, each
+    scaled by `weight` where given; mean over samples; `dice_smooth` in numerator and denominator; pixels with the ignore label enter neither term), for the main and
+    the auxiliary head alike; the dict gains 'dice_loss', the main head's unscaled Dice term.  Both are plain floats: no buffer, no state_dict key.  dice_weight == 0
+    is the code path without it."""
+
+    def __init__(self, ignore_index=255, reduction='mean', weight=None, label_smoothing=0.0, dice_weight=0.0, dice_smooth=1.0):
         super().__init__()
         if reduction != 'mean':
             raise ValueError('segland_amd OrthLoss implements reduction="mean" (what the reference uses)')
         label_smoothing = float(label_smoothing)
         if not 0.0 <= label_smoothing <= 1.0:
             raise ValueError('OrthLoss: label_smoothing %r outside [0, 1]' % (label_smoothing,))
+        dice_weight, dice_smooth = float(dice_weight), float(dice_smooth)
+        if not 0.0 <= dice_weight < float('inf'):
+            raise ValueError('OrthLoss: dice_weight %r is not a finite value >= 0' % (dice_weight,))
+        if not 0.0 < dice_smooth < float('inf'):
+            raise ValueError('OrthLoss: dice_smooth %r is not a finite value > 0' % (dice_smooth,))
         if weight is not None:
             weight = torch.as_tensor(weight, dtype=torch.float32).detach().clone().contiguous()
             if weight.dim() != 1 or weight.numel() == 0:
@@ -34,6 +45,8 @@ class OrthLoss(nn.Module):
         self.register_buffer('weight', weight, persistent=False)
         self.ignore_index = ignore_index
         self.label_smoothing = label_smoothing
+        self.dice_weight = dice_weight
+        self.dice_smooth = dice_smooth
         self.w = 10.0
         self._triu = {}
 
@@ -49,17 +62,28 @@ class OrthLoss(nn.Module):
             idx = self._triu[key] = torch.triu_indices(proto_sim.shape[0], proto_sim.shape[1], offset=1).to(proto_sim.device)
         return torch.abs(proto_sim[idx[0], idx[1]]).mean()
 
-    def seg_loss(self, preds, target):
+    def head_loss(self, preds, target):
+        """(segmentation loss of one head, its unscaled Dice term or None): with dice_weight > 0 one forward pass and one backward launch for both terms"""
         if self.weight is not None and self.weight.numel() != preds.shape[1]:
             raise ValueError('OrthLoss: %d class weights for %d logit channels' % (self.weight.numel(), preds.shape[1]))
-        return UpsampleCEFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.weight, self.label_smoothing)
+        if self.dice_weight > 0.0:
+            ce, dice = UpsampleCEDiceFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.weight, self.label_smoothing, self.dice_smooth)
+            return torch.add(ce, dice, alpha=self.dice_weight), dice
+        return UpsampleCEFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.weight, self.label_smoothing), None
+
+    def seg_loss(self, preds, target):
+        return self.head_loss(preds, target)[0]
 
     def forward(self, preds, target, is_ft=False, proto_sim=None, aux_preds=None):
-        seg_loss = self.seg_loss(preds, target)
+        seg_loss, dice = self.head_loss(preds, target)
         orth_loss = self.get_orth_loss(proto_sim, is_ft=is_ft)
         if aux_preds is not None:
             aux_loss = self.seg_loss(aux_preds, target)
             total = seg_loss + orth_loss * self.w + 0.4 * aux_loss
-            return {'total_loss': total, 'seg_loss': seg_loss, 'aux_loss': aux_loss, 'orth_loss': orth_loss}
-        # one launch each way (add with alpha; its backward is one scale) instead of mul + add
-        return {'total_loss': torch.add(seg_loss, orth_loss, alpha=self.w), 'seg_loss': seg_loss, 'orth_loss': orth_loss}
+            out = {'total_loss': total, 'seg_loss': seg_loss, 'aux_loss': aux_loss, 'orth_loss': orth_loss}
+        else:
+            # one launch each way (add with alpha; its backward is one scale) instead of mul + add
+            out = {'total_loss': torch.add(seg_loss, orth_loss, alpha=self.w), 'seg_loss': seg_loss, 'orth_loss': orth_loss}
+        if dice is not None:
+            out['dice_loss'] = dice
+        return out

@@ -1074,6 +1074,44 @@ def upsample_ce_bwd(logits, target, loss_cnt, gscale, ignore_index, weight=None,
     return dl
 
 
+def _ce_dice_weight(weight, K, device):
+    """None (the kernels then take weights of one) or `weight` itself, checked as _ce_class_weight checks it"""
+    return None if weight is None else _ce_class_weight(weight, K, device)
+
+
+def upsample_ce_dice_fwd(logits, target, ignore_index, weight=None, label_smoothing=0.0, smooth=1.0):
+    """(float [3] = (cross-entropy as upsample_ce_fwd gives it, its denominator, multiclass soft Dice loss with softmax: sum over classes, mean over samples),
+    float [B, K, 2] = the backward's coefficient table).  One pass over the pixels for both terms plus one finalize launch; `weight` scales both the cross-entropy
+    and the per-class Dice terms, `label_smoothing` the cross-entropy only; pixels with the ignore label (or one outside [0, K)) enter neither."""
+    B, K, h, w = logits.shape
+    H, W = target.shape[1:]
+    L = _lib.lib()
+    cw = _ce_dice_weight(weight, K, logits.device)
+    rows = L.sl_upsample_ce_dice_rows(B, H, W)
+    part = _f32((max(rows, 1), 2 + 3 * K), logits.device)
+    tok = PROFILER.begin_bytes('upsample_ce_dice_fwd', logits.numel() * 4 + target.numel() * target.element_size())
+    check(L.sl_upsample_ce_dice_fwd(_p(logits), _p(target), _p(cw), label_smoothing, B, K, h, w, H, W, ignore_index, _p(part), _s()), 'upsample_ce_dice_fwd')
+    PROFILER.end_bytes(tok)
+    out, coef = _f32((3,), logits.device), _f32((B, K, 2), logits.device)
+    check(L.sl_upsample_ce_dice_finalize(_p(part), _p(cw), smooth, B, K, H, W, _p(out), _p(coef), _s()), 'upsample_ce_dice_finalize')
+    return out, coef
+
+
+def upsample_ce_dice_bwd(logits, target, out, coef, gscale, ignore_index, weight=None, label_smoothing=0.0):
+    """d (gscale[0] * cross-entropy + gscale[1] * dice) / d logits in one launch; `out` and `coef` from upsample_ce_dice_fwd, gscale float [2] on the device."""
+    B, K, h, w = logits.shape
+    H, W = target.shape[1:]
+    if gscale.numel() != 2:
+        raise ValueError('upsample_ce_dice_bwd: gscale holds the two upstream gradients (got %d values)' % gscale.numel())
+    cw = _ce_dice_weight(weight, K, logits.device)
+    dl = torch.empty_like(logits)
+    tok = PROFILER.begin_bytes('upsample_ce_dice_bwd', 2 * logits.numel() * 4 + target.numel() * target.element_size())
+    check(_lib.lib().sl_upsample_ce_dice_bwd(_p(logits), _p(target), _p(cw), label_smoothing, _p(out), _p(coef), _p(gscale), B, K, h, w, H, W, ignore_index,
+                                              _p(dl), _s()), 'upsample_ce_dice_bwd')
+    PROFILER.end_bytes(tok)
+    return dl
+
+
 def pseudo_label_(logits, mask, n_base):
     """In place on `mask` (int64 [B,H,W]); logits [B,K2,h,w] float, K2 <= 33."""
     B, K2, h, w = logits.shape
