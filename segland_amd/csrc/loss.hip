@@ -27,11 +27,31 @@ template <> struct CeW<true> { const float* w; float keep, epsk; };   // w[K] on
 // In the hybrid kernels the class-weight pointer may be null (weights of one): cew_at.
 template <bool DC> struct CeD {};
 template <> struct CeD<true> { const float* coef; };                  // [B][K][2] on the device
-template <bool DC>
-__device__ __forceinline__ float cew_at(const CeW<true>& cw, int k) {
-  if constexpr (DC) return cw.w ? cw.w[k] : 1.f;
+template <bool DC, bool WT>
+__device__ __forceinline__ float cew_at(const CeW<WT>& cw, int k) {
+  if constexpr (!WT) return 1.f;
+  else if constexpr (DC) return cw.w ? cw.w[k] : 1.f;
   else return cw.w[k];
 }
+__device__ __forceinline__ float dice_q(int k, int t, float qa, float qg) { return qg + (k == t ? qa : 0.f); }   // q_k = g_k + a_k [k == t]
+
+// The gradient of one valid pixel of label t with respect to its interpolated logits, in the three forms above: built once per pixel, at(k) once per channel.  wt = w_t,
+// wsum = sum_j w_j, p = softmax_k, w = w_k, (qa, qg) = coef[b][k], sq = sum_c p_c q_c.  <false, false> is p - [k == t] and nothing else; without DC the caller applies
+// the scale gscale[0] / denominator after the bilinear scatter, with DC f0 and f1 are inside.  A new loss term goes here and into ce_pixel, nowhere else.
+template <bool WT, bool DC>
+struct PixGrad {
+  int t; float hit, ct, epsk, f0, f1, sq;
+  __device__ __forceinline__ PixGrad(int t_, float wt, const CeW<WT>& cw, float wsum, float f0_, float f1_, float sq_) : t(t_), hit(1.f), ct(1.f), epsk(0.f), f0(f0_), f1(f1_), sq(sq_) {
+    if constexpr (WT) { hit = cw.keep * wt; ct = hit + cw.epsk * wsum; epsk = cw.epsk; }
+  }
+  __device__ __forceinline__ float at(int k, float p, float w, float qa, float qg) const {
+    float ce;
+    if constexpr (WT) ce = p * ct - ((k == t ? hit : 0.f) + epsk * w);
+    else ce = p - (k == t ? 1.f : 0.f);
+    if constexpr (DC) return f0 * ce + f1 * (p * (dice_q(k, t, qa, qg) - sq));
+    else return ce;
+  }
+};
 
 __host__ inline float ac1_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 
@@ -43,6 +63,9 @@ __device__ __forceinline__ void src_index_ac1(int dst, int in, float scale, int&
   l1 = src - (float)i0;
   l1 = l1 < 0.f ? 0.f : (l1 > 1.f ? 1.f : l1);
 }
+// the backward direction: the first / last destination index in [lo, hi] whose two sources can include cell i
+__device__ __forceinline__ int foot_lo(int i, float scale, int lo) { return scale > 0.f ? max(lo, (int)floorf((float)(i - 1) / scale)) : lo; }
+__device__ __forceinline__ int foot_hi(int i, float scale, int hi) { return scale > 0.f ? min(hi, (int)ceilf((float)(i + 1) / scale)) : hi; }
 
 // interpolated logits of pixel (Y,X) of image b into v[0..K)
 template <int KW>
@@ -61,6 +84,35 @@ __device__ __forceinline__ void pixel_logits(const UpGeom& g, const float* __res
   }
 }
 
+// Cross-entropy term of one valid pixel of label t from its logits v, for both forward kernels: ce_max gives m = max_k v_k and vt = v_t, the kernel sums
+// s = sum_k exp(v_k - m) (the hybrid one keeps the exponentials: with that loop in here too its K = 33 instantiation lost a wave per SIMD), ce_pixel gives the
+// numerator and denominator (plain: -logp_t and 1; WT: the weighted form above).
+template <int KW>
+__device__ __forceinline__ float ce_max(const float* v, int t, float& vt) {
+  float m = v[0];
+  vt = 0.f;
+#pragma unroll
+  for (int k = 0; k < KW; ++k) { m = fmaxf(m, v[k]); if (k == t) vt = v[k]; }
+  return m;
+}
+struct CePix { float num, den; };
+template <int KW, bool WT, bool DC>
+__device__ __forceinline__ CePix ce_pixel(int K, const float* v, float m, float s, float vt, int t, const CeW<WT>& cw) {
+  CePix o;
+  if constexpr (WT) {
+    const float lse = logf(s) + m, wt = cew_at<DC>(cw, t);
+    float sm = 0.f;                                     // sum_k w_k (-logp_k), in index order
+#pragma unroll
+    for (int k = 0; k < KW; ++k) if (k < K) sm += cew_at<DC>(cw, k) * (lse - v[k]);
+    o.num = cw.keep * wt * (lse - vt) + cw.epsk * sm;
+    o.den = wt;
+  } else {
+    o.num = logf(s) + m - vt;
+    o.den = 1.f;
+  }
+  return o;
+}
+
 // part[blk] = (sum of pixel losses, number of valid pixels); WT: (sum of the pixel numerators, sum of w_t)
 template <int KW, bool WT>
 __global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(UpGeom g, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
@@ -75,23 +127,13 @@ __global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(UpGeom g, const fl
     const int Y = (int)(r % g.H), b = (int)(r / g.H);
     float v[KW];
     pixel_logits<KW>(g, lg, b, Y, X, v);
-    float m = v[0], vt = 0.f;
-#pragma unroll
-    for (int k = 0; k < KW; ++k) { m = fmaxf(m, v[k]); if (k == (int)t) vt = v[k]; }
+    float vt;
+    const float m = ce_max<KW>(v, (int)t, vt);
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < KW; ++k) if (k < g.K) s += expf(v[k] - m);
-    if constexpr (WT) {
-      const float lse = logf(s) + m, wt = cw.w[t];
-      float sm = 0.f;                                   // sum_k w_k (-logp_k), in index order
-#pragma unroll
-      for (int k = 0; k < KW; ++k) if (k < g.K) sm += cw.w[k] * (lse - v[k]);
-      loss += cw.keep * wt * (lse - vt) + cw.epsk * sm;
-      cnt += wt;
-    } else {
-      loss += logf(s) + m - vt;
-      cnt += 1.f;
-    }
+    const CePix px = ce_pixel<KW, WT, false>(g.K, v, m, s, vt, (int)t, cw);
+    loss += px.num; cnt += px.den;
   }
   loss = wave_sum(loss); cnt = wave_sum(cnt);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -138,25 +180,14 @@ __global__ __launch_bounds__(256) void upsample_ce_dice_fwd_kernel(UpGeom g, int
     tn = i + stride < hw ? tb[i + stride] : -1;
     if (t == ignore || t < 0 || t >= g.K) continue;
     const int Y = i / g.W, X = i - Y * g.W;
-    float v[KW], e[KW];
+    float v[KW], e[KW], vt;
     pixel_logits<KW>(g, lg, b, Y, X, v);
-    float m = v[0], vt = 0.f;
-#pragma unroll
-    for (int k = 0; k < KW; ++k) { m = fmaxf(m, v[k]); if (k == (int)t) vt = v[k]; }
+    const float m = ce_max<KW>(v, (int)t, vt);
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < KW; ++k) { e[k] = k < g.K ? expf(v[k] - m) : 0.f; if (k < g.K) s += e[k]; }
-    if constexpr (WT) {
-      const float lse = logf(s) + m, wt = cew_at<true>(cw, (int)t);
-      float sm = 0.f;                                   // sum_k w_k (-logp_k), in index order
-#pragma unroll
-      for (int k = 0; k < KW; ++k) if (k < g.K) sm += cew_at<true>(cw, k) * (lse - v[k]);
-      loss += cw.keep * wt * (lse - vt) + cw.epsk * sm;
-      cnt += wt;
-    } else {
-      loss += logf(s) + m - vt;
-      cnt += 1.f;
-    }
+    const CePix px = ce_pixel<KW, WT, true>(g.K, v, m, s, vt, (int)t, cw);
+    loss += px.num; cnt += px.den;
     const float inv = 1.f / s;
 #pragma unroll
     for (int k = 0; k < KW; ++k) {
@@ -246,10 +277,8 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
   float acc[KW];
 #pragma unroll
   for (int k = 0; k < KW; ++k) acc[k] = 0.f;
-  const int Ylo = g.sy > 0.f ? max(0, (int)floorf((float)(i - 1) / g.sy)) : 0;
-  const int Yhi = g.sy > 0.f ? min(g.H - 1, (int)ceilf((float)(i + 1) / g.sy)) : g.H - 1;
-  const int Xlo = g.sx > 0.f ? max(0, (int)floorf((float)(j - 1) / g.sx)) : 0;
-  const int Xhi = g.sx > 0.f ? min(g.W - 1, (int)ceilf((float)(j + 1) / g.sx)) : g.W - 1;
+  const int Ylo = foot_lo(i, g.sy, 0), Yhi = foot_hi(i, g.sy, g.H - 1);
+  const int Xlo = foot_lo(j, g.sx, 0), Xhi = foot_hi(j, g.sx, g.W - 1);
   float wsum = 0.f;
   if constexpr (WT) {
 #pragma unroll
@@ -286,29 +315,17 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
 #pragma unroll
         for (int k = 0; k < KW; ++k) { v[k] = k < g.K ? expf(v[k] - m) : 0.f; s += v[k]; }
         const float wgt = wy * wx, inv = 1.f / s;
-        if constexpr (DC) {
-          float sq = 0.f;                                 // sum_c p_c q_c, in index order
+        float sq = 0.f;                                   // DC: sum_c p_c q_c, in index order
 #pragma unroll
-          for (int k = 0; k < KW; ++k) { v[k] *= inv; sq += v[k] * (qg[k] + (k == (int)t ? qa[k] : 0.f)); }
-          float hit = 1.f, ct = 1.f;
-          if constexpr (WT) { hit = cw.keep * cew_at<DC>(cw, (int)t); ct = hit + cw.epsk * wsum; }
-#pragma unroll
-          for (int k = 0; k < KW; ++k) {
-            if (k < g.K) {
-              float ce;
-              if constexpr (WT) ce = v[k] * ct - ((k == (int)t ? hit : 0.f) + cw.epsk * cew_at<DC>(cw, k));
-              else ce = v[k] - (k == (int)t ? 1.f : 0.f);
-              acc[k] += wgt * (f0 * ce + f1 * (v[k] * ((qg[k] + (k == (int)t ? qa[k] : 0.f)) - sq)));
-            }
-          }
-        } else if constexpr (WT) {
-          const float hit = cw.keep * cw.w[t], ct = hit + cw.epsk * wsum;
-#pragma unroll
-          for (int k = 0; k < KW; ++k) if (k < g.K) acc[k] += wgt * (v[k] * inv * ct - ((k == (int)t ? hit : 0.f) + cw.epsk * cw.w[k]));
-        } else {
-#pragma unroll
-          for (int k = 0; k < KW; ++k) acc[k] += wgt * (v[k] * inv - (k == (int)t ? 1.f : 0.f));
+        for (int k = 0; k < KW; ++k) {
+          v[k] *= inv;
+          if constexpr (DC) sq += v[k] * dice_q(k, (int)t, qa[k], qg[k]);
         }
+        const PixGrad<WT, DC> pg((int)t, cew_at<DC>(cw, (int)t), cw, wsum, f0, f1, sq);
+        constexpr bool PLAIN = !WT && !DC;                // reads no table: runs over all KW unguarded (acc beyond K is never stored)
+#pragma unroll
+        for (int k = 0; k < KW; ++k)
+          if (PLAIN || k < g.K) acc[k] += wgt * pg.at(k, v[k], cew_at<DC>(cw, k), DC ? qa[k] : 0.f, DC ? qg[k] : 0.f);
       }
     }
   }
@@ -327,8 +344,144 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
 // footprint ONCE (the per-cell gather above evaluates each pixel for each of the ~4 cells it touches, from global memory), then applies the
 // separable bilinear weights in two LDS passes:  H1[Y][j][k] = sum_X wx(X, j) G[Y][X][k],  dlg[i][j][k] = sum_Y wy(Y, i) H1[Y][j][k].
 // Sums run in a fixed order (deterministic); they are associated differently from the gather kernel (last-bit differences).
+//
+// For K > KNC, G[NY][NX][K] does not fit the LDS any more (x8 upsampling, CT = 4: 44 x 44 pixels x 33 channels x 4 B = 256 KB of 160 KiB), so the channel-sliced
+// ("wide") kernel takes the channels through G and H1 in slices of KS <= KNC (the host picks the fewest slices that fit; KS == K in the one-pass kernel).
 constexpr int CT = 4;
-struct UpTile { int NYmax, NXmax; };
+struct UpTile { int NYmax, NXmax, KS; };
+
+// The LDS of both tiled kernels: ONE list of buffers, in this order, in floats.  The host sums it (tile_lds_bytes), the device carves the block's LDS by it (tile_frame).
+enum TileBuf {
+  T_LGT,   // [(CT+2)^2][K] logits of the cells around the tile (clamped at the map border)
+  T_WY0,   // [NY][3] per footprint row: cell y0 and cell y1 as int, weight ly on y1
+  T_WX0,   // [NX][3]
+  T_WXJ,   // [NX][CT] weight of footprint column X on cell j0 + jr
+  T_WYI,   // [NY][CT]
+  T_ST,    // wide: [NY][NX][SW] max, 1 / sum, label as int (-1: the pixel does not count); DC: the fourth word is sum_c p_c q_c over ALL K channels
+  T_H1,    // [NY][CT][KS]
+  T_G,     // [NY][NX][KS]
+  T_WL,    // WT: [K] class weights
+  T_CF,    // DC: [K][2] Dice coefficients (a, g) of this block's sample
+  T_NBUF
+};
+// I: size_t on the host, which sizes a launch it may still refuse; int on the device, where the sum has passed the host's 150 KiB limit
+template <typename I>
+__host__ __device__ inline void tile_extents(int K, const UpTile& ut, bool wt, bool dc, bool wide, I* n) {
+  const I NY = ut.NYmax, NX = ut.NXmax;
+  n[T_LGT] = (I)(CT + 2) * (CT + 2) * K;
+  n[T_WY0] = 3 * NY; n[T_WX0] = 3 * NX; n[T_WXJ] = CT * NX; n[T_WYI] = CT * NY;
+  n[T_ST] = wide ? (dc ? 4 : 3) * NY * NX : 0;
+  n[T_H1] = NY * CT * ut.KS; n[T_G] = NY * NX * ut.KS;
+  n[T_WL] = wt ? K : 0; n[T_CF] = dc ? 2 * K : 0;
+}
+inline size_t tile_lds_bytes(int K, const UpTile& ut, bool wt, bool dc, bool wide) {
+  size_t n[T_NBUF], s = 0;
+  tile_extents(K, ut, wt, dc, wide, n);
+  for (int i = 0; i < T_NBUF; ++i) s += n[i];
+  return s * sizeof(float);
+}
+
+// The block's tile: sample b, cells [i0, i1] x [j0, j1], their joint footprint [Ylo, Yhi] x [Xlo, Xhi] of NY x NX pixels, and its LDS buffers.
+struct TileFrame {
+  int b, i0, j0, i1, j1, Ylo, Yhi, Xlo, Xhi, NY, NX;
+  float* buf[T_NBUF];
+};
+// Carves the LDS and fills lgt, the weight and coefficient tables and wy0 / wx0 / wyi / wxj; ends with the barrier.
+template <int NT, bool WT, bool DC, bool WIDE>
+__device__ __forceinline__ TileFrame tile_frame(const UpGeom& g, const UpTile& ut, float* sm, const float* __restrict__ lg, const CeW<WT>& cw, const CeD<DC>& cd) {
+  TileFrame f;
+  const int K = g.K, tid = threadIdx.x;
+  int n[T_NBUF];
+  tile_extents(K, ut, WT, DC, WIDE, n);
+#pragma unroll
+  for (int i = 0; i < T_NBUF; ++i) { f.buf[i] = sm; sm += n[i]; }
+  float *lgt = f.buf[T_LGT], *wy0 = f.buf[T_WY0], *wx0 = f.buf[T_WX0], *wxj = f.buf[T_WXJ], *wyi = f.buf[T_WYI];
+  const int tw = cdiv(g.w, CT), th = cdiv(g.h, CT);
+  int blk = blockIdx.x;
+  const int tj = blk % tw; blk /= tw;
+  const int ti = blk % th; const int b = blk / th;
+  const int i0 = ti * CT, j0 = tj * CT;
+  const int i1 = min(i0 + CT, g.h) - 1, j1 = min(j0 + CT, g.w) - 1;          // last cell of the tile
+  const int Ylo = foot_lo(i0, g.sy, 0), Yhi = foot_hi(i1, g.sy, g.H - 1);
+  const int Xlo = foot_lo(j0, g.sx, 0), Xhi = foot_hi(j1, g.sx, g.W - 1);
+  const int NY = Yhi - Ylo + 1, NX = Xhi - Xlo + 1;
+  const float* lb = lg + (size_t)b * K * g.h * g.w;
+  for (int e = tid; e < (CT + 2) * (CT + 2) * K; e += NT) {
+    const int k = e % K, c = e / K, cy = c / (CT + 2), cx = c - cy * (CT + 2);
+    const int yy = min(max(i0 - 1 + cy, 0), g.h - 1), xx = min(max(j0 - 1 + cx, 0), g.w - 1);
+    lgt[e] = lb[((size_t)k * g.h + yy) * g.w + xx];
+  }
+  if constexpr (WT) for (int e = tid; e < K; e += NT) f.buf[T_WL][e] = cew_at<DC>(cw, e);
+  if constexpr (DC) for (int e = tid; e < 2 * K; e += NT) f.buf[T_CF][e] = cd.coef[(size_t)b * K * 2 + e];
+  for (int e = tid; e < NY; e += NT) {
+    int y0, y1; float ly; src_index_ac1(Ylo + e, g.h, g.sy, y0, y1, ly);
+    wy0[3 * e] = __int_as_float(y0); wy0[3 * e + 1] = __int_as_float(y1); wy0[3 * e + 2] = ly;
+#pragma unroll
+    for (int r = 0; r < CT; ++r) wyi[e * CT + r] = (y0 == i0 + r ? 1.f - ly : 0.f) + (y1 == i0 + r ? ly : 0.f);
+  }
+  for (int e = tid; e < NX; e += NT) {
+    int x0, x1; float lx; src_index_ac1(Xlo + e, g.w, g.sx, x0, x1, lx);
+    wx0[3 * e] = __int_as_float(x0); wx0[3 * e + 1] = __int_as_float(x1); wx0[3 * e + 2] = lx;
+#pragma unroll
+    for (int r = 0; r < CT; ++r) wxj[e * CT + r] = (x0 == j0 + r ? 1.f - lx : 0.f) + (x1 == j0 + r ? lx : 0.f);
+  }
+  __syncthreads();
+  f.b = b; f.i0 = i0; f.j0 = j0; f.i1 = i1; f.j1 = j1; f.Ylo = Ylo; f.Yhi = Yhi; f.Xlo = Xlo; f.Xhi = Xhi; f.NY = NY; f.NX = NX;
+  return f;
+}
+
+// the four neighbourhood cells a footprint pixel (yr, xr) interpolates from, and its weights
+struct UpTap {
+  const float *q00, *q01, *q10, *q11;
+  float wya, wxa, ly, lx;
+  __device__ __forceinline__ float at(int k) const { return wya * (wxa * q00[k] + lx * q01[k]) + ly * (wxa * q10[k] + lx * q11[k]); }
+};
+__device__ __forceinline__ UpTap up_tap(const float* lgt, const float* wy0, const float* wx0, int yr, int xr, int i0, int j0, int K) {
+  UpTap t;
+  const int y0 = __float_as_int(wy0[3 * yr]), y1 = __float_as_int(wy0[3 * yr + 1]); t.ly = wy0[3 * yr + 2];
+  const int x0 = __float_as_int(wx0[3 * xr]), x1 = __float_as_int(wx0[3 * xr + 1]); t.lx = wx0[3 * xr + 2];
+  t.wya = 1.f - t.ly; t.wxa = 1.f - t.lx;
+  // a footprint pixel at the rim may interpolate from a cell outside the (CT+2)^2 neighbourhood; it then has zero weight on every cell of
+  // this tile, so any finite value will do: clamp the index
+  const int ry0 = min(max(y0 - i0 + 1, 0), CT + 1), ry1 = min(max(y1 - i0 + 1, 0), CT + 1);
+  const int rx0 = min(max(x0 - j0 + 1, 0), CT + 1), rx1 = min(max(x1 - j0 + 1, 0), CT + 1);
+  t.q00 = lgt + (ry0 * (CT + 2) + rx0) * K; t.q01 = lgt + (ry0 * (CT + 2) + rx1) * K;
+  t.q10 = lgt + (ry1 * (CT + 2) + rx0) * K; t.q11 = lgt + (ry1 * (CT + 2) + rx1) * K;
+  return t;
+}
+
+// The separable bilinear scatter of channels [k0, k0 + kn) held in G with channel stride KS.  Pass 2a, along X: H1[Y][j][k] = sum_X wx(X, j) G[Y][X][k].
+template <int NT>
+__device__ __forceinline__ void scatter_x(const UpGeom& g, const TileFrame& f, int kn, int KS) {
+  const float *G = f.buf[T_G], *wxj = f.buf[T_WXJ];
+  float* H1 = f.buf[T_H1];
+  for (int e = threadIdx.x; e < f.NY * CT * kn; e += NT) {
+    const int kk = e % kn, r = e / kn, jr = r % CT, yr = r / CT;
+    const int j = f.j0 + jr;
+    float acc = 0.f;
+    if (j <= f.j1) {
+      const int xa = foot_lo(j, g.sx, f.Xlo) - f.Xlo, xb = foot_hi(j, g.sx, f.Xhi) - f.Xlo;
+      const float* grow = G + (size_t)yr * f.NX * KS + kk;
+      for (int xr = xa; xr <= xb; ++xr) acc += wxj[xr * CT + jr] * grow[xr * KS];
+    }
+    H1[(yr * CT + jr) * KS + kk] = acc;
+  }
+}
+// Pass 2b, along Y, times the final scale, store: dlg[i][j][k0 + k] = scale * sum_Y wy(Y, i) H1[Y][j][k].
+template <int NT>
+__device__ __forceinline__ void scatter_y_store(const UpGeom& g, const TileFrame& f, int k0, int kn, int KS, float scale, float* __restrict__ dlg) {
+  const float *H1 = f.buf[T_H1], *wyi = f.buf[T_WYI];
+  for (int e = threadIdx.x; e < CT * CT * kn; e += NT) {
+    const int kk = e % kn, c = e / kn, ir = c / CT, jr = c - ir * CT;
+    const int i = f.i0 + ir, j = f.j0 + jr;
+    if (i > f.i1 || j > f.j1) continue;
+    const int ya = foot_lo(i, g.sy, f.Ylo), yb = foot_hi(i, g.sy, f.Yhi);
+    float acc = 0.f;
+    for (int yr = ya - f.Ylo; yr <= yb - f.Ylo; ++yr) acc += wyi[yr * CT + ir] * H1[(yr * CT + jr) * KS + kk];
+    dlg[(((size_t)f.b * g.K + k0 + kk) * g.h + i) * g.w + j] = acc * scale;
+  }
+}
+
 template <int NT, bool WT, bool DC>
 __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpTile ut, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
                                                                     const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
@@ -336,16 +489,18 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int KW = KNC;                            // this kernel serves K <= KNC (G holds all K channels of every footprint pixel)
   const int K = g.K;
-  float* lgt = sm;                                   // [(CT+2)^2][K] logits of the cells around the tile (clamped at the map border)
-  float* wy0 = lgt + (CT + 2) * (CT + 2) * K;        // per footprint row: weight on cell y0, weight on y1 ; y0 as int
+  // This kernel keeps its own prologue and scatter passes, in the order of TileBuf (no statistics): through tile_frame / scatter_x / scatter_y_store its plain and
+  // weighted forms, the default training step's kernels, measured 0.5 .. 2 % slower on equal arithmetic.
+  float* lgt = sm;
+  float* wy0 = lgt + (CT + 2) * (CT + 2) * K;
   float* wx0 = wy0 + 3 * ut.NYmax;
-  float* wxj = wx0 + 3 * ut.NXmax;                   // [NX][CT] weight of footprint column X on cell j0 + jr
-  float* wyi = wxj + CT * ut.NXmax;                  // [NY][CT]
-  float* H1 = wyi + CT * ut.NYmax;                   // [NY][CT][K]
-  float* G = H1 + ut.NYmax * CT * K;                 // [NY][NX][K]
-  float* wl = nullptr;                               // WT: [K] class weights behind G (the host adds K floats to the launch's LDS)
+  float* wxj = wx0 + 3 * ut.NXmax;
+  float* wyi = wxj + CT * ut.NXmax;
+  float* H1 = wyi + CT * ut.NYmax;
+  float* G = H1 + ut.NYmax * CT * K;
+  float* wl = nullptr;
   if constexpr (WT) wl = G + (size_t)ut.NYmax * ut.NXmax * K;
-  float* cf = nullptr;                               // DC: [K][2] Dice coefficients (a, g) of this block's sample behind G / wl (the host adds 2 K floats)
+  float* cf = nullptr;
   if constexpr (DC) cf = G + (size_t)ut.NYmax * ut.NXmax * K + (WT ? K : 0);
   const int tid = threadIdx.x;
   const int tw = cdiv(g.w, CT), th = cdiv(g.h, CT);
@@ -354,10 +509,8 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
   const int ti = blk % th; const int b = blk / th;
   const int i0 = ti * CT, j0 = tj * CT;
   const int i1 = min(i0 + CT, g.h) - 1, j1 = min(j0 + CT, g.w) - 1;          // last cell of the tile
-  const int Ylo = g.sy > 0.f ? max(0, (int)floorf((float)(i0 - 1) / g.sy)) : 0;
-  const int Yhi = g.sy > 0.f ? min(g.H - 1, (int)ceilf((float)(i1 + 1) / g.sy)) : g.H - 1;
-  const int Xlo = g.sx > 0.f ? max(0, (int)floorf((float)(j0 - 1) / g.sx)) : 0;
-  const int Xhi = g.sx > 0.f ? min(g.W - 1, (int)ceilf((float)(j1 + 1) / g.sx)) : g.W - 1;
+  const int Ylo = foot_lo(i0, g.sy, 0), Yhi = foot_hi(i1, g.sy, g.H - 1);
+  const int Xlo = foot_lo(j0, g.sx, 0), Xhi = foot_hi(j1, g.sx, g.W - 1);
   const int NY = Yhi - Ylo + 1, NX = Xhi - Xlo + 1;
   const float* lb = lg + (size_t)b * K * g.h * g.w;
   for (int e = tid; e < (CT + 2) * (CT + 2) * K; e += NT) {
@@ -409,51 +562,28 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
       for (int k = 0; k < K; ++k) out[k] = 0.f;
       continue;
     }
-    const int y0 = __float_as_int(wy0[3 * yr]), y1 = __float_as_int(wy0[3 * yr + 1]); const float ly = wy0[3 * yr + 2];
-    const int x0 = __float_as_int(wx0[3 * xr]), x1 = __float_as_int(wx0[3 * xr + 1]); const float lx = wx0[3 * xr + 2];
-    const float wya = 1.f - ly, wxa = 1.f - lx;
-    // a footprint pixel at the rim may interpolate from a cell outside the (CT+2)^2 neighbourhood; it then has zero weight on every cell of
-    // this tile, so any finite value will do: clamp the index
-    const int ry0 = min(max(y0 - i0 + 1, 0), CT + 1), ry1 = min(max(y1 - i0 + 1, 0), CT + 1);
-    const int rx0 = min(max(x0 - j0 + 1, 0), CT + 1), rx1 = min(max(x1 - j0 + 1, 0), CT + 1);
-    const float* q00 = lgt + (ry0 * (CT + 2) + rx0) * K;
-    const float* q01 = lgt + (ry0 * (CT + 2) + rx1) * K;
-    const float* q10 = lgt + (ry1 * (CT + 2) + rx0) * K;
-    const float* q11 = lgt + (ry1 * (CT + 2) + rx1) * K;
+    const UpTap tap = up_tap(lgt, wy0, wx0, yr, xr, i0, j0, K);
     float v[KW];
     float m = -INFINITY;
 #pragma unroll
     for (int k = 0; k < KW; ++k) {
-      if (k < K) { v[k] = wya * (wxa * q00[k] + lx * q01[k]) + ly * (wxa * q10[k] + lx * q11[k]); m = fmaxf(m, v[k]); }
+      if (k < K) { v[k] = tap.at(k); m = fmaxf(m, v[k]); }
       else v[k] = -INFINITY;
     }
     float ssum = 0.f;
 #pragma unroll
     for (int k = 0; k < KW; ++k) { v[k] = k < K ? __expf(v[k] - m) : 0.f; ssum += v[k]; }      // hardware exp2-based: 2 ulp, the gradient's tolerance is 1e-3
     const float inv = 1.f / ssum;
+    // DC normalises v first (sq = sum_c p_c q_c, in index order, needs every p); the other forms multiply by inv at the one use below, under the same k < K guard as
+    // the store: a normalising loop of its own costs them 16 selects per pixel (measured: +3 % on this kernel)
+    float sq = 0.f;
     if constexpr (DC) {
-      float sq = 0.f;                                  // sum_c p_c q_c, in index order
 #pragma unroll
-      for (int k = 0; k < KW; ++k) if (k < K) { v[k] *= inv; sq += v[k] * (cf[2 * k + 1] + (k == (int)t ? cf[2 * k] : 0.f)); }
-      float hit = 1.f, ct = 1.f;
-      if constexpr (WT) { hit = cw.keep * wl[t]; ct = hit + cw.epsk * wsum; }
-#pragma unroll
-      for (int k = 0; k < KW; ++k) {
-        if (k < K) {
-          float ce;
-          if constexpr (WT) ce = v[k] * ct - ((k == (int)t ? hit : 0.f) + cw.epsk * wl[k]);
-          else ce = v[k] - (k == (int)t ? 1.f : 0.f);
-          out[k] = f0 * ce + f1 * (v[k] * ((cf[2 * k + 1] + (k == (int)t ? cf[2 * k] : 0.f)) - sq));
-        }
-      }
-    } else if constexpr (WT) {
-      const float hit = cw.keep * wl[t], ct = hit + cw.epsk * wsum;
-#pragma unroll
-      for (int k = 0; k < KW; ++k) if (k < K) out[k] = v[k] * inv * ct - ((k == (int)t ? hit : 0.f) + cw.epsk * wl[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < KW; ++k) if (k < K) out[k] = v[k] * inv - (k == (int)t ? 1.f : 0.f);
+      for (int k = 0; k < KW; ++k) if (k < K) { v[k] *= inv; sq += v[k] * dice_q(k, (int)t, cf[2 * k], cf[2 * k + 1]); }
     }
+    const PixGrad<WT, DC> pg((int)t, WT ? wl[t] : 1.f, cw, wsum, f0, f1, sq);
+#pragma unroll
+    for (int k = 0; k < KW; ++k) if (k < K) out[k] = pg.at(k, DC ? v[k] : v[k] * inv, WT ? wl[k] : 0.f, DC ? cf[2 * k] : 0.f, DC ? cf[2 * k + 1] : 0.f);
   }
   __syncthreads();
   // ---- pass 2a: along X
@@ -462,7 +592,7 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
     const int j = j0 + jr;
     float acc = 0.f;
     if (j <= j1) {
-      const int xa = (g.sx > 0.f ? max(Xlo, (int)floorf((float)(j - 1) / g.sx)) : Xlo) - Xlo, xb = (g.sx > 0.f ? min(Xhi, (int)ceilf((float)(j + 1) / g.sx)) : Xhi) - Xlo;
+      const int xa = foot_lo(j, g.sx, Xlo) - Xlo, xb = foot_hi(j, g.sx, Xhi) - Xlo;
       const float* grow = G + (size_t)yr * NX * K + k;
       for (int xr = xa; xr <= xb; ++xr) acc += wxj[xr * CT + jr] * grow[xr * K];
     }
@@ -476,88 +606,27 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
     const int k = e % K, c = e / K, ir = c / CT, jr = c - ir * CT;
     const int i = i0 + ir, j = j0 + jr;
     if (i > i1 || j > j1) continue;
-    const int ya = g.sy > 0.f ? max(Ylo, (int)floorf((float)(i - 1) / g.sy)) : Ylo, yb = g.sy > 0.f ? min(Yhi, (int)ceilf((float)(i + 1) / g.sy)) : Yhi;
+    const int ya = foot_lo(i, g.sy, Ylo), yb = foot_hi(i, g.sy, Yhi);
     float acc = 0.f;
     for (int yr = ya - Ylo; yr <= yb - Ylo; ++yr) acc += wyi[yr * CT + ir] * H1[(yr * CT + jr) * K + k];
     dlg[(((size_t)b * K + k) * g.h + i) * g.w + j] = acc * f;
   }
 }
 
-// The tiled gradient for K > KNC.  G[NY][NX][K] does not fit the LDS any more (x8 upsampling, CT = 4: 44 x 44 pixels x 33 channels x 4 B = 256 KB of 160 KiB), so
-// the channels go through G and H1 in slices of KS <= KNC (the host picks the fewest slices that fit).  One pass over the footprint first computes every pixel's
-// max and 1 / sum over ALL K channels from lgt and keeps them with the label (three words per pixel); passes 1, 2a, 2b then run once per slice on those statistics.
+// The tiled gradient for K > KNC, channels in slices of ut.KS.  One pass over the footprint first computes every pixel's max and 1 / sum over ALL K channels from lgt
+// and keeps them with the label (three words per pixel); pass 1 and the scatter then run once per slice on those statistics.
 // Each pixel's softmax is still evaluated once (2 K exponentials instead of K); sums in a fixed order, no atomics.
-struct UpTileW { int NYmax, NXmax, KS; };
-struct UpTap {            // the four neighbourhood cells a footprint pixel interpolates from, and its weights
-  const float *q00, *q01, *q10, *q11;
-  float wya, wxa, ly, lx;
-  __device__ __forceinline__ float at(int k) const { return wya * (wxa * q00[k] + lx * q01[k]) + ly * (wxa * q10[k] + lx * q11[k]); }
-};
-__device__ __forceinline__ UpTap up_tap(const float* lgt, const float* wy0, const float* wx0, int yr, int xr, int i0, int j0, int K) {
-  const int y0 = __float_as_int(wy0[3 * yr]), y1 = __float_as_int(wy0[3 * yr + 1]);
-  const int x0 = __float_as_int(wx0[3 * xr]), x1 = __float_as_int(wx0[3 * xr + 1]);
-  UpTap t;
-  t.ly = wy0[3 * yr + 2]; t.lx = wx0[3 * xr + 2];
-  t.wya = 1.f - t.ly; t.wxa = 1.f - t.lx;
-  // a rim pixel may interpolate from a cell outside the (CT+2)^2 neighbourhood; it has zero weight on every cell of this tile: clamp the index (as in the one-pass kernel)
-  const int ry0 = min(max(y0 - i0 + 1, 0), CT + 1), ry1 = min(max(y1 - i0 + 1, 0), CT + 1);
-  const int rx0 = min(max(x0 - j0 + 1, 0), CT + 1), rx1 = min(max(x1 - j0 + 1, 0), CT + 1);
-  t.q00 = lgt + (ry0 * (CT + 2) + rx0) * K; t.q01 = lgt + (ry0 * (CT + 2) + rx1) * K;
-  t.q10 = lgt + (ry1 * (CT + 2) + rx0) * K; t.q11 = lgt + (ry1 * (CT + 2) + rx1) * K;
-  return t;
-}
 template <int NT, bool WT, bool DC>
-__global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g, UpTileW ut, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
+__global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g, UpTile ut, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
                                                                          const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
                                                                          int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  constexpr int SW = DC ? 4 : 3;                     // statistics words per footprint pixel; DC: the fourth is sum_c p_c q_c over ALL K channels
-  const int K = g.K, KS = ut.KS;
-  float* lgt = sm;                                   // [(CT+2)^2][K]
-  float* wy0 = lgt + (CT + 2) * (CT + 2) * K;        // as in the one-pass kernel
-  float* wx0 = wy0 + 3 * ut.NYmax;
-  float* wxj = wx0 + 3 * ut.NXmax;                   // [NX][CT]
-  float* wyi = wxj + CT * ut.NXmax;                  // [NY][CT]
-  float* st = wyi + CT * ut.NYmax;                   // [NY][NX][SW]: max, 1 / sum, label as int (-1: the pixel does not count)
-  float* H1 = st + SW * ut.NYmax * ut.NXmax;         // [NY][CT][KS]
-  float* G = H1 + ut.NYmax * CT * KS;                // [NY][NX][KS]
-  float* wl = nullptr;                               // WT: [K] class weights behind G (the host adds K floats to the launch's LDS)
-  if constexpr (WT) wl = G + (size_t)ut.NYmax * ut.NXmax * KS;
-  float* cf = nullptr;                               // DC: [K][2] Dice coefficients (a, g) of this block's sample behind G / wl (the host adds 2 K floats)
-  if constexpr (DC) cf = G + (size_t)ut.NYmax * ut.NXmax * KS + (WT ? K : 0);
-  const int tid = threadIdx.x;
-  const int tw = cdiv(g.w, CT), th = cdiv(g.h, CT);
-  int blk = blockIdx.x;
-  const int tj = blk % tw; blk /= tw;
-  const int ti = blk % th; const int b = blk / th;
-  const int i0 = ti * CT, j0 = tj * CT;
-  const int i1 = min(i0 + CT, g.h) - 1, j1 = min(j0 + CT, g.w) - 1;          // last cell of the tile
-  const int Ylo = g.sy > 0.f ? max(0, (int)floorf((float)(i0 - 1) / g.sy)) : 0;
-  const int Yhi = g.sy > 0.f ? min(g.H - 1, (int)ceilf((float)(i1 + 1) / g.sy)) : g.H - 1;
-  const int Xlo = g.sx > 0.f ? max(0, (int)floorf((float)(j0 - 1) / g.sx)) : 0;
-  const int Xhi = g.sx > 0.f ? min(g.W - 1, (int)ceilf((float)(j1 + 1) / g.sx)) : g.W - 1;
-  const int NY = Yhi - Ylo + 1, NX = Xhi - Xlo + 1;
-  const float* lb = lg + (size_t)b * K * g.h * g.w;
-  for (int e = tid; e < (CT + 2) * (CT + 2) * K; e += NT) {
-    const int k = e % K, c = e / K, cy = c / (CT + 2), cx = c - cy * (CT + 2);
-    const int yy = min(max(i0 - 1 + cy, 0), g.h - 1), xx = min(max(j0 - 1 + cx, 0), g.w - 1);
-    lgt[e] = lb[((size_t)k * g.h + yy) * g.w + xx];
-  }
-  if constexpr (WT) for (int e = tid; e < K; e += NT) wl[e] = cew_at<DC>(cw, e);
-  if constexpr (DC) for (int e = tid; e < 2 * K; e += NT) cf[e] = cd.coef[(size_t)b * K * 2 + e];
-  for (int e = tid; e < NY; e += NT) {
-    int y0, y1; float ly; src_index_ac1(Ylo + e, g.h, g.sy, y0, y1, ly);
-    wy0[3 * e] = __int_as_float(y0); wy0[3 * e + 1] = __int_as_float(y1); wy0[3 * e + 2] = ly;
-#pragma unroll
-    for (int r = 0; r < CT; ++r) wyi[e * CT + r] = (y0 == i0 + r ? 1.f - ly : 0.f) + (y1 == i0 + r ? ly : 0.f);
-  }
-  for (int e = tid; e < NX; e += NT) {
-    int x0, x1; float lx; src_index_ac1(Xlo + e, g.w, g.sx, x0, x1, lx);
-    wx0[3 * e] = __int_as_float(x0); wx0[3 * e + 1] = __int_as_float(x1); wx0[3 * e + 2] = lx;
-#pragma unroll
-    for (int r = 0; r < CT; ++r) wxj[e * CT + r] = (x0 == j0 + r ? 1.f - lx : 0.f) + (x1 == j0 + r ? lx : 0.f);
-  }
-  __syncthreads();
+  constexpr int SW = DC ? 4 : 3;                     // statistics words per footprint pixel
+  const int K = g.K, KS = ut.KS, tid = threadIdx.x;
+  const TileFrame f = tile_frame<NT, WT, DC, true>(g, ut, sm, lg, cw, cd);
+  const int b = f.b, i0 = f.i0, j0 = f.j0, Ylo = f.Ylo, Xlo = f.Xlo, NY = f.NY, NX = f.NX;
+  float *st = f.buf[T_ST], *G = f.buf[T_G];
+  const float *lgt = f.buf[T_LGT], *wy0 = f.buf[T_WY0], *wx0 = f.buf[T_WX0], *wl = f.buf[T_WL], *cf = f.buf[T_CF];
   // ---- pass 0: max and 1 / sum over all K channels of every footprint pixel, once
   for (int pix = tid; pix < NY * NX; pix += NT) {
     const int yr = pix / NX, xr = pix - yr * NX;
@@ -570,7 +639,7 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
     float ssum = 0.f;
     if constexpr (DC) {
       float sq = 0.f;                                  // sum_c e_c q_c from the same exponentials, in index order
-      for (int k = 0; k < K; ++k) { const float e = __expf(tap.at(k) - m); ssum += e; sq += e * (cf[2 * k + 1] + (k == (int)t ? cf[2 * k] : 0.f)); }
+      for (int k = 0; k < K; ++k) { const float e = __expf(tap.at(k) - m); ssum += e; sq += e * dice_q(k, (int)t, cf[2 * k], cf[2 * k + 1]); }
       s[3] = sq * (1.f / ssum);
     } else {
       for (int k = 0; k < K; ++k) ssum += __expf(tap.at(k) - m);
@@ -578,7 +647,7 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
     s[0] = m; s[1] = 1.f / ssum; s[2] = __int_as_float((int)t);
   }
   __syncthreads();
-  const float f = gscale[0] / loss_cnt[1];           // DC: f0, applied per pixel with f1 before the separable passes
+  const float f0 = gscale[0] / loss_cnt[1];          // DC: applied per pixel with f1 before the scatter
   float f1 = 0.f;
   if constexpr (DC) f1 = gscale[1];
   float wsum = 0.f;
@@ -597,50 +666,17 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
       }
       const UpTap tap = up_tap(lgt, wy0, wx0, yr, xr, i0, j0, K);
       const float m = s[0], inv = s[1];
-      if constexpr (DC) {
-        const float sq = s[3];
-        float hit = 1.f, ct = 1.f;
-        if constexpr (WT) { hit = cw.keep * wl[t]; ct = hit + cw.epsk * wsum; }
-        for (int kk = 0; kk < kn; ++kk) {
-          const int k = k0 + kk;
-          const float p = __expf(tap.at(k) - m) * inv;
-          float ce;
-          if constexpr (WT) ce = p * ct - ((k == t ? hit : 0.f) + cw.epsk * wl[k]);
-          else ce = p - (k == t ? 1.f : 0.f);
-          out[kk] = f * ce + f1 * (p * ((cf[2 * k + 1] + (k == t ? cf[2 * k] : 0.f)) - sq));
-        }
-      } else if constexpr (WT) {
-        const float hit = cw.keep * wl[t], ct = hit + cw.epsk * wsum;
-        for (int kk = 0; kk < kn; ++kk) out[kk] = __expf(tap.at(k0 + kk) - m) * inv * ct - ((k0 + kk == t ? hit : 0.f) + cw.epsk * wl[k0 + kk]);
-      } else {
-        for (int kk = 0; kk < kn; ++kk) out[kk] = __expf(tap.at(k0 + kk) - m) * inv - (k0 + kk == t ? 1.f : 0.f);
+      const PixGrad<WT, DC> pg(t, WT ? wl[t] : 1.f, cw, wsum, f0, f1, DC ? s[3] : 0.f);
+      for (int kk = 0; kk < kn; ++kk) {
+        const int k = k0 + kk;
+        out[kk] = pg.at(k, __expf(tap.at(k) - m) * inv, WT ? wl[k] : 0.f, DC ? cf[2 * k] : 0.f, DC ? cf[2 * k + 1] : 0.f);
       }
     }
     __syncthreads();
-    // ---- pass 2a: along X
-    for (int e = tid; e < NY * CT * kn; e += NT) {
-      const int kk = e % kn, r = e / kn, jr = r % CT, yr = r / CT;
-      const int j = j0 + jr;
-      float acc = 0.f;
-      if (j <= j1) {
-        const int xa = (g.sx > 0.f ? max(Xlo, (int)floorf((float)(j - 1) / g.sx)) : Xlo) - Xlo, xb = (g.sx > 0.f ? min(Xhi, (int)ceilf((float)(j + 1) / g.sx)) : Xhi) - Xlo;
-        const float* grow = G + (size_t)yr * NX * KS + kk;
-        for (int xr = xa; xr <= xb; ++xr) acc += wxj[xr * CT + jr] * grow[xr * KS];
-      }
-      H1[(yr * CT + jr) * KS + kk] = acc;
-    }
+    scatter_x<NT>(g, f, kn, KS);
     __syncthreads();
-    // ---- pass 2b: along Y, scale, store.  The next slice's pass 1 writes G only, and H1 is written again after the barrier that follows it.
-    for (int e = tid; e < CT * CT * kn; e += NT) {
-      const int kk = e % kn, c = e / kn, ir = c / CT, jr = c - ir * CT;
-      const int i = i0 + ir, j = j0 + jr;
-      if (i > i1 || j > j1) continue;
-      const int ya = g.sy > 0.f ? max(Ylo, (int)floorf((float)(i - 1) / g.sy)) : Ylo, yb = g.sy > 0.f ? min(Yhi, (int)ceilf((float)(i + 1) / g.sy)) : Yhi;
-      float acc = 0.f;
-      for (int yr = ya - Ylo; yr <= yb - Ylo; ++yr) acc += wyi[yr * CT + ir] * H1[(yr * CT + jr) * KS + kk];
-      if constexpr (DC) dlg[(((size_t)b * K + k0 + kk) * g.h + i) * g.w + j] = acc;
-      else dlg[(((size_t)b * K + k0 + kk) * g.h + i) * g.w + j] = acc * f;
-    }
+    // the next slice's pass 1 writes G only, and H1 is written again after the barrier that follows it
+    scatter_y_store<NT>(g, f, k0, kn, KS, DC ? 1.f : f0, dlg);
   }
 }
 
@@ -805,30 +841,30 @@ int launch_ce_bwd(const UpGeom& g, const float* logits, const int64_t* target, c
                   hipStream_t stream, CeW<WT> cw, CeD<DC> cd = CeD<DC>()) {
   const int B = g.B, K = g.K, h = g.h, w = g.w, H = g.H, W = g.W;
   const long long cells = (long long)B * h * w;
-  const size_t wl = (WT ? (size_t)K : 0) + (DC ? 2 * (size_t)K : 0);              // the weighted kernels keep the K class weights behind G, the hybrid ones 2 K coefficients
   // tiled kernel when the joint footprint of a CT x CT cell tile fits the LDS (always for an upsampling factor <= ~12 at K <= 16); test hook sl_debug_ce_tiled(0): never
-  if (g.sy > 0.f && g.sx > 0.f && g_sl_debug.ce_tiled && K > KNC) {
-    // channel-sliced form: the fewest slices (of at most KNC channels) whose G and H1 fit next to the per-pixel statistics
-    UpTileW ut;
-    ut.NYmax = (int)ceilf((float)(CT + 1) / g.sy) + 3; if (ut.NYmax > H) ut.NYmax = H;
-    ut.NXmax = (int)ceilf((float)(CT + 1) / g.sx) + 3; if (ut.NXmax > W) ut.NXmax = W;
-    const size_t fixed = (size_t)(CT + 2) * (CT + 2) * K + (3 + CT) * (ut.NYmax + ut.NXmax) + (DC ? 4 : 3) * (size_t)ut.NYmax * ut.NXmax + wl;
-    for (int ns = cdiv(K, KNC); ns <= K; ++ns) {
-      ut.KS = cdiv(K, ns);
-      const size_t lds = (fixed + (size_t)ut.NYmax * CT * ut.KS + (size_t)ut.NYmax * ut.NXmax * ut.KS) * sizeof(float);
-      if (lds > 150 * 1024) continue;
-      return sl_launch("upsample_ce_bwd_tiled_wide_kernel", upsample_ce_bwd_tiled_wide_kernel<512, WT, DC>, dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(512), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw, cd);
-    }
-  } else if (g.sy > 0.f && g.sx > 0.f && g_sl_debug.ce_tiled) {
+  if (g.sy > 0.f && g.sx > 0.f && g_sl_debug.ce_tiled) {
+#ifndef SL_UPCE_NT
+#define SL_UPCE_NT 512      // threads per block of the one-pass tiled kernel (A/B build: 256)
+#endif
+    const bool wide = K > KNC;
+    const dim3 tiles((unsigned)(B * cdiv(h, CT) * cdiv(w, CT)));
     UpTile ut;
     ut.NYmax = (int)ceilf((float)(CT + 1) / g.sy) + 3; if (ut.NYmax > H) ut.NYmax = H;
     ut.NXmax = (int)ceilf((float)(CT + 1) / g.sx) + 3; if (ut.NXmax > W) ut.NXmax = W;
-    const size_t lds = ((size_t)(CT + 2) * (CT + 2) * K + (3 + CT) * (ut.NYmax + ut.NXmax) + (size_t)ut.NYmax * CT * K + (size_t)ut.NYmax * ut.NXmax * K + wl) * sizeof(float);
-    if (lds <= 150 * 1024) {
-#ifndef SL_UPCE_NT
-#define SL_UPCE_NT 512      // threads per block of the tiled kernel (A/B build: 256)
-#endif
-      return sl_launch("upsample_ce_bwd_tiled_kernel", upsample_ce_bwd_tiled_kernel<SL_UPCE_NT, WT, DC>, dim3((unsigned)(B * cdiv(h, CT) * cdiv(w, CT))), dim3(SL_UPCE_NT), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw, cd);
+    const size_t limit = 150 * 1024;
+    if (!wide) {                                     // all K channels in one pass, or not tiled
+      ut.KS = K;
+      const size_t lds = tile_lds_bytes(K, ut, WT, DC, false);
+      if (lds <= limit)
+        return sl_launch("upsample_ce_bwd_tiled_kernel", upsample_ce_bwd_tiled_kernel<SL_UPCE_NT, WT, DC>, tiles, dim3(SL_UPCE_NT), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw, cd);
+    } else {
+      // channel-sliced form: the fewest slices (of at most KNC channels) whose G and H1 fit next to the per-pixel statistics
+      for (int ns = cdiv(K, KNC); ns <= K; ++ns) {
+        ut.KS = cdiv(K, ns);
+        const size_t lds = tile_lds_bytes(K, ut, WT, DC, true);
+        if (lds > limit) continue;
+        return sl_launch("upsample_ce_bwd_tiled_wide_kernel", upsample_ce_bwd_tiled_wide_kernel<512, WT, DC>, tiles, dim3(512), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw, cd);
+      }
     }
   }
   return sl_launch("upsample_ce_bwd_kernel", K <= KNC ? upsample_ce_bwd_kernel<KNC, WT, DC> : upsample_ce_bwd_kernel<KMAXC, WT, DC>, dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, stream, g, logits, target,
