@@ -18,10 +18,12 @@ same -- same buckets, same in-place gradients, same collectives around the two b
 (`capturable()` says why) instead of handing the job to DistributedDataParallel's reducer.
 Capturing is a COLLECTIVE decision: the three parts are captured back to back without running anything and without any collective, the ranks then agree (MIN
 all-reduce of a success flag) and either all replay or all stay kernel by kernel -- a rank whose capture failed alone would otherwise issue the step's all-reduces
-a second time while the others issue them once (round-3 advisor).
+a second time while the others issue them once (round-3 advisor).  Key, warm-up, attempt policy, capture preamble and replay path are graph_step.StepLifecycle's,
+shared with the one-graph step; `GraphedBucketStep` adds how the parts are recorded and replayed around the collectives, and the handshake.
 Exposed communication: the early buckets only (34 MB for ResNet-50 against 190 MB without the cut, SEGLAND_BUCKET_CUT=0); the DistributedDataParallel wrapper
 costs 2-3 % at any world size.  SEGLAND_BUCKET_STEP=0 keeps DistributedDataParallel with the in-place bucket gradients of
 engine.enable_inplace_bucket_gradients."""
+import logging
 import os
 
 import torch
@@ -253,121 +255,53 @@ class BucketedReplica(nn.Module):
         return self._run(self.train_step_parts(optimizer, double_step), img, mask, lambda f, *a: f(*a))
 
 
-class GraphedBucketStep:
+class GraphedBucketStep(graph_step.StepLifecycle):
     """Callable with the signature and results of train_base.train_iteration for a BucketedReplica: graph A1 (forward + backward down to the cut), all-reduce of the
-    late buckets (asynchronous), graph A2 (rest of the backward), all-reduce of the early buckets, graph B (clip + AdamW).  The graphs are captured together (after
-    `warmup` eager steps per input signature) from one memory pool WITHOUT running and without collectives; the ranks then agree on the outcome
-    (BucketedReplica.agree) and either all replay -- the capturing step itself is the first replay -- or all issue this step and the following ones kernel by kernel
+    late buckets (asynchronous), graph A2 (rest of the backward), all-reduce of the early buckets, graph B (clip + AdamW).  The lifecycle is graph_step.StepLifecycle's;
+    what differs: the graphs are recorded together from one memory pool WITHOUT collectives, and whether an attempt stands is the ranks' decision
+    (BucketedReplica.agree): either all replay -- the capturing step itself is the first replay -- or all issue this step and the following ones kernel by kernel
     (two more attempts).  Every rank must see the same sequence of input signatures (DistributedSampler + drop_last, engine._loader): the attempts line up."""
 
     def __init__(self, replica, optimizer, double_step=True, warmup=3):
-        self.replica, self.optimizer, self.warmup = replica, optimizer, warmup
+        super().__init__(replica, optimizer, warmup)
+        self.replica = replica
         self.parts = replica.train_step_parts(optimizer, double_step)
-        self.seen, self.key, self.graphs = {}, None, None
-        self.static_in, self.outs, self.static_grads = None, None, None
-        self.replays, self.failures = 0, 0
-        self.bn_training = True
         self.eager_reason = capturable(replica.module)
         if self.eager_reason is not None:
-            import logging
             logging.getLogger('Segmentation').info('bucket_step: steps are issued kernel by kernel (%s)', self.eager_reason)
 
-    def _state_key(self, tensors):
-        m = self.replica
-        return tuple((tuple(t.shape), t.dtype) for t in tensors) + (sum(1 for p in m.parameters() if p.requires_grad), sum(1 for x in m.modules() if x.training))
-
     def _eager(self, img, mask):
-        loss, norm = self.replica._run(self.parts, img, mask, lambda f, *a: graph_step._detached(f(*a)))
-        return loss, norm
+        return self.replica._run(self.parts, img, mask, lambda f, *a: graph_step._detached(f(*a)))
 
     def _capture_graphs(self, img, mask):
         """-> (graphs, (loss, norm)): the parts recorded in order from one pool.  Nothing executes and no collective is issued (the unit tests replace this method)."""
-        self.static_in = (img.clone(), mask.clone())
-        self.optimizer.capture_begin()
         graphs, pool = [], None
-        from . import functional
-        functional.flush_num_batches_tracked()
-        torch.cuda.synchronize()
 
         def call(fn, *args):
             nonlocal pool
             g = torch.cuda.CUDAGraph()
-            a = self.static_in if args else ()
             with torch.cuda.graph(g, pool=pool, capture_error_mode='thread_local'):
-                out = graph_step._detached(fn(*a))
+                out = graph_step._detached(fn(*args))
             if pool is None:
                 pool = g.pool()
             graphs.append(g)
             return out
         return graphs, self.replica._run(self.parts, img, mask, call, collectives=False)
 
-    def _capture(self, img, mask, key):
-        """One capture attempt on every rank.  True: self.graphs holds this step, not yet run."""
-        self.graphs, err = None, None
-        try:
-            graphs, outs = self._capture_graphs(img, mask)
-        except Exception as e:                            # noqa: BLE001  (whatever it was, the other ranks must hear about it)
-            graphs, outs, err = None, None, e
-            if torch.cuda.is_available():
-                from . import ops
-                ops.after_failed_capture()
-        if not self.replica.agree(err is None, signature=key):
-            self.graphs, self.key = None, None
-            from . import functional
-            functional.after_failed_capture()                # counters queued and caches filled by the attempt (here or on the rank that did capture): nothing of it ran
-            self.failures += 1
-            graph_step.STATS['failures'] += 1
-            import logging
-            logging.getLogger('Segmentation').warning('bucket_step: capture failed on %s (%s); every rank issues this step kernel by kernel, %s',
-                                                      'this rank' if err is not None else 'another rank',
-                                                      '%s: %s' % (type(err).__name__, str(err).splitlines()[0] if str(err) else '') if err is not None else 'its log has the reason',
-                                                      'then another attempt' if self.failures < 3 else 'and all later ones')
-            if self.failures >= 3:
-                self.warmup = float('inf')
-            return False
-        self.graphs, self.outs, self.key = graphs, outs, key
-        self.bn_training = any(isinstance(x, torch.nn.modules.batchnorm._BatchNorm) and x.training for x in self.replica.modules())
-        self.static_grads = [(p, p.grad) for p in self.replica.parameters() if p.grad is not None]
-        graph_step.STATS['captures'] += 1
-        return True
+    def _agree(self, ok, key):
+        return self.replica.agree(ok, signature=key)
 
-    def __call__(self, img, mask):
-        if self.eager_reason is not None:
-            return self._eager(img, mask)
-        key = self._state_key((img, mask))
-        fresh = False
-        if key != self.key or self.graphs is None:
-            n = self.seen.get(key, 0)
-            if n < self.warmup:
-                self.seen[key] = n + 1
-                return self._eager(img, mask)
-            if not self._capture(img, mask, key):
-                return self._eager(img, mask)             # nothing of the failed attempt has run: this is the step's one and only execution, on every rank
-            fresh = True                                  # static_in holds this batch already
-        if not fresh:
-            for dst, src in zip(self.static_in, (img, mask)):
-                dst.copy_(src, non_blocking=True)
-        for p, g in self.static_grads:
-            if p.grad is not g:
-                p.grad = g
-        it = iter(self.graphs)
+    def _warn_failed(self, err, last):
+        logging.getLogger('Segmentation').warning('bucket_step: capture failed on %s (%s); every rank issues this step kernel by kernel, %s',
+                                                  'this rank' if err is not None else 'another rank',
+                                                  '%s: %s' % (type(err).__name__, str(err).splitlines()[0] if str(err) else '') if err is not None else 'its log has the reason',
+                                                  'and all later ones' if last else 'then another attempt')
+
+    def _replay(self, tensors):
+        it = iter(self.graph)
 
         def call(fn, *args):
             if fn is self.parts[2]:
                 self.optimizer.graph_prepare()
             next(it).replay()
-        self.replica._run(self.parts, img, mask, call)
-        self.replays += 1
-        graph_step.STATS['replays'] += 1
-        self._invalidate()
-        return self.outs
-
-    def _invalidate(self):
-        from . import functional
-        functional.weights_changed()
-        if self.bn_training:
-            functional.running_stats_changed()
-
-    @property
-    def graph(self):
-        return self.graphs
+        self.replica._run(self.parts, *tensors, call)

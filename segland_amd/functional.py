@@ -844,10 +844,20 @@ def _base_chain(model, S_b, dtype, frozen):
     return out
 
 
+def unwrapped(model):
+    """The module behind any `.module` wrappers (engine.ModuleWrapper, bucket_step.BucketedReplica, nn.DataParallel / DistributedDataParallel): the one that owns
+    `base_emb`, `classifier` and the `_sl_base_chain` entry."""
+    while getattr(model, 'module', None) is not None:
+        model = model.module
+    return model
+
+
 def base_chain_key(model):
     """What the cached rows of _base_chain are computed from (versions + addresses of the frozen base classifier's weights and of base_emb), or None when the cache does
-    not apply.  graph_step.GraphedStep puts it into its state key: a captured fine-tune step has the cached tensors baked in, so a change of these weights behind a
-    graph (load_state_dict, init_cls_n) must force a re-capture -- every other weight is picked up through its pointer, these rows are not (round-5 advisor)."""
+    not apply.  The step graphs put it into their state key (graph_step.StepLifecycle): a captured fine-tune step has the cached tensors baked in, so a change of these
+    weights behind a graph (load_state_dict, init_cls_n) must force a re-capture -- every other weight is picked up through its pointer, these rows are not (round-5
+    advisor).  `model` may be wrapped: the drivers hand the step graphs what engine.data_parallel returned."""
+    model = unwrapped(model)
     emb = getattr(model, 'base_emb', None)
     cls = getattr(model, 'classifier', None)
     if not (_BASE_CHAIN_CACHE and getattr(model, 'is_ft', False) and emb is not None and cls is not None and not emb.requires_grad):

@@ -199,6 +199,72 @@ def test_graphed_ft_step_equals_eager(hip, family, sgd):
         assert torch.equal(par_r[n], par_g[n]), n
 
 
+def test_graphed_ft_step_behind_the_wrapper_recaptures_when_the_base_classifier_changes(hip):
+    """What ft_pop.main really builds: GraphedStep and ft_graph_body on engine.ModuleWrapper(model) (engine.data_parallel on one GPU).  The frozen base classifier's
+    prototype rows are cached tensors baked into the captured step (functional._base_chain); the lifecycle must look behind the wrapper for them: `baked` holds the cache
+    entry the graph reads, and a change of classifier[0].weight in VALUE before iteration 4 (what load_state_dict / init_cls_n do behind a captured step) re-captures
+    after two new warm-up steps instead of replaying the stale rows.  PSPNet-POP resnet50 fp32, os 8, pairs of 2 x 96 x 128, segland_amd.optim.SGD in the graph, ten
+    iterations over six batches: losses, gradient norms and trainable parameters equal the kernel-by-kernel loop bit for bit."""
+    from segland_amd import engine, graph_step
+    from segland_amd.ft_pop import ft_graph_body, ft_iteration, ft_iteration_graphed
+    from segland_amd.loss.criterion import OrthLoss
+    from segland_amd.networks.pspnet_pop import GFSS_Model
+    from segland_amd.optim import SGD
+    from segland_amd.utils.pyt_utils import NativeScalerWithGradNormCount, get_parameters
+    H, W = 96, 128
+    ref = GFSS_Model(n_base=7, criterion=OrthLoss(255), pretrained_model=None, is_ft=True, n_novel=4, compute_dtype=torch.float32, backbone='resnet50', dilated=True, os=8)
+    fm.load_formula_weights(ref)
+    ref = ref.to(DEV)
+    ref.init_cls_n()
+    got = copy.deepcopy(ref)
+    data = []
+    for k in range(6):
+        img = fm.formula_image(2, H, W, 'gf/img%d' % k).to(DEV)
+        img_b = fm.formula_image(2, H, W, 'gf/imgb%d' % k).to(DEV)
+        mask = (fm.formula_mask(2, H, W, 4, 'gf/mask%d' % k, block=16, ignore_rows=4) + 8)
+        mask[mask > 11] = 255
+        mask_b = fm.formula_mask(2, H, W, 8, 'gf/maskb%d' % k, block=16, ignore_rows=0)
+        data.append((img, mask.to(DEV), img_b, mask_b.to(DEV)))
+
+    def run(model, graphed):
+        model.train_mode()
+        opt = SGD(get_parameters(model, lr=1e-2, freeze_backbone=True), lr=1e-2, momentum=0.9, weight_decay=5e-4)
+        opt.zero_grad()
+        sc = NativeScalerWithGradNormCount()
+        wrapped = engine.ModuleWrapper(model)
+        g = graph_step.GraphedStep(ft_graph_body(wrapped, optimizer=opt), wrapped, opt, warmup=2) if graphed else None
+        log = []
+        for k in range(10):
+            if k == 4:
+                with torch.no_grad():
+                    model.classifier[0].weight.mul_(1.5)
+            for grp in opt.param_groups:
+                grp['lr'] = 1e-2 * (1 - k / 10.0)
+            img, mask, img_b, mask_b = data[k % 6]
+            batch = (img, mask, img_b, mask_b.clone())
+            d, gn = ft_iteration_graphed(g, opt, batch, DEV) if graphed else ft_iteration(model, opt, sc, batch, DEV)
+            log.append((float(d['total_loss'].detach()), float(gn)))
+            if graphed and k == 3:
+                first.append((g.baked, g.replays))
+        return log, {n: p.detach().float().cpu() for n, p in model.named_parameters() if p.requires_grad}, g
+
+    first = []
+    log_r, par_r, _ = run(ref, False)
+    before = dict(graph_step.STATS)
+    log_g, par_g, g = run(got, True)
+    d = {k: graph_step.STATS[k] - before[k] for k in before}
+    print(log_r, log_g, d)
+    assert log_r == log_g, 'first differing iteration: %s' % [k for k in range(10) if log_r[k] != log_g[k]][:1]
+    assert par_r.keys() == par_g.keys() and len(par_r) > 0
+    for n in par_r:
+        assert torch.equal(par_r[n], par_g[n]), n
+    assert d == {'captures': 2, 'replays': 2 + 4, 'failures': 0}, d       # 0-1 warm-up, 2 capture, 3 replay, 4-5 warm-up again, 6 capture, 7-9 replays
+    assert first[0][0] is not None and first[0][1] == 2, 'the first capture did not hold on to the base-chain cache entry'
+    ent = got.__dict__.get('_sl_base_chain')
+    assert g.baked is not None and g.baked is not first[0][0] and ent is not None and g.baked[0] == ent[0]
+    assert len(ent[1]) == len(g.baked[1]) and all(a is b for a, b in zip(ent[1], g.baked[1])), 'the graph reads tensors that nothing keeps alive'
+
+
 def test_train_base_replays_the_step_with_loader_workers(hip, tmp_path):
     """train_base.py end to end with the drivers' defaults that matter here -- DataLoader workers and the pin-memory thread alive while the
     step is captured (thread_local capture mode) -- must capture once and replay every later iteration; BatchNorm's num_batches_tracked,

@@ -159,6 +159,14 @@ def test_ft_base_chain_cache_engages_and_is_part_of_the_graph_key(hip):
     with torch.no_grad():
         m.classifier[0].weight.add_(0.0)                  # an in-place write (what load_state_dict does): the version counter moves
     assert gs._state_key((img,)) != k0 and sf.base_chain_key(m) is not None
+    # ... and the same behind the wrapper the fine-tune driver hands over (engine.data_parallel on one GPU)
+    from segland_amd import engine
+    gw = graph_step.GraphedStep(lambda *a: None, engine.ModuleWrapper(m))
+    k1 = gw._state_key((img,))
+    assert k1[-1] is not None and k1[-1] == sf.base_chain_key(m)
+    with torch.no_grad():
+        m.classifier[0].weight.add_(0.0)
+    assert gw._state_key((img,)) != k1
 
 
 @pytest.mark.parametrize('cin,cout,B,H', [(128, 128, 16, 128), (256, 256, 16, 128), (128, 256, 24, 64)])

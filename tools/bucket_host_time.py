@@ -3,7 +3,7 @@
 all-reduces, against the GPU time of the step.  Measured: 8.2 ms of host time per 25.8 ms step (hipGraphLaunch of the ~450-node first graph 4.9 ms, second 2.1, third 0.7, all-reduce calls 0.15):
 the host runs ahead of the GPU, the 1.9 % the bucket step costs at world size 1 is on the GPU side of the eager section between the graphs."""
 import os, sys, time
-sys.path.insert(0, '/root/repo' if os.path.exists('/root/repo/bench.py') else os.getcwd())
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault('MASTER_ADDR', '127.0.0.1'); os.environ.setdefault('MASTER_PORT', '29561'); os.environ.setdefault('RANK', '0'); os.environ.setdefault('WORLD_SIZE', '1')
 import torch, torch.distributed as dist
 dist.init_process_group('nccl', rank=0, world_size=1)
