@@ -420,7 +420,7 @@ int sl_pop_decompose_bwd(int dtype, const void* dg, const void* feats, const flo
 /* ------------------------------------------------------------------------------------------------ loss
  * loss/criterion.py:51-52: F.interpolate(bilinear, align_corners=True) to the label size fused with
  * CrossEntropyLoss(ignore_index, mean); the H x W logits are never written.
- * sl_upsample_ce_fwd/bwd, sl_pseudo_label, sl_upsample_argmax and sl_upsample_logits take 1 <= K <= 33 logit channels (background + 32 prototypes); more is SL_EINVAL
+ * sl_upsample_ce_fwd/bwd, sl_pseudo_label, sl_upsample_argmax, sl_upsample_logits and sl_tta_fuse take 1 <= K <= 33 logit channels (background + 32 prototypes); more is SL_EINVAL
  * and the message names the limit.  The backward's tiled kernel cuts more than 16 channels into slices of at most 16 (its LDS holds one slice of the tile's footprint). */
 int sl_upsample_ce_rows(int B, int H, int W);
 /* partial[blk][2] = (sum of pixel losses, number of valid pixels) */
@@ -473,6 +473,19 @@ int sl_upsample_argmax(const float* logits, int B, int K, int h, int w, int H, i
                        sl_stream_t stream);
 /* eval_base.py:168,189-190: the upsampled logits themselves (the 'outputs' array of the per-tile .mat probability dumps), NCHW float */
 int sl_upsample_logits(const float* logits, int B, int K, int h, int w, int H, int W, float* out, sl_stream_t stream);
+/* Test-time augmentation: up to SL_TTA_MAX_VIEWS views of one model (scales, each plain and flipped) fused on the label grid in ONE kernel; the per-view H x W maps
+ * of the torch composition (F.interpolate, softmax, flip, +=) are never written.  View i is float [B][K][h_i][w_i], contiguous, on the device; the struct is a host
+ * struct read during the call and handed to the kernel by value (no device table, no copy, no synchronisation: capturable).  For output pixel (b, Y, X):
+ *   Y' = (flip_i & 2) ? H-1-Y : Y,  X' = (flip_i & 1) ? W-1-X : X,  u_i = the bilinear (align_corners=True) value of view i at (Y', X')
+ *     == torch.flip(F.interpolate(l_i, (H, W), mode='bilinear', align_corners=True), dims): the un-flip is an index remap;
+ *   t_i = softmax_k(u_i) (mode 0: max subtracted, expf) or u_i (mode 1);  fused[k] = (sum_i weight_i t_i[k]) / (sum_i weight_i), both sums in list order in float,
+ *   term 0 starting the sum;  labels = argmax_k fused[k], first maximum wins.
+ * labels: uint8 [B][H][W] (required); fused: float [B][K][H][W] or NULL (then one byte per pixel is all that is written).  1 <= n <= SL_TTA_MAX_VIEWS, 1 <= K <= 33,
+ * B, H, W, h_i, w_i >= 1, flip_i in [0, 3], weight_i finite and > 0, mode 0 or 1, no NULL but fused, else SL_EINVAL before any launch.  No atomics: two runs give the
+ * same bits. */
+#define SL_TTA_MAX_VIEWS 16
+typedef struct SlTtaViews { int n; const float* logits[SL_TTA_MAX_VIEWS]; int h[SL_TTA_MAX_VIEWS], w[SL_TTA_MAX_VIEWS], flip[SL_TTA_MAX_VIEWS]; float weight[SL_TTA_MAX_VIEWS]; } SlTtaViews;
+int sl_tta_fuse(const SlTtaViews* views, int B, int K, int H, int W, int mode, uint8_t* labels, float* fused, sl_stream_t stream);
 /* fusemat.py:35-52: argmax over classes of the mean of n_models probability maps [K][hw] (mats_dev: device array of n_models float pointers),
  * summed in list order like the reference's in-place `mats[idx] += prob` */
 int sl_fuse_argmax(const void* mats_dev, int n_models, int K, long long hw, uint8_t* labels, sl_stream_t stream);

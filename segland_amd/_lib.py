@@ -59,6 +59,14 @@ class SlColsumBatch(C.Structure):
                 ('C', C.c_int * SL_COLSUM_MAX)]
 
 
+SL_TTA_MAX_VIEWS = 16
+
+
+class SlTtaViews(C.Structure):
+    _fields_ = [('n', C.c_int), ('logits', C.c_void_p * SL_TTA_MAX_VIEWS), ('h', C.c_int * SL_TTA_MAX_VIEWS), ('w', C.c_int * SL_TTA_MAX_VIEWS),
+                ('flip', C.c_int * SL_TTA_MAX_VIEWS), ('weight', C.c_float * SL_TTA_MAX_VIEWS)]
+
+
 _CTYPE = {
     'int': C.c_int, 'long long': C.c_longlong, 'float': C.c_float, 'size_t': C.c_size_t, 'sl_stream_t': C.c_void_p,
 }

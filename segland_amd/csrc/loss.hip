@@ -5,7 +5,7 @@
 
 namespace {
 
-constexpr int KMAXC = 33;  // max logit channels (background + 32 prototypes) of sl_upsample_ce_* / sl_pseudo_label / sl_upsample_argmax / sl_upsample_logits: the ONE limit of this file
+constexpr int KMAXC = 33;  // max logit channels (background + 32 prototypes) of sl_upsample_ce_* / sl_pseudo_label / sl_upsample_argmax / sl_upsample_logits / sl_tta_fuse: the ONE limit of this file
 constexpr int KNC = 16;    // up to KNC channels run on the <KNC> instantiations and the one-pass tiled backward (device code as before the wide head); more on <KMAXC> and the
                            // channel-sliced tiled backward.  KW below is the per-thread array width of an instantiation.
 
@@ -713,6 +713,52 @@ __global__ void upsample_logits_kernel(UpGeom g, const float* __restrict__ lg, f
   }
 }
 
+// Test-time augmentation (sl_tta_fuse): the views of ONE model -- scales, each plain and flipped -- fused on the label grid.  TtaViews is SlTtaViews as the kernel takes it
+// by value (no device table, no copy): the pointers and sizes of the views plus what the host works out once, the align_corners scales and the weight sum (list order).
+struct TtaViews { int n; float wsum; const float* lg[SL_TTA_MAX_VIEWS]; int h[SL_TTA_MAX_VIEWS], w[SL_TTA_MAX_VIEWS], flip[SL_TTA_MAX_VIEWS]; float sy[SL_TTA_MAX_VIEWS], sx[SL_TTA_MAX_VIEWS], wt[SL_TTA_MAX_VIEWS]; };
+
+// One thread per output pixel, the views in a runtime loop (the view index is wave-uniform: the view's parameters are scalar loads from the kernel arguments).  A flipped view is read
+// at the mirrored pixel -- torch.flip(F.interpolate(l, (H, W), align_corners=True)) is an index remap of pixel_logits, not a second interpolation.  mode 0: t = softmax_k
+// (max subtracted, expf, one division per channel), mode 1: t = the interpolated logits.  fused_k = (sum_i wt_i t_ik) / wsum with term 0 starting the sum; the label is
+// the first maximum of fused (torch.argmax).  fused may be null: then one byte per pixel is all that is written.
+template <int KW>
+__global__ __launch_bounds__(256) void tta_fuse_kernel(TtaViews a, int B, int K, int H, int W, int mode, uint8_t* __restrict__ labels, float* __restrict__ fused) {
+  const long long total = (long long)B * H * W;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += gridDim.x * 256LL) {
+    const int X = (int)(i % W); const long long r = i / W;
+    const int Y = (int)(r % H), b = (int)(r / H);
+    float acc[KW];
+    for (int n = 0; n < a.n; ++n) {
+      UpGeom g; g.B = B; g.K = K; g.h = a.h[n]; g.w = a.w[n]; g.H = H; g.W = W; g.sy = a.sy[n]; g.sx = a.sx[n];
+      const int f = a.flip[n];
+      const float wt = a.wt[n];
+      float v[KW];
+      pixel_logits<KW>(g, a.lg[n], b, (f & 2) ? H - 1 - Y : Y, (f & 1) ? W - 1 - X : X, v);
+      if (mode == 0) {
+        float m = v[0];
+#pragma unroll
+        for (int k = 1; k < KW; ++k) if (k < K) m = fmaxf(m, v[k]);
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < KW; ++k) if (k < K) { v[k] = expf(v[k] - m); s += v[k]; }
+#pragma unroll
+        for (int k = 0; k < KW; ++k) if (k < K) v[k] = v[k] / s;
+      }
+#pragma unroll
+      for (int k = 0; k < KW; ++k) acc[k] = n == 0 ? wt * v[k] : acc[k] + wt * v[k];
+    }
+    const size_t plane = (size_t)H * W;
+    int best = 0; float bv = 0.f;
+#pragma unroll
+    for (int k = 0; k < KW; ++k) if (k < K) {
+      const float fk = acc[k] / a.wsum;
+      if (k == 0 || fk > bv) { bv = fk; best = k; }                                     // first maximum wins (torch.argmax)
+      if (fused) fused[((size_t)b * K + k) * plane + (size_t)Y * W + X] = fk;
+    }
+    labels[i] = (uint8_t)best;
+  }
+}
+
 // fusemat.py:35-52: mats[idx] += prob in list order, argmax(mat / n, axis=0): float sum in the same order, first maximum wins (np.argmax)
 __global__ void fuse_argmax_kernel(const float* const* __restrict__ mats, int n, int K, long long hw, uint8_t* __restrict__ out) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < hw; i += (long long)gridDim.x * blockDim.x) {
@@ -984,6 +1030,26 @@ extern "C" int sl_upsample_logits(const float* logits, int B, int K, int h, int 
   SL_REQUIRE(K <= KMAXC, "upsample_logits: %d logit channels; this build holds at most %d", K, KMAXC);
   const UpGeom g = make_up(B, K, h, w, H, W);
   return sl_launch("upsample_logits_kernel", K <= KNC ? upsample_logits_kernel<KNC> : upsample_logits_kernel<KMAXC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, logits, out);
+}
+
+extern "C" int sl_tta_fuse(const SlTtaViews* views, int B, int K, int H, int W, int mode, uint8_t* labels, float* fused, sl_stream_t stream) {
+  SL_REQUIRE(views && labels && B > 0 && H > 0 && W > 0, "tta_fuse: bad args");
+  SL_REQUIRE(K >= 1 && K <= KMAXC, "tta_fuse: %d logit channels; this build holds at most %d", K, KMAXC);
+  SL_REQUIRE(mode == 0 || mode == 1, "tta_fuse: mode %d is neither 0 (mean of the softmax probabilities) nor 1 (mean of the upsampled logits)", mode);
+  SL_REQUIRE(views->n >= 1 && views->n <= SL_TTA_MAX_VIEWS, "tta_fuse: %d views; one call fuses 1 to %d", views->n, SL_TTA_MAX_VIEWS);
+  TtaViews a = {};                                         // the unused slots stay zero: every word of the kernel argument is defined
+  a.n = views->n;
+  for (int i = 0; i < a.n; ++i) {
+    SL_REQUIRE(views->logits[i] && views->h[i] > 0 && views->w[i] > 0, "tta_fuse: view %d: bad args", i);
+    SL_REQUIRE(views->flip[i] >= 0 && views->flip[i] <= 3, "tta_fuse: view %d: flip %d outside [0, 3] (bit 0 horizontal, bit 1 vertical)", i, views->flip[i]);
+    SL_REQUIRE(views->weight[i] > 0.f && views->weight[i] <= 3.402823466e38f, "tta_fuse: view %d: weight %g is not a finite value > 0", i, (double)views->weight[i]);
+    a.lg[i] = views->logits[i]; a.h[i] = views->h[i]; a.w[i] = views->w[i]; a.flip[i] = views->flip[i]; a.wt[i] = views->weight[i];
+    a.sy[i] = ac1_scale(a.h[i], H); a.sx[i] = ac1_scale(a.w[i], W);
+    a.wsum = i == 0 ? a.wt[0] : a.wsum + a.wt[i];        // list order, term 0 starts the sum
+  }
+  SL_REQUIRE(a.wsum <= 3.402823466e38f, "tta_fuse: the weights sum to %g", (double)a.wsum);
+  return sl_launch("tta_fuse_kernel", K <= KNC ? tta_fuse_kernel<KNC> : tta_fuse_kernel<KMAXC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, a, B, K, H, W, mode,
+                   labels, fused);
 }
 
 extern "C" int sl_fuse_argmax(const void* mats_dev, int n_models, int K, long long hw, uint8_t* labels, sl_stream_t stream) {

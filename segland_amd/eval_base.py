@@ -8,6 +8,10 @@ Per batch: logits (eval-mode forward, folded BN) -> upsample(align_corners=True)
 eval_base.py:168 are never written) -> confusion-matrix kernel on the label grid; mIoU over base / novel / all classes from the
 accumulated matrix exactly as eval_base.py:193-199.  The unlabeled-test branch (GeoTIFF + .mat dumps, eval_base.py:178-191) needs
 rasterio and is row f-2 of SURVEY.md section 8.
+
+--tta-scales 0.75,1.0,1.25 --tta-flip True [--tta-mode prob|logit]: test-time augmentation (segland_amd/tta.py).  One forward per view (scale, plain / mirrored), then
+ONE kernel upsamples every view to the same grid, takes the softmax (prob) or not (logit), un-flips, averages and takes the argmax; with --save-prob the .mat holds the
+fused map.  With the default flags (one scale of 1.0, no flip) the loop body is the single-view code above and the fusion kernel is never called.
 """
 import argparse
 import os
@@ -19,6 +23,7 @@ import torch
 from . import dataset as dataset_pkg
 from . import networks
 from . import ops
+from . import tta
 from .drivers import batch_to_device, checkpoint_or_none, compute_dtype, resolve, str2bool
 from .engine import Engine
 from .utils import pyt_utils as my_utils
@@ -46,21 +51,29 @@ def get_parser():
     p.add_argument('--fp16', action='store_true')
     p.add_argument('--save-prob', action='store_true', help="dump the upsampled logits of every tile as <save-path>/prob_<seed>/<id>.mat ({'outputs': [1,K,H,W]}, "
                    'eval_base.py:189-190) for segland_amd.fusemat, plus the predicted label map as a palette PNG')
+    p.add_argument('--tta-scales', type=str, default='1.0', help="test-time augmentation: image scales of the views, e.g. '0.75,1.0,1.25' (sides rounded to multiples of 32)")
+    p.add_argument('--tta-flip', type=str2bool, default='False', help='test-time augmentation: add the horizontally mirrored view of every scale')
+    p.add_argument('--tta-mode', type=str, default='prob', choices=['prob', 'logit'], help='the views are fused as softmax probabilities or as upsampled logits (one kernel, '
+                   'segland_amd.tta); with --save-prob the .mat holds the fused map')
     p.add_argument('--allow-random-init', action='store_true', help='evaluate random weights when --restore-from does not exist')
     return p
+
+
+def label_grid(label, ignore_label, pad_to_longside=False):
+    """(label, size) the prediction is scored at: the label as it is, or (eval_ft.py:166-181) padded with ignore to a square of its long side."""
+    h, w = label.shape[-2:]
+    if not pad_to_longside:
+        return label, (h, w)
+    side = max(h, w)
+    pad = torch.full((label.shape[0], side, side), ignore_label, dtype=label.dtype, device=label.device)
+    pad[:, :h, :w] = label
+    return pad, (side, side)
 
 
 def confusion_of_batch(logits, label, num_classes, ignore_label, pad_to_longside=False):
     """eval_base.py:166-177 (eval_ft.py:166-181 with pad_to_longside): prediction at the label grid and its confusion counts."""
     from . import ops
-    h, w = label.shape[-2:]
-    if pad_to_longside:                     # eval_ft.py: upsample to a square of the long side, labels padded with ignore
-        side = max(h, w)
-        pad = torch.full((label.shape[0], side, side), ignore_label, dtype=label.dtype, device=label.device)
-        pad[:, :h, :w] = label
-        label, size = pad, (side, side)
-    else:
-        size = (h, w)
+    label, size = label_grid(label, ignore_label, pad_to_longside)
     pred = ops.upsample_argmax(logits.float().contiguous(), size)
     return pred, ops.confusion_matrix(pred, label.contiguous(), num_classes, ignore_label)
 
@@ -94,11 +107,16 @@ def dump_probabilities(logits, size, pred, ids, out_dir, data_dir=None):
     """eval_base.py:168,180-190: per tile `<id>.mat` = {'outputs': [1,K,H,W] logits upsampled with align_corners=True} (the input of fusemat.py), `<id>.tif` = the
     argmax as a colormapped single-band TIFF next to the .mat directory (write_prediction_tiff: the reference's GeoTIFF when rasterio and the source tile
     <data_dir>/image/<id>.tif exist), and `<id>.png`, the same as a palette image."""
-    import scipy.io
     from . import ops
+    dump_maps(ops.upsample_logits(logits.float().contiguous(), tuple(size)), size, pred, ids, out_dir, data_dir)
+
+
+def dump_maps(up, size, pred, ids, out_dir, data_dir=None):
+    """The files of dump_probabilities from a ready [B,K,H,W] map: the upsampled logits, or the fused map of the test-time augmentation (cut to `size`)."""
+    import scipy.io
     from .fusemat import COLORMAP
     os.makedirs(out_dir, exist_ok=True)
-    up = ops.upsample_logits(logits.float().contiguous(), tuple(size)).cpu().numpy()
+    up = up[:, :, :size[0], :size[1]].cpu().numpy()
     pred = pred.cpu().numpy()
     for b in range(up.shape[0]):
         name = str(ids[b].item() if hasattr(ids[b], 'item') else ids[b])
@@ -151,6 +169,8 @@ def main(argv=None, ft=False):
         seg_model = model_cls(n_base=args.base_classes, backbone=args.backbone, dilated=(args.os != 32), os=args.os,
                               n_novel=args.novel_classes, is_ft=ft, compute_dtype=compute_dtype(args))
         model = engine.data_parallel(seg_model.to(engine.device))
+        tta_scales = tta.parse_scales(args.tta_scales)
+        tta_on, tta_sizes = tta.is_on(tta_scales, args.tta_flip), None
         results = {}
         for seed in map(int, args.random_seed.split(',')):
             path = (args.restore_from[:-4] + '_%d.pth' % seed) if ft else args.restore_from       # eval_ft.py:154
@@ -162,6 +182,21 @@ def main(argv=None, ft=False):
                 # ready tensors (synthetic) or raw uint8 tiles + draws prepared on the GPU (oem / synthetic_raw: Engine installs raw_collate)
                 image, label = batch_to_device(batch, testset, engine.device)
                 ids = batch[2]
+                if tta_on:
+                    # the views of this batch fused on the grid the single-view code scores at; with --save-prob the .mat holds the fused map
+                    label_p, size = label_grid(label, args.ignore_label, pad_to_longside=ft) if label is not None else (None, tuple(image.shape[-2:]))
+                    if tta_sizes is None and engine.is_main:
+                        tta_sizes = tta.view_sizes(image.shape[-2], image.shape[-1], tta_scales)
+                        (logger.info if logger else print)('test-time augmentation: %d views per tile (images %s%s), mode %s, fused at %dx%d' % (
+                            len(tta_sizes) * (2 if args.tta_flip else 1), ', '.join('%dx%d' % s for s in tta_sizes), '; each plain and mirrored' if args.tta_flip else '',
+                            args.tta_mode, size[0], size[1]))
+                    pred, fused = tta.predict(model, image, size, scales=tta_scales, flip=args.tta_flip, mode=args.tta_mode, want_map=bool(args.save_prob and args.save_path))
+                    if label is not None:
+                        cm += ops.confusion_matrix(pred, label_p.contiguous(), args.num_classes, args.ignore_label)
+                    if fused is not None:
+                        dump_maps(fused, tuple(image.shape[-2:]) if label is None else tuple(label.shape[-2:]), pred, ids, osp.join(args.save_path, 'prob_%d' % seed),
+                                  data_dir=getattr(args, 'data_dir', None))
+                    continue
                 with torch.no_grad():
                     logits = model(image)
                 if label is None:

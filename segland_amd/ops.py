@@ -1149,6 +1149,35 @@ def fuse_argmax(mats):
     return out
 
 
+TTA_MODES = {'prob': 0, 'logit': 1}
+
+
+def tta_fuse(views, size, mode='prob', want_map=False):
+    """Test-time augmentation fused on the label grid in one kernel (sl_tta_fuse): views = [(logits [B,K,h_i,w_i] float, flip, weight), ...] of one model, flip bit 0 =
+    the view saw the image flipped horizontally, bit 1 vertically.  mode 'prob': weighted mean of the views' softmax of the upsampled (align_corners=True) logits, 'logit':
+    of the upsampled logits.  Returns (labels uint8 [B,H,W], the fused map float [B,K,H,W] if want_map else None); without the map one byte per pixel is written."""
+    if mode not in TTA_MODES:
+        raise RuntimeError("tta_fuse: mode %r is neither 'prob' nor 'logit'" % (mode,))
+    views = list(views)
+    if not 1 <= len(views) <= _lib.SL_TTA_MAX_VIEWS:
+        raise RuntimeError('tta_fuse: %d views; one call fuses 1 to %d' % (len(views), _lib.SL_TTA_MAX_VIEWS))
+    first = views[0][0]
+    if first.dim() != 4:
+        raise RuntimeError('tta_fuse: every view must be float32 [B,K,h,w]')
+    B, K = first.shape[:2]
+    v = _lib.SlTtaViews()
+    v.n = len(views)
+    for i, (lg, flip, weight) in enumerate(views):
+        if lg.dtype != torch.float32 or lg.dim() != 4 or tuple(lg.shape[:2]) != (B, K) or lg.device != first.device:
+            raise RuntimeError('tta_fuse: every view must be float32 [%d,%d,h,w] on %s (view %d: %s %s on %s)' % (B, K, first.device, i, lg.dtype, tuple(lg.shape), lg.device))
+        v.logits[i], v.h[i], v.w[i], v.flip[i], v.weight[i] = _p(lg), lg.shape[2], lg.shape[3], int(flip), float(weight)
+    H, W = int(size[0]), int(size[1])
+    labels = torch.empty((B, H, W), dtype=torch.uint8, device=first.device)
+    fused = _f32((B, K, H, W), first.device) if want_map else None
+    check(_lib.lib().sl_tta_fuse(C.byref(v), B, K, H, W, TTA_MODES[mode], _p(labels), _p(fused), _s()), 'tta_fuse')
+    return labels, fused
+
+
 def iou_hist(pred_u8, target, K, ignore_index):
     hist = torch.zeros((3, K), dtype=torch.int64, device=target.device)
     check(_lib.lib().sl_iou_hist(_p(pred_u8), _p(target), target.numel(), K, ignore_index, _p(hist), _s()), 'iou_hist')
