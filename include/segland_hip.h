@@ -464,6 +464,29 @@ int sl_upsample_ce_dice_finalize(const float* partial, const float* class_weight
 int sl_upsample_ce_dice_bwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing,
                             const float* loss3, const float* coef, const float* gscale, int B, int K, int h, int w, int H, int W,
                             int ignore_index, float* dlogits, sl_stream_t stream);
+/* Online hard-pixel mining (OHEM, bootstrapped cross-entropy) in front of the criterion above: three passes that turn (logits, target) into a MINED label map, the
+ * target with every dropped pixel set to ignore_index; the forward, finalize and backward entry points above then run on it unchanged.  Per call (per GPU batch):
+ *   valid pixel: label != ignore_index and inside [0, K) (the rule of the loss kernels); n = number of valid pixels;
+ *   p = expf(v_t - m) / s for a valid pixel, v = the bilinear (align_corners=True) logits, m = max_k v_k, s = sum_k expf(v_k - m) in index order (the forward kernel's
+ *     arithmetic; class weights and label smoothing do not enter p);
+ *   k = min(min_kept, n);  q = the k-th smallest p (1-based) over all valid pixels, exact;  theta = max(thresh, q);
+ *   kept = the valid pixels with p <= theta: every pixel at or below thresh and at least k pixels, all ties at q included;
+ *   mined = target on kept pixels, ignore_index elsewhere, in a buffer of its own (target is never written);  n == 0: mined = target, theta = thresh, counts = 0.
+ * theta and the kept set are constants for the gradient.  Everything stays on the device (no synchronisation, no copy: capturable); the selection is a radix select
+ * over the bit patterns of p (non-negative floats order as unsigned integers) with integer histogram counts (LDS and global integer atomics), no float atomics: two
+ * runs give the same bits.
+ * sl_upsample_ohem_prob: prob[B][H][W] = p for valid pixels, the sentinel 2.0f for the others.  1 <= K <= 33 (the message names the limit), B * H * W < 2^31.
+ * sl_ohem_workspace: bytes of the selection's workspace (0 for a bad shape).
+ * sl_ohem_threshold: theta[0] (float) and counts[3] (int64: n, k, number of kept pixels) from prob[n_pix]; 0 < thresh <= 1, min_kept >= 1, 1 <= n_pix < 2^31,
+ *   ws_bytes >= sl_ohem_workspace, no NULL buffer, else SL_EINVAL before any launch.  Nine small launches on `stream`; the workspace needs no initialisation.
+ * sl_ohem_mine: mined[n_pix] from the STORED prob and theta / counts of sl_ohem_threshold: the value compared is the value selected, never a second evaluation. */
+int sl_upsample_ohem_prob(const float* logits, const int64_t* target, int B, int K, int h, int w, int H, int W, int ignore_index, float* prob,
+                          sl_stream_t stream);
+size_t sl_ohem_workspace(int B, int H, int W);
+int sl_ohem_threshold(const float* prob, long long n_pix, float thresh, long long min_kept, void* workspace, size_t ws_bytes, float* theta, long long* counts,
+                      sl_stream_t stream);
+int sl_ohem_mine(const float* prob, const int64_t* target, const float* theta, const long long* counts, long long n_pix, int ignore_index, int64_t* mined,
+                 sl_stream_t stream);
 /* pspnet_pop.py:221-231: argmax of the upsampled (align_corners=True) [K2][h][w] logits of tile b, ids > 0 shifted
  * by n_base, written into mask[b] where mask == 0 (in place, int64). */
 int sl_pseudo_label(const float* logits, int K2, int h, int w, int64_t* mask, int B, int H, int W, int n_base,

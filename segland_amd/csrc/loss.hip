@@ -851,6 +851,117 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ src, T* __restrict
   }
 }
 
+// ---- Online hard-pixel mining (OHEM, bootstrapped cross-entropy; the contract is in include/segland_hip.h).  Three passes in front of the unchanged loss kernels:
+//   1. upsample_ohem_prob_kernel: p = softmax probability of the true class of every valid pixel (the forward kernel's arithmetic), OHEM_SENTINEL elsewhere;
+//   2. an exact radix select of the k-th smallest p: probabilities are non-negative floats, so their bit patterns order as unsigned integers.  OHEM_PASSES digits of 8
+//      bits from the top; per digit ohem_hist_kernel counts the values under the prefix found so far (LDS histogram, then one integer global atomic per non-empty bin
+//      and block) and the one-block ohem_select_kernel takes the bin that holds the k-th value.  Integer counts only: two runs give the same bits;
+//   3. ohem_mine_kernel: the mined label map from the STORED p and the theta of pass 2.
+// k, q, theta and the counts never leave the device (no synchronisation: capturable).
+constexpr float OHEM_SENTINEL = 2.0f;                // prob of a pixel that is not valid: above every probability, so its top digit (0x40) lies above every valid one (<= 0x3f)
+constexpr int OHEM_PASSES = 4, OHEM_BINS = 256;
+constexpr int OHEM_TOP_VALID = 0x3f;                 // top digit of 1.0f (0x3f800000): the valid pixels are the bins 0 .. OHEM_TOP_VALID of pass 0
+// workspace: unsigned hist[OHEM_PASSES][OHEM_BINS], then the select state
+enum OhemState { OS_PREFIX, OS_KREM, OS_LESS, OS_N, OS_K, OS_LE_THRESH, OS_NWORDS = 8 };
+constexpr int OHEM_WS_WORDS = OHEM_PASSES * OHEM_BINS + OS_NWORDS;
+
+template <int KW>
+__global__ __launch_bounds__(256) void upsample_ohem_prob_kernel(UpGeom g, const float* __restrict__ lg, const int64_t* __restrict__ tgt, int ignore, float* __restrict__ prob) {
+  const long long total = (long long)g.B * g.H * g.W;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += gridDim.x * 256LL) {
+    const long long t = tgt[i];
+    if (t == ignore || t < 0 || t >= g.K) { prob[i] = OHEM_SENTINEL; continue; }
+    const int X = (int)(i % g.W); const long long r = i / g.W;
+    const int Y = (int)(r % g.H), b = (int)(r / g.H);
+    float v[KW];
+    pixel_logits<KW>(g, lg, b, Y, X, v);
+    float vt;
+    const float m = ce_max<KW>(v, (int)t, vt);
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < KW; ++k) if (k < g.K) s += expf(v[k] - m);
+    prob[i] = expf(vt - m) / s;
+  }
+}
+
+__global__ __launch_bounds__(256) void ohem_init_kernel(unsigned* __restrict__ ws) {
+  for (int i = threadIdx.x; i < OHEM_WS_WORDS; i += 256) ws[i] = 0u;
+}
+
+// digit `pass` (8 bits, from the top) of every value whose higher digits equal the prefix selected so far; pass 0 also counts the values <= thresh
+__global__ __launch_bounds__(256) void ohem_hist_kernel(const float* __restrict__ prob, long long n, int pass, float thresh, unsigned* __restrict__ ws) {
+  __shared__ unsigned h[OHEM_BINS];
+  __shared__ unsigned le[4];
+  const int tid = threadIdx.x;
+  h[tid] = 0u;
+  __syncthreads();
+  const int shift = 24 - 8 * pass;
+  const unsigned* st = ws + OHEM_PASSES * OHEM_BINS;
+  const unsigned prefix = pass ? st[OS_PREFIX] : 0u;
+  const unsigned himask = pass ? 0xffffffffu << (shift + 8) : 0u;
+  unsigned nle = 0u;
+  for (long long i = blockIdx.x * 256LL + tid; i < n; i += gridDim.x * 256LL) {
+    const float p = prob[i];
+    const unsigned u = __float_as_uint(p);
+    if (pass == 0) nle += p <= thresh ? 1u : 0u;       // the sentinel is above every threshold
+    if ((u & himask) == prefix) atomicAdd(&h[(u >> shift) & (OHEM_BINS - 1)], 1u);
+  }
+  __syncthreads();
+  if (h[tid]) atomicAdd(&ws[pass * OHEM_BINS + tid], h[tid]);
+  if (pass == 0) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nle += __shfl_xor(nle, o, 64);
+    if ((tid & 63) == 0) le[tid >> 6] = nle;
+    __syncthreads();
+    if (tid == 0 && le[0] + le[1] + le[2] + le[3]) atomicAdd(&ws[OHEM_PASSES * OHEM_BINS + OS_LE_THRESH], le[0] + le[1] + le[2] + le[3]);
+  }
+}
+
+// One block, one thread per bin: the bin of digit `pass` that holds the k-th smallest value extends the prefix.  Pass 0 fixes n (the values below the sentinel's digit)
+// and k = min(min_kept, n); the last pass has the k-th smallest value q itself and writes theta = max(thresh, q) and counts = (n, k, number of values <= theta).
+// n == 0: theta = thresh, counts = 0, and the later passes find k == 0 and write nothing.
+__global__ __launch_bounds__(OHEM_BINS) void ohem_select_kernel(int pass, long long min_kept, float thresh, unsigned* __restrict__ ws, float* __restrict__ theta,
+                                                                long long* __restrict__ counts) {
+  __shared__ unsigned inc[OHEM_BINS];
+  const int tid = threadIdx.x;
+  unsigned* st = ws + OHEM_PASSES * OHEM_BINS;
+  const unsigned c = ws[pass * OHEM_BINS + tid];
+  inc[tid] = c;
+  __syncthreads();
+  for (int o = 1; o < OHEM_BINS; o <<= 1) {             // inclusive prefix sums of the bins
+    const unsigned a = tid >= o ? inc[tid - o] : 0u;
+    __syncthreads();
+    inc[tid] += a;
+    __syncthreads();
+  }
+  const unsigned n = pass == 0 ? inc[OHEM_TOP_VALID] : st[OS_N];
+  const unsigned k = pass == 0 ? (unsigned)(min_kept < (long long)n ? min_kept : (long long)n) : st[OS_K];
+  const unsigned krem = pass == 0 ? k : st[OS_KREM];
+  const unsigned prefix = pass == 0 ? 0u : st[OS_PREFIX], less = pass == 0 ? 0u : st[OS_LESS], le_thresh = st[OS_LE_THRESH];
+  __syncthreads();                                      // every thread has read the state before one of them writes it
+  const unsigned excl = inc[tid] - c;
+  if (krem >= 1u && excl < krem && krem <= inc[tid]) {  // exactly one thread: its bin is not empty
+    const unsigned pre = prefix | ((unsigned)tid << (24 - 8 * pass));
+    st[OS_PREFIX] = pre; st[OS_KREM] = krem - excl; st[OS_LESS] = less + excl;
+    if (pass == 0) { st[OS_N] = n; st[OS_K] = k; }
+    if (pass == OHEM_PASSES - 1) {
+      const float q = __uint_as_float(pre);
+      const unsigned le_q = less + excl + c;            // values <= q: all ties at q are kept
+      theta[0] = fmaxf(thresh, q);
+      counts[0] = n; counts[1] = k; counts[2] = le_q > le_thresh ? le_q : le_thresh;
+    }
+  }
+  if (pass == 0 && n == 0u && tid == 0) { theta[0] = thresh; counts[0] = 0; counts[1] = 0; counts[2] = 0; }
+}
+
+// mined = target where the stored p <= theta (the sentinel never is) and ignore elsewhere; without a valid pixel the map is the target
+__global__ __launch_bounds__(256) void ohem_mine_kernel(const float* __restrict__ prob, const int64_t* __restrict__ tgt, const float* __restrict__ theta,
+                                                        const long long* __restrict__ counts, long long n, int ignore, int64_t* __restrict__ mined) {
+  const float th = theta[0];
+  const bool none = counts[0] == 0;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += gridDim.x * 256LL) mined[i] = (none || prob[i] <= th) ? tgt[i] : (int64_t)ignore;
+}
+
 inline UpGeom make_up(int B, int K, int h, int w, int H, int W) {
   UpGeom g; g.B = B; g.K = K; g.h = h; g.w = w; g.H = H; g.W = W; g.sy = ac1_scale(h, H); g.sx = ac1_scale(w, W);
   return g;
@@ -1005,6 +1116,46 @@ extern "C" int sl_upsample_ce_dice_bwd(const float* logits, const int64_t* targe
   if (!class_weight && label_smoothing == 0.f)
     return launch_ce_bwd<false, true>(g, logits, target, loss3, gscale, ignore_index, dlogits, (hipStream_t)stream, CeW<false>(), cd);
   return launch_ce_bwd<true, true>(g, logits, target, loss3, gscale, ignore_index, dlogits, (hipStream_t)stream, make_cew(class_weight, label_smoothing, K), cd);
+}
+
+// ---- online hard-pixel mining: probability pass, exact k-th smallest selection, mined label map (the kernels above; one call of each per head)
+extern "C" int sl_upsample_ohem_prob(const float* logits, const int64_t* target, int B, int K, int h, int w, int H, int W, int ignore_index, float* prob,
+                                     sl_stream_t stream) {
+  SL_REQUIRE(K >= 1 && K <= KMAXC, "upsample_ohem_prob: %d logit channels; this build holds at most %d", K, KMAXC);
+  SL_REQUIRE(B > 0 && h > 0 && w > 0 && H > 0 && W > 0 && (long long)B * H * W < (1LL << 31), "upsample_ohem_prob: bad shape");
+  SL_REQUIRE(logits && target && prob, "upsample_ohem_prob: null buffer");
+  const UpGeom g = make_up(B, K, h, w, H, W);
+  return sl_launch("upsample_ohem_prob_kernel", K <= KNC ? upsample_ohem_prob_kernel<KNC> : upsample_ohem_prob_kernel<KMAXC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0,
+                   (hipStream_t)stream, g, logits, target, ignore_index, prob);
+}
+
+extern "C" size_t sl_ohem_workspace(int B, int H, int W) { return B > 0 && H > 0 && W > 0 ? OHEM_WS_WORDS * sizeof(unsigned) : 0; }
+
+extern "C" int sl_ohem_threshold(const float* prob, long long n_pix, float thresh, long long min_kept, void* workspace, size_t ws_bytes, float* theta, long long* counts,
+                                 sl_stream_t stream) {
+  SL_REQUIRE(thresh > 0.f && thresh <= 1.f, "ohem_threshold: thresh %g outside (0, 1]", (double)thresh);
+  SL_REQUIRE(min_kept >= 1, "ohem_threshold: min_kept %lld is not >= 1", min_kept);
+  SL_REQUIRE(n_pix > 0 && n_pix < (1LL << 31), "ohem_threshold: %lld pixels; one call selects among 1 to 2^31 - 1", n_pix);
+  SL_REQUIRE(prob && workspace && theta && counts, "ohem_threshold: null buffer");
+  SL_REQUIRE(ws_bytes >= OHEM_WS_WORDS * sizeof(unsigned), "ohem_threshold: workspace %zu < %zu (sl_ohem_workspace)", ws_bytes, OHEM_WS_WORDS * sizeof(unsigned));
+  unsigned* ws = (unsigned*)workspace;
+  const hipStream_t s = (hipStream_t)stream;
+  // 8 values per thread: a block ends in up to OHEM_BINS global atomics
+  const long long nb = (n_pix + 2047) / 2048;
+  const dim3 grid((unsigned)(nb < 1 ? 1 : (nb > 1024 ? 1024 : nb)));
+  SL_TRY(sl_launch("ohem_init_kernel", ohem_init_kernel, dim3(1), dim3(256), 0, s, ws));
+  for (int pass = 0; pass < OHEM_PASSES; ++pass) {
+    SL_TRY(sl_launch("ohem_hist_kernel", ohem_hist_kernel, grid, dim3(256), 0, s, prob, n_pix, pass, thresh, ws));
+    SL_TRY(sl_launch("ohem_select_kernel", ohem_select_kernel, dim3(1), dim3(OHEM_BINS), 0, s, pass, min_kept, thresh, ws, theta, counts));
+  }
+  return 0;
+}
+
+extern "C" int sl_ohem_mine(const float* prob, const int64_t* target, const float* theta, const long long* counts, long long n_pix, int ignore_index, int64_t* mined,
+                            sl_stream_t stream) {
+  SL_REQUIRE(n_pix > 0 && n_pix < (1LL << 31), "ohem_mine: %lld pixels; one call takes 1 to 2^31 - 1", n_pix);
+  SL_REQUIRE(prob && target && theta && counts && mined, "ohem_mine: null buffer");
+  return sl_launch("ohem_mine_kernel", ohem_mine_kernel, dim3(ce_blocks(n_pix)), dim3(256), 0, (hipStream_t)stream, prob, target, theta, counts, n_pix, ignore_index, mined);
 }
 
 extern "C" int sl_pseudo_label(const float* logits, int K2, int h, int w, int64_t* mask, int B, int H, int W, int n_base,

@@ -54,13 +54,36 @@ def dice_weight(v):
     return lam
 
 
+def ohem_thresh(v):
+    try:
+        th = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError('float expected (got %r)' % (v,))
+    if not 0.0 <= th <= 1.0:
+        raise argparse.ArgumentTypeError('the hard-pixel mining threshold must lie in (0, 1], or be 0 for off (got %r)' % (v,))
+    return th
+
+
+def ohem_min_kept(v):
+    try:
+        n = int(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError('integer expected (got %r)' % (v,))
+    if n < 1:
+        raise argparse.ArgumentTypeError('the number of pixels hard-pixel mining keeps at least must be >= 1 (got %r)' % (v,))
+    return n
+
+
 def log_loss_options(args):
-    """One line at start: the controls of the segmentation criterion (loss.get_loss reads the same fields); the Dice weight only where it is on."""
+    """One line at start: the controls of the segmentation criterion (loss.get_loss reads the same fields); the Dice weight and the mining controls only where they are on."""
     import logging
     w = class_weights(getattr(args, 'class_weights', ()) or ())
     lam = float(getattr(args, 'dice_weight', 0.0))
-    logging.getLogger('Segmentation').info('segmentation loss: class weights %s, label smoothing %g' + (', dice weight %g' if lam > 0.0 else ''),
-                                           ','.join('%g' % x for x in w) if w else 'none', float(getattr(args, 'label_smoothing', 0.0)), *((lam,) if lam > 0.0 else ()))
+    th = float(getattr(args, 'ohem_thresh', 0.0) or 0.0)
+    logging.getLogger('Segmentation').info('segmentation loss: class weights %s, label smoothing %g' + (', dice weight %g' if lam > 0.0 else '')
+                                           + (', hard-pixel mining: threshold %g, at least %d pixels per batch' if th > 0.0 else ''),
+                                           ','.join('%g' % x for x in w) if w else 'none', float(getattr(args, 'label_smoothing', 0.0)), *((lam,) if lam > 0.0 else ()),
+                                           *((th, int(getattr(args, 'ohem_min_kept', 100000))) if th > 0.0 else ()))
 
 
 # (flag, kwargs) -- common to both drivers
@@ -99,6 +122,10 @@ _COMMON = [
     ('--label-smoothing', dict(type=label_smoothing, default=0.0, help='label smoothing of the segmentation cross-entropy, in [0, 1]; default 0.')),
     ('--dice-weight', dict(type=dice_weight, default=0.0, help='weight of the multiclass soft Dice term added to the segmentation cross-entropy (main and auxiliary '
                                                                'head; class weights scale its per-class terms, ignored pixels are left out); default 0: cross-entropy only.')),
+    ('--ohem-thresh', dict(type=ohem_thresh, default=0.0, help='online hard-pixel mining (bootstrapped cross-entropy): only pixels whose probability of the true class '
+                                                               'is at most this threshold, in (0, 1], enter the segmentation loss of a head, but never fewer than '
+                                                               '--ohem-min-kept of them; default 0: off.')),
+    ('--ohem-min-kept', dict(type=ohem_min_kept, default=100000, help='pixels per GPU batch that hard-pixel mining keeps at least (the hardest ones); default 100000.')),
     ('--fp16', dict(action='store_true', default=False, help='mixed precision: bf16 MFMA with fp32 accumulate on MI355X '
                                                                 '(the reference uses fp16 autocast + GradScaler); default is exact-fp32 MFMA.')),
 ]

@@ -3,6 +3,7 @@ kernel pair (the H x W logits are never materialised).  Returns the same dict of
 import torch
 import torch.nn as nn
 
+from .. import ops
 from ..functional import UpsampleCEDiceFn, UpsampleCEFn
 
 
@@ -24,9 +25,17 @@ class OrthLoss(nn.Module):
     MulticlassHybridLoss): seg_loss = cross-entropy + dice_weight * Dice, with multiclass soft Dice on the softmax of the upsampled logits (sum over classes, each
     scaled by `weight` where given; mean over samples; `dice_smooth` in numerator and denominator; pixels with the ignore label enter neither term), for the main and
     the auxiliary head alike; the dict gains 'dice_loss', the main head's unscaled Dice term.  Both are plain floats: no buffer, no state_dict key.  dice_weight == 0
-    is the code path without it."""
+    is the code path without it.
 
-    def __init__(self, ignore_index=255, reduction='mean', weight=None, label_smoothing=0.0, dice_weight=0.0, dice_smooth=1.0):
+    `ohem_thresh` (None or 0: off) turns on online hard-pixel mining (bootstrapped cross-entropy): per call and per head, only the valid pixels whose softmax probability
+    of the true class is at most max(ohem_thresh, the ohem_min_kept-th smallest such probability) count -- every pixel at or below the threshold, and at least
+    ohem_min_kept pixels (all of them when fewer are valid).  The head's criterion, cross-entropy and Dice term alike, is evaluated on the mined label map (the target
+    with the dropped pixels set to ignore_index, in a new buffer: `target` is never written) by the same kernels; the kept set is a constant for the gradient.  Each
+    head mines by its own probabilities; `weight` and `label_smoothing` do not enter them.  ohem_min_kept counts pixels per call (per GPU batch).  The dict gains
+    'ohem_frac', the kept fraction of the main head's valid pixels (a device scalar; no read-back, so the step stays capturable).  Both are plain Python values: no
+    buffer, no state_dict key.  Off is the code path without it."""
+
+    def __init__(self, ignore_index=255, reduction='mean', weight=None, label_smoothing=0.0, dice_weight=0.0, dice_smooth=1.0, ohem_thresh=None, ohem_min_kept=100000):
         super().__init__()
         if reduction != 'mean':
             raise ValueError('segland_amd OrthLoss implements reduction="mean" (what the reference uses)')
@@ -38,6 +47,14 @@ class OrthLoss(nn.Module):
             raise ValueError('OrthLoss: dice_weight %r is not a finite value >= 0' % (dice_weight,))
         if not 0.0 < dice_smooth < float('inf'):
             raise ValueError('OrthLoss: dice_smooth %r is not a finite value > 0' % (dice_smooth,))
+        if ohem_thresh is not None:
+            ohem_thresh = float(ohem_thresh)
+            if ohem_thresh == 0.0:
+                ohem_thresh = None
+            elif not 0.0 < ohem_thresh <= 1.0:
+                raise ValueError('OrthLoss: ohem_thresh %r outside (0, 1] (None or 0: off)' % (ohem_thresh,))
+        if isinstance(ohem_min_kept, bool) or int(ohem_min_kept) != ohem_min_kept or int(ohem_min_kept) < 1:
+            raise ValueError('OrthLoss: ohem_min_kept %r is not an integer >= 1' % (ohem_min_kept,))
         if weight is not None:
             weight = torch.as_tensor(weight, dtype=torch.float32).detach().clone().contiguous()
             if weight.dim() != 1 or weight.numel() == 0:
@@ -47,6 +64,8 @@ class OrthLoss(nn.Module):
         self.label_smoothing = label_smoothing
         self.dice_weight = dice_weight
         self.dice_smooth = dice_smooth
+        self.ohem_thresh = ohem_thresh
+        self.ohem_min_kept = int(ohem_min_kept)
         self.w = 10.0
         self._triu = {}
 
@@ -62,20 +81,31 @@ class OrthLoss(nn.Module):
             idx = self._triu[key] = torch.triu_indices(proto_sim.shape[0], proto_sim.shape[1], offset=1).to(proto_sim.device)
         return torch.abs(proto_sim[idx[0], idx[1]]).mean()
 
+    def mine(self, preds, target):
+        """(mined label map of one head, the kept fraction of its valid pixels) of online hard-pixel mining; nothing here is differentiated"""
+        with torch.no_grad():
+            mined, _, counts = ops.ohem_mine(preds.detach().float().contiguous(), target, self.ignore_index, self.ohem_thresh, self.ohem_min_kept)
+            frac = (counts[2].double() / counts[0].clamp(min=1).double()).float()
+        return mined, frac
+
     def head_loss(self, preds, target):
-        """(segmentation loss of one head, its unscaled Dice term or None): with dice_weight > 0 one forward pass and one backward launch for both terms"""
+        """(segmentation loss of one head, its unscaled Dice term or None, its kept fraction or None): with dice_weight > 0 one forward pass and one backward launch for
+        both terms; with mining on, both run on the head's mined label map"""
         if self.weight is not None and self.weight.numel() != preds.shape[1]:
             raise ValueError('OrthLoss: %d class weights for %d logit channels' % (self.weight.numel(), preds.shape[1]))
+        frac = None
+        if self.ohem_thresh is not None:
+            target, frac = self.mine(preds, target)
         if self.dice_weight > 0.0:
             ce, dice = UpsampleCEDiceFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.weight, self.label_smoothing, self.dice_smooth)
-            return torch.add(ce, dice, alpha=self.dice_weight), dice
-        return UpsampleCEFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.weight, self.label_smoothing), None
+            return torch.add(ce, dice, alpha=self.dice_weight), dice, frac
+        return UpsampleCEFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.weight, self.label_smoothing), None, frac
 
     def seg_loss(self, preds, target):
         return self.head_loss(preds, target)[0]
 
     def forward(self, preds, target, is_ft=False, proto_sim=None, aux_preds=None):
-        seg_loss, dice = self.head_loss(preds, target)
+        seg_loss, dice, frac = self.head_loss(preds, target)
         orth_loss = self.get_orth_loss(proto_sim, is_ft=is_ft)
         if aux_preds is not None:
             aux_loss = self.seg_loss(aux_preds, target)
@@ -86,4 +116,6 @@ class OrthLoss(nn.Module):
             out = {'total_loss': torch.add(seg_loss, orth_loss, alpha=self.w), 'seg_loss': seg_loss, 'orth_loss': orth_loss}
         if dice is not None:
             out['dice_loss'] = dice
+        if frac is not None:
+            out['ohem_frac'] = frac
         return out

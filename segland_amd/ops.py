@@ -1112,6 +1112,41 @@ def upsample_ce_dice_bwd(logits, target, out, coef, gscale, ignore_index, weight
     return dl
 
 
+def ohem_prob(logits, target, ignore_index):
+    """float [B, H, W]: the softmax probability of the true class of every valid pixel of the upsampled logits (the forward kernel's arithmetic), 2.0 elsewhere"""
+    B, K, h, w = logits.shape
+    H, W = target.shape[1:]
+    prob = _f32((B, H, W), logits.device)
+    tok = PROFILER.begin_bytes('upsample_ohem_prob', logits.numel() * 4 + target.numel() * target.element_size() + prob.numel() * 4)
+    check(_lib.lib().sl_upsample_ohem_prob(_p(logits), _p(target), B, K, h, w, H, W, ignore_index, _p(prob), _s()), 'upsample_ohem_prob')
+    PROFILER.end_bytes(tok)
+    return prob
+
+
+def ohem_threshold(prob, thresh, min_kept):
+    """(theta float [1], counts int64 [3] = (valid pixels n, k = min(min_kept, n), kept pixels)): theta = max(thresh, k-th smallest probability), exact, on the device"""
+    L = _lib.lib()
+    B, H, W = prob.shape
+    nbytes = L.sl_ohem_workspace(B, H, W)
+    ws = workspace(nbytes, prob.device)
+    theta = _f32((1,), prob.device)
+    counts = torch.empty(3, dtype=torch.int64, device=prob.device)
+    check(L.sl_ohem_threshold(_p(prob), prob.numel(), thresh, min_kept, _p(ws), nbytes, _p(theta), _p(counts), _s()), 'ohem_threshold')
+    return theta, counts
+
+
+def ohem_mine(logits, target, ignore_index, thresh, min_kept):
+    """Online hard-pixel mining of one head (include/segland_hip.h): (mined int64 [B, H, W], theta float [1], counts int64 [3] = (n, k, n_kept)).  `mined` is `target`
+    on the valid pixels whose probability of the true class is at most theta = max(thresh, k-th smallest probability), k = min(min_kept, n), and `ignore_index`
+    elsewhere; `target` is not written.  No read-back: the call is capturable."""
+    target = target.contiguous()
+    prob = ohem_prob(logits, target, ignore_index)
+    theta, counts = ohem_threshold(prob, thresh, min_kept)
+    mined = torch.empty_like(target)
+    check(_lib.lib().sl_ohem_mine(_p(prob), _p(target), _p(theta), _p(counts), prob.numel(), ignore_index, _p(mined), _s()), 'ohem_mine')
+    return mined, theta, counts
+
+
 def pseudo_label_(logits, mask, n_base):
     """In place on `mask` (int64 [B,H,W]); logits [B,K2,h,w] float, K2 <= 33."""
     B, K2, h, w = logits.shape

@@ -2,7 +2,8 @@
 """HIP-event times of the fused upsample + loss kernels in their three forms -- plain cross-entropy, weighted (class weights + label smoothing 0.1), hybrid (cross-entropy
 + soft Dice, without and with weights) -- at the bench shape (B 16, K 8, 64 x 64 -> 512 x 512) and at the widest head (K 33): forward with its finalize launch, tiled
 backward, gather backward (sl_debug_ce_tiled(0)).  The variants are timed in interleaved rounds in one process, 50 launches each after a warm-up; the table gives the
-median over the rounds in us and the ratio to the plain pair.  For an A/B of two builds run it alternately with SEGLAND_LIB_PATH at each library."""
+median over the rounds in us and the ratio to the plain pair.  Below it the three passes of online hard-pixel mining (probability, selection, mined map) and their sum through
+ops.ohem_mine, in the same interleaved rounds, with the spread of the rounds.  For an A/B of two builds run it alternately with SEGLAND_LIB_PATH at each library."""
 import os
 import statistics
 import sys
@@ -50,3 +51,24 @@ for K in (8, 33):
     for name, _, _ in variants:
         med = [statistics.median(t) for t in times[name]]
         print('%-16s | ' % name + '  '.join('%7.1f x%4.2f' % (v, v / b0) for v, b0 in zip(med, base)))
+    # the three passes of online hard-pixel mining in front of those kernels, on logits that are mostly right (+6 at the label of the nearest pixel: the selection then
+    # works where the probabilities crowd, just below 1) and on the random ones above; thresh 0.7; min_kept 100000 (the default of the drivers: the threshold decides) and
+    # 3500000 (nine tenths of the valid pixels: min_kept decides, q lies in the crowd)
+    cell = torch.randint(0, K, (B, h, h), device='cuda')
+    blocky = cell.repeat_interleave(H // h, 1).repeat_interleave(H // h, 2).contiguous(); blocky[:, :40] = 255
+    right = (logits + 6.0 * torch.nn.functional.one_hot(cell, K).permute(0, 3, 1, 2)).contiguous()
+    for what, lg, target, min_kept in (('random logits', logits, target, 100000), ('mostly right', right, blocky, 100000), ('mostly right', right, blocky, 3500000)):
+        prob = ops.ohem_prob(lg, target, 255)
+        theta, counts = ops.ohem_threshold(prob, 0.7, min_kept)
+        mined = torch.empty_like(target)
+        passes = [('probability', lambda: ops.ohem_prob(lg, target, 255)), ('selection', lambda: ops.ohem_threshold(prob, 0.7, min_kept)),
+                  ('mined map', lambda: _lib.lib().sl_ohem_mine(prob.data_ptr(), target.data_ptr(), theta.data_ptr(), counts.data_ptr(), prob.numel(), 255, mined.data_ptr(), ops._s())),
+                  ('all three', lambda: ops.ohem_mine(lg, target, 255, 0.7, min_kept))]
+        rounds = {name: [] for name, _ in passes}
+        for _ in range(ROUNDS):
+            for name, fn in passes:
+                rounds[name].append(timeit(fn))
+        n, k, kept = counts.tolist()
+        print('mining, %s (n %d, k %d, kept %d, theta %.6f) | ' % (what, n, k, kept, float(theta)) + '  '.join(
+            '%s %.1f (%.1f .. %.1f) x%.2f' % (name, statistics.median(t), min(t), max(t), statistics.median(t) / base[0]) for name, t in rounds.items())
+            + '   (us: median (min .. max) of the rounds; x = ratio to the plain fwd+finalize)')
