@@ -420,7 +420,7 @@ int sl_pop_decompose_bwd(int dtype, const void* dg, const void* feats, const flo
 /* ------------------------------------------------------------------------------------------------ loss
  * loss/criterion.py:51-52: F.interpolate(bilinear, align_corners=True) to the label size fused with
  * CrossEntropyLoss(ignore_index, mean); the H x W logits are never written.
- * sl_upsample_ce_fwd/bwd, sl_pseudo_label, sl_upsample_argmax, sl_upsample_logits and sl_tta_fuse take 1 <= K <= 33 logit channels (background + 32 prototypes); more is SL_EINVAL
+ * sl_upsample_ce_fwd/bwd, sl_pseudo_label, sl_upsample_argmax, sl_upsample_logits, sl_tta_fuse and sl_slide_fuse take 1 <= K <= 33 logit channels (background + 32 prototypes); more is SL_EINVAL
  * and the message names the limit.  The backward's tiled kernel cuts more than 16 channels into slices of at most 16 (its LDS holds one slice of the tile's footprint). */
 int sl_upsample_ce_rows(int B, int H, int W);
 /* partial[blk][2] = (sum of pixel losses, number of valid pixels) */
@@ -509,6 +509,30 @@ int sl_upsample_logits(const float* logits, int B, int K, int h, int w, int H, i
 #define SL_TTA_MAX_VIEWS 16
 typedef struct SlTtaViews { int n; const float* logits[SL_TTA_MAX_VIEWS]; int h[SL_TTA_MAX_VIEWS], w[SL_TTA_MAX_VIEWS], flip[SL_TTA_MAX_VIEWS]; float weight[SL_TTA_MAX_VIEWS]; } SlTtaViews;
 int sl_tta_fuse(const SlTtaViews* views, int B, int K, int H, int W, int mode, uint8_t* labels, float* fused, sl_stream_t stream);
+/* Sliding-window inference: the overlapping windows of one scene batch fused on the scene grid in ONE gather kernel; the per-window maps, the [B][K][H][W] accumulator
+ * and the weight map of the torch composition (F.interpolate, softmax, weighted +=, /, argmax) are never written.
+ * The window grid along one side of length L with crop c and stride s, 1 <= s <= c: window side c' = min(c, L), n = max(L - c' + s - 1, 0) / s + 1 windows (integer
+ * division), window i at offset min(i * s, L - c'): the last window is shifted back to end at the border; a side shorter than the crop gives one window of the scene's own
+ * side.  sl_slide_windows returns n, or -1 unless L, c >= 1 and 1 <= s <= c (a stride above the crop as given leaves holes).
+ * A scene batch [B][3][H][W] gives B * ny * nx windows, all ch x cw = min(crop_h, H) x min(crop_w, W); window (b, iy, ix) has index (b * ny + iy) * nx + ix.
+ * logits: float [B * ny * nx][K][h][w], contiguous, on the device, any h, w >= 1.  For output pixel (b, Y, X):
+ *   the covering windows are those with y1 <= Y < y1 + ch and x1 <= X < x1 + cw, taken in ascending (iy, ix) order, ix innermost;
+ *   u = the bilinear (align_corners=True, h x w -> ch x cw) value of the window's logits at the local pixel (y, x) = (Y - y1, X - x1);
+ *   t = softmax_k(u) (mode SL_SLIDE_PROB: max subtracted, expf, one division per channel) or u (mode SL_SLIDE_LOGIT);
+ *   wt = 1 (blend SL_SLIDE_UNIFORM) or min(y + 1, ch - y) * min(x + 1, cw - x) (blend SL_SLIDE_TENT: an exact integer in float);
+ *   acc[k] = wt * t[k] for the first covering window, acc[k] + wt * t[k] after; den the same sum of wt;  fused[k] = acc[k] / den;  labels = argmax_k fused[k], first
+ *   maximum wins.
+ * labels: uint8 [B][H][W] (required); fused: float [B][K][H][W] or NULL (then one byte per pixel is all that is written).  The descriptor is a host struct read during
+ * the call and handed to the kernel by value (no device table, no copy, no synchronisation: capturable).  B, H, W, h, w, crop_h, crop_w >= 1, 1 <= stride <= crop per side,
+ * 1 <= K <= 33, mode and blend 0 or 1, B * ny * nx within an int, no NULL but fused, else SL_EINVAL before any launch with the value in the message.  No LDS, no
+ * atomics: two runs give the same bits. */
+#define SL_SLIDE_PROB 0
+#define SL_SLIDE_LOGIT 1
+#define SL_SLIDE_UNIFORM 0
+#define SL_SLIDE_TENT 1
+typedef struct SlSlide { int B, K, H, W, h, w, crop_h, crop_w, stride_h, stride_w, mode, blend; } SlSlide;
+int sl_slide_windows(int L, int crop, int stride);
+int sl_slide_fuse(const SlSlide* s, const float* logits, uint8_t* labels, float* fused, sl_stream_t stream);
 /* fusemat.py:35-52: argmax over classes of the mean of n_models probability maps [K][hw] (mats_dev: device array of n_models float pointers),
  * summed in list order like the reference's in-place `mats[idx] += prob` */
 int sl_fuse_argmax(const void* mats_dev, int n_models, int K, long long hw, uint8_t* labels, sl_stream_t stream);

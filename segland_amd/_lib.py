@@ -67,6 +67,14 @@ class SlTtaViews(C.Structure):
                 ('flip', C.c_int * SL_TTA_MAX_VIEWS), ('weight', C.c_float * SL_TTA_MAX_VIEWS)]
 
 
+SL_SLIDE_PROB, SL_SLIDE_LOGIT = 0, 1
+SL_SLIDE_UNIFORM, SL_SLIDE_TENT = 0, 1
+
+
+class SlSlide(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('B', 'K', 'H', 'W', 'h', 'w', 'crop_h', 'crop_w', 'stride_h', 'stride_w', 'mode', 'blend')]
+
+
 _CTYPE = {
     'int': C.c_int, 'long long': C.c_longlong, 'float': C.c_float, 'size_t': C.c_size_t, 'sl_stream_t': C.c_void_p,
 }

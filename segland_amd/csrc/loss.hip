@@ -5,7 +5,7 @@
 
 namespace {
 
-constexpr int KMAXC = 33;  // max logit channels (background + 32 prototypes) of sl_upsample_ce_* / sl_pseudo_label / sl_upsample_argmax / sl_upsample_logits / sl_tta_fuse: the ONE limit of this file
+constexpr int KMAXC = 33;  // max logit channels (background + 32 prototypes) of sl_upsample_ce_* / sl_pseudo_label / sl_upsample_argmax / sl_upsample_logits / sl_tta_fuse / sl_slide_fuse: the ONE limit of this file
 constexpr int KNC = 16;    // up to KNC channels run on the <KNC> instantiations and the one-pass tiled backward (device code as before the wide head); more on <KMAXC> and the
                            // channel-sliced tiled backward.  KW below is the per-thread array width of an instantiation.
 
@@ -759,6 +759,79 @@ __global__ __launch_bounds__(256) void tta_fuse_kernel(TtaViews a, int B, int K,
   }
 }
 
+// Sliding-window inference (sl_slide_fuse): the overlapping windows of ONE scene batch fused on the scene grid.  The grid of one side of length L with crop c and stride s
+// (1 <= s <= c): window side c' = min(c, L), n = max(L - c' + s - 1, 0) / s + 1 windows, window i at min(i * s, L - c') -- the last one is shifted back to end at the border.
+__host__ inline long long slide_count(long long L, long long c, long long s) {
+  const long long cs = c < L ? c : L, span = L - cs + s - 1;
+  return (span > 0 ? span : 0) / s + 1;
+}
+// SlideGeom is SlSlide as the kernel takes it by value: c = the window side (the crop clamped to the scene), s = the stride, n = the window count per side, and the
+// align_corners scales from h x w to the window, worked out once on the host.
+struct SlideGeom { int B, K, H, W, h, w, ch, cw, sh, sw, ny, nx, mode, blend; float sy, sx; };
+
+// The windows of one side that cover coordinate P, lo..hi: the offsets are monotone, so the covering set is a contiguous index range and no window is searched for.  Every
+// window but the last sits at i * s, and (n - 2) * s < L - c <= (n - 1) * s.  hi, the last offset <= P: the shifted last window from P = L - c on, else P / s (<= n - 2).
+// lo, the first offset > P - c: with t = P - c + 1 > 0 the first i with i * s >= t, which is at most n - 1 because t <= L - c.
+__device__ __forceinline__ void slide_cover(int P, int L, int c, int s, int n, int& lo, int& hi) {
+  hi = P >= L - c ? n - 1 : P / s;
+  const int t = P - c + 1;
+  lo = t > 0 ? min((t + s - 1) / s, n - 1) : 0;
+}
+
+// One thread per output pixel; its covering windows in ascending (iy, ix) order, ix innermost, each sampled with pixel_logits at the local pixel (the window's logits are
+// "image" (b * ny + iy) * nx + ix of an h x w -> ch x cw upsampling).  mode 0: t = softmax_k (max subtracted, expf, one division per channel, the arithmetic of
+// tta_fuse_kernel), mode 1: t = the interpolated logits.  blend 0: wt = 1, blend 1: wt = min(y + 1, ch - y) * min(x + 1, cw - x) on the local pixel (an exact integer in
+// float).  acc_k = wt * t_k for the first window, acc_k + wt * t_k after, den the same sum of wt; fused_k = acc_k / den; the label is the first maximum (torch.argmax).
+// v and acc stay in registers: no LDS, no atomics.  fused may be null: then one byte per pixel is all that is written.
+template <int KW>
+__global__ __launch_bounds__(256) void slide_fuse_kernel(SlideGeom a, const float* __restrict__ lg, uint8_t* __restrict__ labels, float* __restrict__ fused) {
+  UpGeom g; g.B = a.B * a.ny * a.nx; g.K = a.K; g.h = a.h; g.w = a.w; g.H = a.ch; g.W = a.cw; g.sy = a.sy; g.sx = a.sx;
+  const int K = a.K;
+  const long long total = (long long)a.B * a.H * a.W;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += gridDim.x * 256LL) {
+    const int X = (int)(i % a.W); const long long r = i / a.W;
+    const int Y = (int)(r % a.H), b = (int)(r / a.H);
+    int iy0, iy1, ix0, ix1;
+    slide_cover(Y, a.H, a.ch, a.sh, a.ny, iy0, iy1);
+    slide_cover(X, a.W, a.cw, a.sw, a.nx, ix0, ix1);
+    float acc[KW];
+    float den = 0.f;
+    bool first = true;
+    for (int iy = iy0; iy <= iy1; ++iy) {
+      const int y = Y - min(iy * a.sh, a.H - a.ch);
+      for (int ix = ix0; ix <= ix1; ++ix) {
+        const int x = X - min(ix * a.sw, a.W - a.cw);
+        float v[KW];
+        pixel_logits<KW>(g, lg, (b * a.ny + iy) * a.nx + ix, y, x, v);
+        if (a.mode == SL_SLIDE_PROB) {
+          float m = v[0];
+#pragma unroll
+          for (int k = 1; k < KW; ++k) if (k < K) m = fmaxf(m, v[k]);
+          float s = 0.f;
+#pragma unroll
+          for (int k = 0; k < KW; ++k) if (k < K) { v[k] = expf(v[k] - m); s += v[k]; }
+#pragma unroll
+          for (int k = 0; k < KW; ++k) if (k < K) v[k] = v[k] / s;
+        }
+        const float wt = a.blend == SL_SLIDE_TENT ? (float)min(y + 1, a.ch - y) * (float)min(x + 1, a.cw - x) : 1.f;
+#pragma unroll
+        for (int k = 0; k < KW; ++k) acc[k] = first ? wt * v[k] : acc[k] + wt * v[k];
+        den = first ? wt : den + wt;
+        first = false;
+      }
+    }
+    const size_t plane = (size_t)a.H * a.W;
+    int best = 0; float bv = 0.f;
+#pragma unroll
+    for (int k = 0; k < KW; ++k) if (k < K) {
+      const float fk = acc[k] / den;
+      if (k == 0 || fk > bv) { bv = fk; best = k; }                                     // first maximum wins (torch.argmax)
+      if (fused) fused[((size_t)b * K + k) * plane + (size_t)Y * a.W + X] = fk;
+    }
+    labels[i] = (uint8_t)best;
+  }
+}
+
 // fusemat.py:35-52: mats[idx] += prob in list order, argmax(mat / n, axis=0): float sum in the same order, first maximum wins (np.argmax)
 __global__ void fuse_argmax_kernel(const float* const* __restrict__ mats, int n, int K, long long hw, uint8_t* __restrict__ out) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < hw; i += (long long)gridDim.x * blockDim.x) {
@@ -1201,6 +1274,33 @@ extern "C" int sl_tta_fuse(const SlTtaViews* views, int B, int K, int H, int W, 
   SL_REQUIRE(a.wsum <= 3.402823466e38f, "tta_fuse: the weights sum to %g", (double)a.wsum);
   return sl_launch("tta_fuse_kernel", K <= KNC ? tta_fuse_kernel<KNC> : tta_fuse_kernel<KMAXC>, dim3(ce_blocks((long long)B * H * W)), dim3(256), 0, (hipStream_t)stream, a, B, K, H, W, mode,
                    labels, fused);
+}
+
+extern "C" int sl_slide_windows(int L, int crop, int stride) {
+  if (L < 1 || crop < 1 || stride < 1 || stride > crop) return -1;
+  return (int)slide_count(L, crop, stride);                 // at most L
+}
+
+extern "C" int sl_slide_fuse(const SlSlide* s, const float* logits, uint8_t* labels, float* fused, sl_stream_t stream) {
+  SL_REQUIRE(s, "slide_fuse: null descriptor");
+  SL_REQUIRE(logits, "slide_fuse: null logits");
+  SL_REQUIRE(labels, "slide_fuse: null labels");
+  SL_REQUIRE(s->B >= 1 && s->H >= 1 && s->W >= 1 && s->h >= 1 && s->w >= 1 && s->crop_h >= 1 && s->crop_w >= 1,
+             "slide_fuse: B %d, H %d, W %d, h %d, w %d, crop_h %d, crop_w %d must all be at least 1", s->B, s->H, s->W, s->h, s->w, s->crop_h, s->crop_w);
+  SL_REQUIRE(s->stride_h >= 1 && s->stride_h <= s->crop_h && s->stride_w >= 1 && s->stride_w <= s->crop_w,
+             "slide_fuse: stride_h %d, stride_w %d outside [1, crop] (crop_h %d, crop_w %d): a stride above the crop leaves holes", s->stride_h, s->stride_w, s->crop_h, s->crop_w);
+  SL_REQUIRE(s->K >= 1 && s->K <= KMAXC, "slide_fuse: %d logit channels; this build holds at most %d", s->K, KMAXC);
+  SL_REQUIRE(s->mode == SL_SLIDE_PROB || s->mode == SL_SLIDE_LOGIT, "slide_fuse: mode %d is neither 0 (mean of the softmax probabilities) nor 1 (mean of the upsampled logits)", s->mode);
+  SL_REQUIRE(s->blend == SL_SLIDE_UNIFORM || s->blend == SL_SLIDE_TENT, "slide_fuse: blend %d is neither 0 (uniform weights) nor 1 (tent weights)", s->blend);
+  const long long ny = slide_count(s->H, s->crop_h, s->stride_h), nx = slide_count(s->W, s->crop_w, s->stride_w);       // each at most its side
+  SL_REQUIRE((double)s->B * (double)ny * (double)nx <= 2147483647.0, "slide_fuse: %.0f windows (B %d x %lld x %lld) do not fit an int", (double)s->B * (double)ny * (double)nx, s->B, ny, nx);
+  SlideGeom a;
+  a.B = s->B; a.K = s->K; a.H = s->H; a.W = s->W; a.h = s->h; a.w = s->w; a.mode = s->mode; a.blend = s->blend;
+  a.ch = s->crop_h < s->H ? s->crop_h : s->H; a.cw = s->crop_w < s->W ? s->crop_w : s->W;
+  a.sh = s->stride_h; a.sw = s->stride_w; a.ny = (int)ny; a.nx = (int)nx;
+  a.sy = ac1_scale(a.h, a.ch); a.sx = ac1_scale(a.w, a.cw);
+  return sl_launch("slide_fuse_kernel", s->K <= KNC ? slide_fuse_kernel<KNC> : slide_fuse_kernel<KMAXC>, dim3(ce_blocks((long long)s->B * s->H * s->W)), dim3(256), 0, (hipStream_t)stream, a,
+                   logits, labels, fused);
 }
 
 extern "C" int sl_fuse_argmax(const void* mats_dev, int n_models, int K, long long hw, uint8_t* labels, sl_stream_t stream) {

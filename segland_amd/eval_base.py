@@ -12,6 +12,12 @@ rasterio and is row f-2 of SURVEY.md section 8.
 --tta-scales 0.75,1.0,1.25 --tta-flip True [--tta-mode prob|logit]: test-time augmentation (segland_amd/tta.py).  One forward per view (scale, plain / mirrored), then
 ONE kernel upsamples every view to the same grid, takes the softmax (prob) or not (logit), un-flips, averages and takes the argmax; with --save-prob the .mat holds the
 fused map.  With the default flags (one scale of 1.0, no flip) the loop body is the single-view code above and the fusion kernel is never called.
+
+--slide-crop 512,512 [--slide-stride 341,341] [--slide-blend uniform|tent] [--slide-mode prob|logit] [--slide-batch N]: sliding-window inference (segland_amd/slide.py).
+The tile is cut into overlapping windows of the crop (the size the model was trained at), the windows are forwarded N at a time, then ONE kernel upsamples every window's
+logits to the crop, takes the softmax (prob) or not (logit), weights them (uniform, or a tent that favours a window's centre), averages the windows over each pixel and takes
+the argmax; with --save-prob the .mat holds the fused map.  Without --slide-crop (the default) no call changes and the fusion kernel is never called.  Sliding together with
+--tta-*, or with a scoring grid that is not the image grid (eval_ft's long-side square of a non-square tile), is refused.
 """
 import argparse
 import os
@@ -23,6 +29,7 @@ import torch
 from . import dataset as dataset_pkg
 from . import networks
 from . import ops
+from . import slide
 from . import tta
 from .drivers import batch_to_device, checkpoint_or_none, compute_dtype, resolve, str2bool
 from .engine import Engine
@@ -55,6 +62,12 @@ def get_parser():
     p.add_argument('--tta-flip', type=str2bool, default='False', help='test-time augmentation: add the horizontally mirrored view of every scale')
     p.add_argument('--tta-mode', type=str, default='prob', choices=['prob', 'logit'], help='the views are fused as softmax probabilities or as upsampled logits (one kernel, '
                    'segland_amd.tta); with --save-prob the .mat holds the fused map')
+    p.add_argument('--slide-crop', type=str, default='', help="sliding-window inference: window size 'H,W' (multiples of 32), e.g. '512,512' for 1024x1024 tiles; empty = off")
+    p.add_argument('--slide-stride', type=str, default='', help="sliding-window inference: window stride 'H,W', each within [1, crop]; default: two thirds of the crop, rounded down")
+    p.add_argument('--slide-blend', type=str, default='uniform', choices=['uniform', 'tent'], help='weights of the overlapping windows: all one, or min(y+1, ch-y) * min(x+1, cw-x)')
+    p.add_argument('--slide-mode', type=str, default='prob', choices=['prob', 'logit'], help='the windows are fused as softmax probabilities or as upsampled logits (one kernel, '
+                   'segland_amd.slide); with --save-prob the .mat holds the fused map')
+    p.add_argument('--slide-batch', type=int, default=0, help='sliding-window inference: windows per forward (0 = all windows of a batch at once)')
     p.add_argument('--allow-random-init', action='store_true', help='evaluate random weights when --restore-from does not exist')
     return p
 
@@ -156,6 +169,12 @@ def main(argv=None, ft=False):
             from datetime import datetime
             logger = my_utils.get_logger('', args.save_path, datetime.now().strftime('%Y_%m_%d_%H_%M_%S'))
         args.base_size = tuple(map(int, args.base_size.split(',')))
+        tta_scales = tta.parse_scales(args.tta_scales)
+        tta_on, tta_sizes = tta.is_on(tta_scales, args.tta_flip), None
+        slide_crop, slide_stride = slide.driver_geometry(args.slide_crop, args.slide_stride)
+        slide_on, slide_logged = slide.is_on(slide_crop), False
+        if slide_on and tta_on:
+            raise ValueError('--slide-crop together with --tta-scales / --tta-flip: windows of augmented views are not implemented; use one of the two')
         ds = resolve(dataset_pkg, args.dataset)
         testset = ds.GFSSegVal(args.data_dir, args.val_list, args.fold, base_size=args.base_size, resize_label=False, use_novel=True, use_base=True)
         test_loader, test_sampler = engine.get_test_loader(testset)
@@ -169,8 +188,6 @@ def main(argv=None, ft=False):
         seg_model = model_cls(n_base=args.base_classes, backbone=args.backbone, dilated=(args.os != 32), os=args.os,
                               n_novel=args.novel_classes, is_ft=ft, compute_dtype=compute_dtype(args))
         model = engine.data_parallel(seg_model.to(engine.device))
-        tta_scales = tta.parse_scales(args.tta_scales)
-        tta_on, tta_sizes = tta.is_on(tta_scales, args.tta_flip), None
         results = {}
         for seed in map(int, args.random_seed.split(',')):
             path = (args.restore_from[:-4] + '_%d.pth' % seed) if ft else args.restore_from       # eval_ft.py:154
@@ -182,6 +199,26 @@ def main(argv=None, ft=False):
                 # ready tensors (synthetic) or raw uint8 tiles + draws prepared on the GPU (oem / synthetic_raw: Engine installs raw_collate)
                 image, label = batch_to_device(batch, testset, engine.device)
                 ids = batch[2]
+                if slide_on:
+                    # the windows of this batch fused on the image grid, which must be the grid the single-view code scores at; with --save-prob the .mat holds the fused map
+                    size = tuple(image.shape[-2:])
+                    label_p, score_size = label_grid(label, args.ignore_label, pad_to_longside=ft) if label is not None else (None, size)
+                    if tuple(score_size) != size:
+                        raise ValueError('--slide-crop: the prediction is scored at %dx%d but the image is %dx%d; windows are cut from the image, so the two grids must be the same'
+                                         % (score_size[0], score_size[1], size[0], size[1]))
+                    if not slide_logged and engine.is_main:
+                        (ch, ys), (cw, xs) = slide.window_grid(size[0], slide_crop[0], slide_stride[0]), slide.window_grid(size[1], slide_crop[1], slide_stride[1])
+                        (logger.info if logger else print)('sliding-window inference: %d windows per tile (%d x %d of %dx%d on %dx%d), crop %dx%d, stride %dx%d, blend %s, mode %s' % (
+                            len(ys) * len(xs), len(ys), len(xs), ch, cw, size[0], size[1], slide_crop[0], slide_crop[1], slide_stride[0], slide_stride[1], args.slide_blend,
+                            args.slide_mode))
+                        slide_logged = True
+                    pred, fused = slide.predict(model, image, slide_crop, slide_stride, mode=args.slide_mode, blend=args.slide_blend,
+                                                want_map=bool(args.save_prob and args.save_path), batch=args.slide_batch)
+                    if label is not None:
+                        cm += ops.confusion_matrix(pred, label_p.contiguous(), args.num_classes, args.ignore_label)
+                    if fused is not None:
+                        dump_maps(fused, size, pred, ids, osp.join(args.save_path, 'prob_%d' % seed), data_dir=getattr(args, 'data_dir', None))
+                    continue
                 if tta_on:
                     # the views of this batch fused on the grid the single-view code scores at; with --save-prob the .mat holds the fused map
                     label_p, size = label_grid(label, args.ignore_label, pad_to_longside=ft) if label is not None else (None, tuple(image.shape[-2:]))

@@ -1213,6 +1213,38 @@ def tta_fuse(views, size, mode='prob', want_map=False):
     return labels, fused
 
 
+SLIDE_MODES = {'prob': _lib.SL_SLIDE_PROB, 'logit': _lib.SL_SLIDE_LOGIT}
+SLIDE_BLENDS = {'uniform': _lib.SL_SLIDE_UNIFORM, 'tent': _lib.SL_SLIDE_TENT}
+
+
+def slide_fuse(logits, B, size, crop, stride, mode='prob', blend='uniform', want_map=False):
+    """Sliding-window inference fused on the scene grid in one kernel (sl_slide_fuse): logits = float [B*ny*nx,K,h,w], the window logits of B scenes of `size` cut with
+    `crop` and `stride` (segland_amd/slide.py: window (b, iy, ix) at index (b*ny + iy)*nx + ix).  Per pixel the covering windows are upsampled (align_corners=True, to the
+    window size), softmaxed (mode 'prob') or not ('logit'), weighted (blend 'uniform': 1, 'tent': min(y+1, ch-y) * min(x+1, cw-x)), averaged and argmaxed.  Returns
+    (labels uint8 [B,H,W], the fused map float [B,K,H,W] if want_map else None); without the map one byte per pixel is written."""
+    if mode not in SLIDE_MODES:
+        raise RuntimeError("slide_fuse: mode %r is neither 'prob' nor 'logit'" % (mode,))
+    if blend not in SLIDE_BLENDS:
+        raise RuntimeError("slide_fuse: blend %r is neither 'uniform' nor 'tent'" % (blend,))
+    if logits.dtype != torch.float32 or logits.dim() != 4:
+        raise RuntimeError('slide_fuse: the window logits must be float32 [B*ny*nx,K,h,w] (%s %s)' % (logits.dtype, tuple(logits.shape)))
+    B, (H, W), (ch, cw), (sh, sw) = int(B), map(int, size), map(int, crop), map(int, stride)
+    L = _lib.lib()
+    ny, nx = L.sl_slide_windows(H, ch, sh), L.sl_slide_windows(W, cw, sw)
+    if B < 1 or ny < 0 or nx < 0:
+        raise RuntimeError('slide_fuse: B %d, scene %dx%d, crop %dx%d, stride %dx%d: sides and batch must be at least 1 and the stride within [1, crop]' % (B, H, W, ch, cw, sh, sw))
+    if logits.shape[0] != B * ny * nx:
+        raise RuntimeError('slide_fuse: %d window logits; B %d scenes of %dx%d with crop %dx%d and stride %dx%d make %d x %d x %d = %d windows' % (
+            logits.shape[0], B, H, W, ch, cw, sh, sw, B, ny, nx, B * ny * nx))
+    K, h, w = logits.shape[1:]
+    s = _lib.SlSlide(B, K, H, W, h, w, ch, cw, sh, sw, SLIDE_MODES[mode], SLIDE_BLENDS[blend])
+    ptr = _p(logits)
+    labels = torch.empty((B, H, W), dtype=torch.uint8, device=logits.device)
+    fused = _f32((B, K, H, W), logits.device) if want_map else None
+    check(L.sl_slide_fuse(C.byref(s), ptr, _p(labels), _p(fused), _s()), 'slide_fuse')
+    return labels, fused
+
+
 def iou_hist(pred_u8, target, K, ignore_index):
     hist = torch.zeros((3, K), dtype=torch.int64, device=target.device)
     check(_lib.lib().sl_iou_hist(_p(pred_u8), _p(target), target.numel(), K, ignore_index, _p(hist), _s()), 'iou_hist')
