@@ -84,6 +84,44 @@ __device__ __forceinline__ void pixel_logits(const UpGeom& g, const float* __res
   }
 }
 
+// The fuse core of tta_fuse_kernel and slide_fuse_kernel: what one term (a view, a window) contributes to a pixel and how the pixel is finished.  Each kernel keeps its
+// own loop over the terms and its own weights; the float operations and their order are these, once.
+// softmax over v[0..K) in place: max subtracted, expf, one division per channel
+template <int KW>
+__device__ __forceinline__ void fuse_softmax(int K, float* v) {
+  float m = v[0];
+#pragma unroll
+  for (int k = 1; k < KW; ++k) if (k < K) m = fmaxf(m, v[k]);
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < KW; ++k) if (k < K) { v[k] = expf(v[k] - m); s += v[k]; }
+#pragma unroll
+  for (int k = 0; k < KW; ++k) if (k < K) v[k] = v[k] / s;
+}
+// acc_k = wt * v_k for the first term (acc is not zeroed), acc_k + wt * v_k after; a branch, not a select per channel: `first` is the same in every lane in both kernels
+template <int KW>
+__device__ __forceinline__ void fuse_accumulate(bool first, float wt, const float* v, float* acc) {
+  if (first) {
+#pragma unroll
+    for (int k = 0; k < KW; ++k) acc[k] = wt * v[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < KW; ++k) acc[k] = acc[k] + wt * v[k];
+  }
+}
+// fused_k = acc_k / den, stored at pixel `pix` of plane bk + k of the fused map unless that is null; returns the label, the first maximum (torch.argmax)
+template <int KW>
+__device__ __forceinline__ uint8_t fuse_finish(int K, const float* acc, float den, float* __restrict__ fused, size_t bk, size_t plane, size_t pix) {
+  int best = 0; float bv = 0.f;
+#pragma unroll
+  for (int k = 0; k < KW; ++k) if (k < K) {
+    const float fk = acc[k] / den;
+    if (k == 0 || fk > bv) { bv = fk; best = k; }
+    if (fused) fused[(bk + k) * plane + pix] = fk;
+  }
+  return (uint8_t)best;
+}
+
 // Cross-entropy term of one valid pixel of label t from its logits v, for both forward kernels: ce_max gives m = max_k v_k and vt = v_t, the kernel sums
 // s = sum_k exp(v_k - m) (the hybrid one keeps the exponentials: with that loop in here too its K = 33 instantiation lost a wave per SIMD), ce_pixel gives the
 // numerator and denominator (plain: -logp_t and 1; WT: the weighted form above).
@@ -718,9 +756,8 @@ __global__ void upsample_logits_kernel(UpGeom g, const float* __restrict__ lg, f
 struct TtaViews { int n; float wsum; const float* lg[SL_TTA_MAX_VIEWS]; int h[SL_TTA_MAX_VIEWS], w[SL_TTA_MAX_VIEWS], flip[SL_TTA_MAX_VIEWS]; float sy[SL_TTA_MAX_VIEWS], sx[SL_TTA_MAX_VIEWS], wt[SL_TTA_MAX_VIEWS]; };
 
 // One thread per output pixel, the views in a runtime loop (the view index is wave-uniform: the view's parameters are scalar loads from the kernel arguments).  A flipped view is read
-// at the mirrored pixel -- torch.flip(F.interpolate(l, (H, W), align_corners=True)) is an index remap of pixel_logits, not a second interpolation.  mode 0: t = softmax_k
-// (max subtracted, expf, one division per channel), mode 1: t = the interpolated logits.  fused_k = (sum_i wt_i t_ik) / wsum with term 0 starting the sum; the label is
-// the first maximum of fused (torch.argmax).  fused may be null: then one byte per pixel is all that is written.
+// at the mirrored pixel -- torch.flip(F.interpolate(l, (H, W), align_corners=True)) is an index remap of pixel_logits, not a second interpolation.  mode 0: t = fuse_softmax
+// of the sample, mode 1: t = the sample.  fused_k = (sum_i wt_i t_ik) / wsum (fuse_accumulate, fuse_finish).  fused may be null: then one byte per pixel is all that is written.
 template <int KW>
 __global__ __launch_bounds__(256) void tta_fuse_kernel(TtaViews a, int B, int K, int H, int W, int mode, uint8_t* __restrict__ labels, float* __restrict__ fused) {
   const long long total = (long long)B * H * W;
@@ -734,28 +771,11 @@ __global__ __launch_bounds__(256) void tta_fuse_kernel(TtaViews a, int B, int K,
       const float wt = a.wt[n];
       float v[KW];
       pixel_logits<KW>(g, a.lg[n], b, (f & 2) ? H - 1 - Y : Y, (f & 1) ? W - 1 - X : X, v);
-      if (mode == 0) {
-        float m = v[0];
-#pragma unroll
-        for (int k = 1; k < KW; ++k) if (k < K) m = fmaxf(m, v[k]);
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < KW; ++k) if (k < K) { v[k] = expf(v[k] - m); s += v[k]; }
-#pragma unroll
-        for (int k = 0; k < KW; ++k) if (k < K) v[k] = v[k] / s;
-      }
-#pragma unroll
-      for (int k = 0; k < KW; ++k) acc[k] = n == 0 ? wt * v[k] : acc[k] + wt * v[k];
+      if (mode == 0) fuse_softmax<KW>(K, v);
+      fuse_accumulate<KW>(n == 0, wt, v, acc);
     }
     const size_t plane = (size_t)H * W;
-    int best = 0; float bv = 0.f;
-#pragma unroll
-    for (int k = 0; k < KW; ++k) if (k < K) {
-      const float fk = acc[k] / a.wsum;
-      if (k == 0 || fk > bv) { bv = fk; best = k; }                                     // first maximum wins (torch.argmax)
-      if (fused) fused[((size_t)b * K + k) * plane + (size_t)Y * W + X] = fk;
-    }
-    labels[i] = (uint8_t)best;
+    labels[i] = fuse_finish<KW>(K, acc, a.wsum, fused, (size_t)b * K, plane, (size_t)Y * W + X);
   }
 }
 
@@ -779,10 +799,9 @@ __device__ __forceinline__ void slide_cover(int P, int L, int c, int s, int n, i
 }
 
 // One thread per output pixel; its covering windows in ascending (iy, ix) order, ix innermost, each sampled with pixel_logits at the local pixel (the window's logits are
-// "image" (b * ny + iy) * nx + ix of an h x w -> ch x cw upsampling).  mode 0: t = softmax_k (max subtracted, expf, one division per channel, the arithmetic of
-// tta_fuse_kernel), mode 1: t = the interpolated logits.  blend 0: wt = 1, blend 1: wt = min(y + 1, ch - y) * min(x + 1, cw - x) on the local pixel (an exact integer in
-// float).  acc_k = wt * t_k for the first window, acc_k + wt * t_k after, den the same sum of wt; fused_k = acc_k / den; the label is the first maximum (torch.argmax).
-// v and acc stay in registers: no LDS, no atomics.  fused may be null: then one byte per pixel is all that is written.
+// "image" (b * ny + iy) * nx + ix of an h x w -> ch x cw upsampling).  mode 0: t = fuse_softmax of the sample, mode 1: t = the interpolated logits.  blend 0: wt = 1,
+// blend 1: wt = min(y + 1, ch - y) * min(x + 1, cw - x) on the local pixel (an exact integer in float).  den is the sum of wt taken as fuse_accumulate takes acc;
+// fused_k = acc_k / den (fuse_finish).  v and acc stay in registers: no LDS, no atomics.  fused may be null: then one byte per pixel is all that is written.
 template <int KW>
 __global__ __launch_bounds__(256) void slide_fuse_kernel(SlideGeom a, const float* __restrict__ lg, uint8_t* __restrict__ labels, float* __restrict__ fused) {
   UpGeom g; g.B = a.B * a.ny * a.nx; g.K = a.K; g.h = a.h; g.w = a.w; g.H = a.ch; g.W = a.cw; g.sy = a.sy; g.sx = a.sx;
@@ -803,32 +822,15 @@ __global__ __launch_bounds__(256) void slide_fuse_kernel(SlideGeom a, const floa
         const int x = X - min(ix * a.sw, a.W - a.cw);
         float v[KW];
         pixel_logits<KW>(g, lg, (b * a.ny + iy) * a.nx + ix, y, x, v);
-        if (a.mode == SL_SLIDE_PROB) {
-          float m = v[0];
-#pragma unroll
-          for (int k = 1; k < KW; ++k) if (k < K) m = fmaxf(m, v[k]);
-          float s = 0.f;
-#pragma unroll
-          for (int k = 0; k < KW; ++k) if (k < K) { v[k] = expf(v[k] - m); s += v[k]; }
-#pragma unroll
-          for (int k = 0; k < KW; ++k) if (k < K) v[k] = v[k] / s;
-        }
+        if (a.mode == SL_SLIDE_PROB) fuse_softmax<KW>(K, v);
         const float wt = a.blend == SL_SLIDE_TENT ? (float)min(y + 1, a.ch - y) * (float)min(x + 1, a.cw - x) : 1.f;
-#pragma unroll
-        for (int k = 0; k < KW; ++k) acc[k] = first ? wt * v[k] : acc[k] + wt * v[k];
+        fuse_accumulate<KW>(first, wt, v, acc);
         den = first ? wt : den + wt;
         first = false;
       }
     }
     const size_t plane = (size_t)a.H * a.W;
-    int best = 0; float bv = 0.f;
-#pragma unroll
-    for (int k = 0; k < KW; ++k) if (k < K) {
-      const float fk = acc[k] / den;
-      if (k == 0 || fk > bv) { bv = fk; best = k; }                                     // first maximum wins (torch.argmax)
-      if (fused) fused[((size_t)b * K + k) * plane + (size_t)Y * a.W + X] = fk;
-    }
-    labels[i] = (uint8_t)best;
+    labels[i] = fuse_finish<KW>(K, acc, den, fused, (size_t)b * K, plane, (size_t)Y * a.W + X);
   }
 }
 

@@ -4,20 +4,18 @@
     python -m segland_amd.eval_base --model pspnet_pop --backbone resnet50 --dataset synthetic --restore-from best.pth --save-path out
     python -m segland_amd.eval_ft   ... --random-seed 123,234 --restore-from novel.pth      # loads novel_<seed>.pth per seed
 
-Per batch: logits (eval-mode forward, folded BN) -> upsample(align_corners=True) + argmax in ONE kernel (the H x W logits of
-eval_base.py:168 are never written) -> confusion-matrix kernel on the label grid; mIoU over base / novel / all classes from the
-accumulated matrix exactly as eval_base.py:193-199.  The unlabeled-test branch (GeoTIFF + .mat dumps, eval_base.py:178-191) needs
-rasterio and is row f-2 of SURVEY.md section 8.
-
---tta-scales 0.75,1.0,1.25 --tta-flip True [--tta-mode prob|logit]: test-time augmentation (segland_amd/tta.py).  One forward per view (scale, plain / mirrored), then
-ONE kernel upsamples every view to the same grid, takes the softmax (prob) or not (logit), un-flips, averages and takes the argmax; with --save-prob the .mat holds the
-fused map.  With the default flags (one scale of 1.0, no flip) the loop body is the single-view code above and the fusion kernel is never called.
-
+One loop serves every mode.  Per batch: the grid the prediction is scored at (label_grid: the label's own, or eval_ft's long-side square; the image's for unlabeled test
+tiles, eval_base.py:178-191, where the prediction and the dump are the product) -> predict -> confusion-matrix kernel -> with --save-prob the .mat / TIFF / PNG dump
+(dump_maps); mIoU over base / novel / all classes from the accumulated matrix exactly as eval_base.py:193-199.  select_predictor picks `predict` once from the flags:
+plain (the default): logits (eval-mode forward, folded BN) -> upsample(align_corners=True) + argmax in ONE kernel (the H x W logits of eval_base.py:168 are never
+  written); with --save-prob the .mat holds the logits upsampled to the tile's own size.  Neither fusion kernel is called.
+--tta-scales 0.75,1.0,1.25 --tta-flip True [--tta-mode prob|logit]: test-time augmentation (segland_amd/tta.py).  One forward per view (scale, plain / mirrored), then ONE
+  kernel upsamples every view to the scoring grid, takes the softmax (prob) or not (logit), un-flips, averages and takes the argmax.
 --slide-crop 512,512 [--slide-stride 341,341] [--slide-blend uniform|tent] [--slide-mode prob|logit] [--slide-batch N]: sliding-window inference (segland_amd/slide.py).
-The tile is cut into overlapping windows of the crop (the size the model was trained at), the windows are forwarded N at a time, then ONE kernel upsamples every window's
-logits to the crop, takes the softmax (prob) or not (logit), weights them (uniform, or a tent that favours a window's centre), averages the windows over each pixel and takes
-the argmax; with --save-prob the .mat holds the fused map.  Without --slide-crop (the default) no call changes and the fusion kernel is never called.  Sliding together with
---tta-*, or with a scoring grid that is not the image grid (eval_ft's long-side square of a non-square tile), is refused.
+  The tile is cut into overlapping windows of the crop (the size the model was trained at), forwarded N at a time, then ONE kernel upsamples every window's logits to the
+  crop, takes the softmax or not, weights them (uniform, or a tent that favours a window's centre), averages the windows over each pixel and takes the argmax.  Refused:
+  sliding together with --tta-*, or with a scoring grid that is not the image grid (eval_ft's long-side square of a non-square tile).
+The two fusing modes put their fused map, cut to the tile, into the .mat and state their geometry in one log line at the first batch.
 """
 import argparse
 import os
@@ -85,7 +83,6 @@ def label_grid(label, ignore_label, pad_to_longside=False):
 
 def confusion_of_batch(logits, label, num_classes, ignore_label, pad_to_longside=False):
     """eval_base.py:166-177 (eval_ft.py:166-181 with pad_to_longside): prediction at the label grid and its confusion counts."""
-    from . import ops
     label, size = label_grid(label, ignore_label, pad_to_longside)
     pred = ops.upsample_argmax(logits.float().contiguous(), size)
     return pred, ops.confusion_matrix(pred, label.contiguous(), num_classes, ignore_label)
@@ -120,7 +117,6 @@ def dump_probabilities(logits, size, pred, ids, out_dir, data_dir=None):
     """eval_base.py:168,180-190: per tile `<id>.mat` = {'outputs': [1,K,H,W] logits upsampled with align_corners=True} (the input of fusemat.py), `<id>.tif` = the
     argmax as a colormapped single-band TIFF next to the .mat directory (write_prediction_tiff: the reference's GeoTIFF when rasterio and the source tile
     <data_dir>/image/<id>.tif exist), and `<id>.png`, the same as a palette image."""
-    from . import ops
     dump_maps(ops.upsample_logits(logits.float().contiguous(), tuple(size)), size, pred, ids, out_dir, data_dir)
 
 
@@ -159,6 +155,44 @@ def miou_from_confusion(cm, n_base):
     return iou, float(np.nanmean(iou[:n_base + 1])), float(np.nanmean(iou[n_base + 1:])) if len(iou) > n_base + 1 else float('nan'), float(np.nanmean(iou))
 
 
+def predict_plain(model, image, size, map_size=None):
+    """The single-view predictor (eval_base.py:166-168): the forward under no_grad, then upsampling + argmax to `size` in one kernel and, when a map is wanted, the logits
+    upsampled to `map_size`.  -> (labels uint8 [B,H,W], float [B,K,map_size] or None)."""
+    with torch.no_grad():
+        logits = model(image).float().contiguous()
+    return ops.upsample_argmax(logits, size), ops.upsample_logits(logits, tuple(map_size)) if map_size is not None else None
+
+
+def select_predictor(args):
+    """(predict, describe) for the parsed flags: plain, test-time augmentation or sliding windows; the latter two together are refused.  Every predict has the call shape of
+    predict_plain; the fusing ones give their map on `size` itself and read `map_size` as 'a map is wanted'.  describe(image size, size) is the log line of the first
+    batch, None for the plain predictor."""
+    scales = tta.parse_scales(args.tta_scales)
+    crop, stride = slide.driver_geometry(args.slide_crop, args.slide_stride)
+    if slide.is_on(crop) and tta.is_on(scales, args.tta_flip):
+        raise ValueError('--slide-crop together with --tta-scales / --tta-flip: windows of augmented views are not implemented; use one of the two')
+    if slide.is_on(crop):
+        def predict(model, image, size, map_size=None):
+            if tuple(size) != tuple(image.shape[-2:]):
+                raise ValueError('--slide-crop: the prediction is scored at %dx%d but the image is %dx%d; windows are cut from the image, so the two grids must be the same'
+                                 % (tuple(size) + tuple(image.shape[-2:])))
+            return slide.predict(model, image, crop, stride, mode=args.slide_mode, blend=args.slide_blend, want_map=map_size is not None, batch=args.slide_batch)
+        def describe(hw, size):
+            (ch, ys), (cw, xs) = slide.window_grid(hw[0], crop[0], stride[0]), slide.window_grid(hw[1], crop[1], stride[1])
+            return 'sliding-window inference: %d windows per tile (%d x %d of %dx%d on %dx%d), crop %dx%d, stride %dx%d, blend %s, mode %s' % (
+                len(ys) * len(xs), len(ys), len(xs), ch, cw, hw[0], hw[1], crop[0], crop[1], stride[0], stride[1], args.slide_blend, args.slide_mode)
+        return predict, describe
+    if tta.is_on(scales, args.tta_flip):
+        def predict(model, image, size, map_size=None):
+            return tta.predict(model, image, size, scales=scales, flip=args.tta_flip, mode=args.tta_mode, want_map=map_size is not None)
+        def describe(hw, size):
+            sizes = tta.view_sizes(hw[0], hw[1], scales)
+            return 'test-time augmentation: %d views per tile (images %s%s), mode %s, fused at %dx%d' % (
+                len(sizes) * (2 if args.tta_flip else 1), ', '.join('%dx%d' % s for s in sizes), '; each plain and mirrored' if args.tta_flip else '', args.tta_mode, size[0], size[1])
+        return predict, describe
+    return predict_plain, None
+
+
 def main(argv=None, ft=False):
     parser = get_parser()
     with Engine(custom_parser=parser, argv=argv) as engine:
@@ -169,12 +203,7 @@ def main(argv=None, ft=False):
             from datetime import datetime
             logger = my_utils.get_logger('', args.save_path, datetime.now().strftime('%Y_%m_%d_%H_%M_%S'))
         args.base_size = tuple(map(int, args.base_size.split(',')))
-        tta_scales = tta.parse_scales(args.tta_scales)
-        tta_on, tta_sizes = tta.is_on(tta_scales, args.tta_flip), None
-        slide_crop, slide_stride = slide.driver_geometry(args.slide_crop, args.slide_stride)
-        slide_on, slide_logged = slide.is_on(slide_crop), False
-        if slide_on and tta_on:
-            raise ValueError('--slide-crop together with --tta-scales / --tta-flip: windows of augmented views are not implemented; use one of the two')
+        predict, describe = select_predictor(args)
         ds = resolve(dataset_pkg, args.dataset)
         testset = ds.GFSSegVal(args.data_dir, args.val_list, args.fold, base_size=args.base_size, resize_label=False, use_novel=True, use_base=True)
         test_loader, test_sampler = engine.get_test_loader(testset)
@@ -195,57 +224,23 @@ def main(argv=None, ft=False):
                 my_utils.load_model(model, path)
             model.eval()
             cm = torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=engine.device)
+            dump_dir = osp.join(args.save_path, 'prob_%d' % seed) if args.save_prob and args.save_path else None
             for batch in test_loader:
                 # ready tensors (synthetic) or raw uint8 tiles + draws prepared on the GPU (oem / synthetic_raw: Engine installs raw_collate)
                 image, label = batch_to_device(batch, testset, engine.device)
-                ids = batch[2]
-                if slide_on:
-                    # the windows of this batch fused on the image grid, which must be the grid the single-view code scores at; with --save-prob the .mat holds the fused map
-                    size = tuple(image.shape[-2:])
-                    label_p, score_size = label_grid(label, args.ignore_label, pad_to_longside=ft) if label is not None else (None, size)
-                    if tuple(score_size) != size:
-                        raise ValueError('--slide-crop: the prediction is scored at %dx%d but the image is %dx%d; windows are cut from the image, so the two grids must be the same'
-                                         % (score_size[0], score_size[1], size[0], size[1]))
-                    if not slide_logged and engine.is_main:
-                        (ch, ys), (cw, xs) = slide.window_grid(size[0], slide_crop[0], slide_stride[0]), slide.window_grid(size[1], slide_crop[1], slide_stride[1])
-                        (logger.info if logger else print)('sliding-window inference: %d windows per tile (%d x %d of %dx%d on %dx%d), crop %dx%d, stride %dx%d, blend %s, mode %s' % (
-                            len(ys) * len(xs), len(ys), len(xs), ch, cw, size[0], size[1], slide_crop[0], slide_crop[1], slide_stride[0], slide_stride[1], args.slide_blend,
-                            args.slide_mode))
-                        slide_logged = True
-                    pred, fused = slide.predict(model, image, slide_crop, slide_stride, mode=args.slide_mode, blend=args.slide_blend,
-                                                want_map=bool(args.save_prob and args.save_path), batch=args.slide_batch)
-                    if label is not None:
-                        cm += ops.confusion_matrix(pred, label_p.contiguous(), args.num_classes, args.ignore_label)
-                    if fused is not None:
-                        dump_maps(fused, size, pred, ids, osp.join(args.save_path, 'prob_%d' % seed), data_dir=getattr(args, 'data_dir', None))
-                    continue
-                if tta_on:
-                    # the views of this batch fused on the grid the single-view code scores at; with --save-prob the .mat holds the fused map
-                    label_p, size = label_grid(label, args.ignore_label, pad_to_longside=ft) if label is not None else (None, tuple(image.shape[-2:]))
-                    if tta_sizes is None and engine.is_main:
-                        tta_sizes = tta.view_sizes(image.shape[-2], image.shape[-1], tta_scales)
-                        (logger.info if logger else print)('test-time augmentation: %d views per tile (images %s%s), mode %s, fused at %dx%d' % (
-                            len(tta_sizes) * (2 if args.tta_flip else 1), ', '.join('%dx%d' % s for s in tta_sizes), '; each plain and mirrored' if args.tta_flip else '',
-                            args.tta_mode, size[0], size[1]))
-                    pred, fused = tta.predict(model, image, size, scales=tta_scales, flip=args.tta_flip, mode=args.tta_mode, want_map=bool(args.save_prob and args.save_path))
-                    if label is not None:
-                        cm += ops.confusion_matrix(pred, label_p.contiguous(), args.num_classes, args.ignore_label)
-                    if fused is not None:
-                        dump_maps(fused, tuple(image.shape[-2:]) if label is None else tuple(label.shape[-2:]), pred, ids, osp.join(args.save_path, 'prob_%d' % seed),
-                                  data_dir=getattr(args, 'data_dir', None))
-                    continue
-                with torch.no_grad():
-                    logits = model(image)
-                if label is None:
-                    # unlabeled test tiles (eval_base.py:178-191): nothing to score -- the prediction and the probability dump are the product
-                    size = tuple(image.shape[-2:])
-                    pred = ops.upsample_argmax(logits.float().contiguous(), size)
-                else:
-                    size = tuple(label.shape[-2:])
-                    pred, cmb = confusion_of_batch(logits, label, args.num_classes, args.ignore_label, pad_to_longside=ft)
-                    cm += cmb
-                if args.save_prob and args.save_path:
-                    dump_probabilities(logits, size, pred, ids, osp.join(args.save_path, 'prob_%d' % seed), data_dir=getattr(args, 'data_dir', None))
+                # the tile's own size and the grid the prediction is scored at; unlabeled test tiles (eval_base.py:178-191): nothing to score, prediction and dump are the product
+                tile = tuple((image if label is None else label).shape[-2:])
+                label_p, size = (None, tile) if label is None else label_grid(label, args.ignore_label, pad_to_longside=ft)
+                # The map is asked for at the tile's size.  predict_plain upsamples the logits to exactly that (the reference's .mat), although its labels are taken at `size`;
+                # the fusing predictors give their map on `size` and dump_maps cuts it to the tile.  The two coincide unless eval_ft pads a non-square tile; each is kept as it is.
+                pred, out_map = predict(model, image, size, tile if dump_dir else None)
+                if describe is not None and engine.is_main:
+                    (logger.info if logger else print)(describe(tuple(image.shape[-2:]), size))
+                    describe = None
+                if label is not None:
+                    cm += ops.confusion_matrix(pred, label_p.contiguous(), args.num_classes, args.ignore_label)
+                if out_map is not None:
+                    dump_maps(out_map, tile, pred, batch[2], dump_dir, data_dir=getattr(args, 'data_dir', None))
             if engine.distributed:
                 cm = engine.all_reduce_tensor(cm, norm=False)
             cmn = cm.cpu().numpy().astype(np.float64)

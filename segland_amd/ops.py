@@ -1185,14 +1185,26 @@ def fuse_argmax(mats):
 
 
 TTA_MODES = {'prob': 0, 'logit': 1}
+SLIDE_MODES = {'prob': _lib.SL_SLIDE_PROB, 'logit': _lib.SL_SLIDE_LOGIT}
+SLIDE_BLENDS = {'uniform': _lib.SL_SLIDE_UNIFORM, 'tent': _lib.SL_SLIDE_TENT}
+
+
+# what tta_fuse and slide_fuse share: the code of a mode / blend argument (or the op's refusal), and the outputs the kernel fills
+def _fuse_choice(op, what, table, value):
+    if value not in table:
+        raise RuntimeError('%s: %s %r is neither %s' % (op, what, value, ' nor '.join(map(repr, table))))
+    return table[value]
+
+
+def _fuse_outputs(B, K, H, W, device, want_map):
+    return torch.empty((B, H, W), dtype=torch.uint8, device=device), _f32((B, K, H, W), device) if want_map else None
 
 
 def tta_fuse(views, size, mode='prob', want_map=False):
     """Test-time augmentation fused on the label grid in one kernel (sl_tta_fuse): views = [(logits [B,K,h_i,w_i] float, flip, weight), ...] of one model, flip bit 0 =
     the view saw the image flipped horizontally, bit 1 vertically.  mode 'prob': weighted mean of the views' softmax of the upsampled (align_corners=True) logits, 'logit':
     of the upsampled logits.  Returns (labels uint8 [B,H,W], the fused map float [B,K,H,W] if want_map else None); without the map one byte per pixel is written."""
-    if mode not in TTA_MODES:
-        raise RuntimeError("tta_fuse: mode %r is neither 'prob' nor 'logit'" % (mode,))
+    mode = _fuse_choice('tta_fuse', 'mode', TTA_MODES, mode)
     views = list(views)
     if not 1 <= len(views) <= _lib.SL_TTA_MAX_VIEWS:
         raise RuntimeError('tta_fuse: %d views; one call fuses 1 to %d' % (len(views), _lib.SL_TTA_MAX_VIEWS))
@@ -1207,14 +1219,9 @@ def tta_fuse(views, size, mode='prob', want_map=False):
             raise RuntimeError('tta_fuse: every view must be float32 [%d,%d,h,w] on %s (view %d: %s %s on %s)' % (B, K, first.device, i, lg.dtype, tuple(lg.shape), lg.device))
         v.logits[i], v.h[i], v.w[i], v.flip[i], v.weight[i] = _p(lg), lg.shape[2], lg.shape[3], int(flip), float(weight)
     H, W = int(size[0]), int(size[1])
-    labels = torch.empty((B, H, W), dtype=torch.uint8, device=first.device)
-    fused = _f32((B, K, H, W), first.device) if want_map else None
-    check(_lib.lib().sl_tta_fuse(C.byref(v), B, K, H, W, TTA_MODES[mode], _p(labels), _p(fused), _s()), 'tta_fuse')
+    labels, fused = _fuse_outputs(B, K, H, W, first.device, want_map)
+    check(_lib.lib().sl_tta_fuse(C.byref(v), B, K, H, W, mode, _p(labels), _p(fused), _s()), 'tta_fuse')
     return labels, fused
-
-
-SLIDE_MODES = {'prob': _lib.SL_SLIDE_PROB, 'logit': _lib.SL_SLIDE_LOGIT}
-SLIDE_BLENDS = {'uniform': _lib.SL_SLIDE_UNIFORM, 'tent': _lib.SL_SLIDE_TENT}
 
 
 def slide_fuse(logits, B, size, crop, stride, mode='prob', blend='uniform', want_map=False):
@@ -1222,10 +1229,7 @@ def slide_fuse(logits, B, size, crop, stride, mode='prob', blend='uniform', want
     `crop` and `stride` (segland_amd/slide.py: window (b, iy, ix) at index (b*ny + iy)*nx + ix).  Per pixel the covering windows are upsampled (align_corners=True, to the
     window size), softmaxed (mode 'prob') or not ('logit'), weighted (blend 'uniform': 1, 'tent': min(y+1, ch-y) * min(x+1, cw-x)), averaged and argmaxed.  Returns
     (labels uint8 [B,H,W], the fused map float [B,K,H,W] if want_map else None); without the map one byte per pixel is written."""
-    if mode not in SLIDE_MODES:
-        raise RuntimeError("slide_fuse: mode %r is neither 'prob' nor 'logit'" % (mode,))
-    if blend not in SLIDE_BLENDS:
-        raise RuntimeError("slide_fuse: blend %r is neither 'uniform' nor 'tent'" % (blend,))
+    mode, blend = _fuse_choice('slide_fuse', 'mode', SLIDE_MODES, mode), _fuse_choice('slide_fuse', 'blend', SLIDE_BLENDS, blend)
     if logits.dtype != torch.float32 or logits.dim() != 4:
         raise RuntimeError('slide_fuse: the window logits must be float32 [B*ny*nx,K,h,w] (%s %s)' % (logits.dtype, tuple(logits.shape)))
     B, (H, W), (ch, cw), (sh, sw) = int(B), map(int, size), map(int, crop), map(int, stride)
@@ -1237,11 +1241,9 @@ def slide_fuse(logits, B, size, crop, stride, mode='prob', blend='uniform', want
         raise RuntimeError('slide_fuse: %d window logits; B %d scenes of %dx%d with crop %dx%d and stride %dx%d make %d x %d x %d = %d windows' % (
             logits.shape[0], B, H, W, ch, cw, sh, sw, B, ny, nx, B * ny * nx))
     K, h, w = logits.shape[1:]
-    s = _lib.SlSlide(B, K, H, W, h, w, ch, cw, sh, sw, SLIDE_MODES[mode], SLIDE_BLENDS[blend])
-    ptr = _p(logits)
-    labels = torch.empty((B, H, W), dtype=torch.uint8, device=logits.device)
-    fused = _f32((B, K, H, W), logits.device) if want_map else None
-    check(L.sl_slide_fuse(C.byref(s), ptr, _p(labels), _p(fused), _s()), 'slide_fuse')
+    s = _lib.SlSlide(B, K, H, W, h, w, ch, cw, sh, sw, mode, blend)
+    labels, fused = _fuse_outputs(B, K, H, W, logits.device, want_map)
+    check(L.sl_slide_fuse(C.byref(s), _p(logits), _p(labels), _p(fused), _s()), 'slide_fuse')
     return labels, fused
 
 

@@ -58,7 +58,3 @@ def fuse(logits, B, size, crop, stride, mode='prob', blend='uniform'):
     fused = acc / den
     return fused.argmax(dim=1), fused
 
-
-def top2_margin(fused):
-    top = fused.topk(min(2, fused.shape[1]), dim=1).values
-    return top[:, 0] - top[:, 1] if top.shape[1] == 2 else torch.full_like(top[:, 0], float('inf'))

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import slide_reference as sr
+from eval_common import run_eval, top2_margin
 from oracle import formula as fm
 
 pytestmark = pytest.mark.gpu
@@ -53,7 +54,7 @@ def test_labels_vs_torch_reference(hip, name, mode, blend):
     labels, _ = kernel(name, mode, blend)
     assert labels.dtype == torch.uint8 and tuple(labels.shape) == (sr.BATCH,) + tuple(size)
     labels = labels.cpu().long()
-    keep = sr.top2_margin(ref_fused) >= 1e-5
+    keep = top2_margin(ref_fused) >= 1e-5
     out_share = 1.0 - float(keep.float().mean())
     differ = int((labels != ref_labels)[keep].sum())
     print('slide case %s mode %s blend %s: %d pixels, %.3f %% below the 1e-5 margin, %d labels differ outside it, %d anywhere' % (
@@ -84,7 +85,7 @@ def test_fused_map_vs_float64(hip, name, mode, blend):
     floor = 2e-6 * float(ref64.abs().max())
     print('slide case %s mode %s blend %s: kernel error %.3g, float32 torch error %.3g, floor %.3g' % (name, mode, blend, e_kernel, e_torch, floor))
     assert e_kernel <= max(4 * e_torch, floor)
-    assert int((labels.cpu().long() != labels64)[sr.top2_margin(ref64) >= 1e-5].sum()) == 0
+    assert int((labels.cpu().long() != labels64)[top2_margin(ref64) >= 1e-5].sum()) == 0
 
 
 @pytest.mark.parametrize('K', [8, 33])
@@ -201,7 +202,7 @@ def test_whole_path_vs_cpu_oracle(hip, blend):
     scale = float(ref_fused.abs().max())
     assert tuple(fused.shape) == tuple(ref_fused.shape) and tuple(pred.shape) == (2,) + size
     err = float((fused.cpu() - ref_fused).abs().max()) / scale
-    keep = sr.top2_margin(ref_fused) >= 4e-3 * scale
+    keep = top2_margin(ref_fused) >= 4e-3 * scale
     out_share = 1.0 - float(keep.float().mean())
     differ = int((pred.cpu().long() != ref_labels)[keep].sum())
     moved = float((ref_labels != whole_labels).float().mean())
@@ -211,18 +212,6 @@ def test_whole_path_vs_cpu_oracle(hip, blend):
     assert out_share <= 0.10
     assert differ == 0
     assert moved > 0.02                     # a property of the oracle alone: the windows matter, so ignoring them cannot pass the label gate
-
-
-EVAL_ARGS = ['--model', 'pspnet_pop', '--backbone', 'resnet50', '--dataset', 'synthetic', '--base-size', '128,128', '--restore-from', '/nonexistent', '--allow-random-init',
-             '--random-seed', '123']
-
-
-def run_eval(out, extra, ft=False):
-    from segland_amd import eval_base
-    torch.manual_seed(0)
-    res = eval_base.main(EVAL_ARGS + ['--save-path', str(out)] + extra, ft=ft)
-    assert 123 in res
-    return np.load(os.path.join(str(out), 'cmatrix_123.npy'))
 
 
 def test_eval_driver_with_sliding(hip, tmp_path):

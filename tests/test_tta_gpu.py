@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import tta_reference as tr
+from eval_common import run_eval, top2_margin
 from oracle import formula as fm
 
 pytestmark = pytest.mark.gpu
@@ -54,7 +55,7 @@ def test_labels_vs_torch_reference(hip, name, mode):
     labels, _ = kernel(name, mode)
     labels = labels.cpu().long()
     assert labels.shape == ref_labels.shape and labels.dtype == torch.int64
-    keep = tr.top2_margin(ref_fused) >= 1e-5
+    keep = top2_margin(ref_fused) >= 1e-5
     out_share = 1.0 - float(keep.float().mean())
     differ = int((labels != ref_labels)[keep].sum())
     print('tta case %s mode %s: %d pixels, %.3f %% below the 1e-5 margin, %d labels differ outside it, %d anywhere' % (
@@ -164,7 +165,7 @@ def test_whole_path_vs_cpu_oracle(hip):
     single_labels, _ = tr.fuse(views[:1], size, 'logit')
     scale = float(ref_fused.abs().max())
     err = float((fused.cpu() - ref_fused).abs().max()) / scale
-    keep = tr.top2_margin(ref_fused) >= 4e-3 * scale
+    keep = top2_margin(ref_fused) >= 4e-3 * scale
     out_share = 1.0 - float(keep.float().mean())
     differ = int((pred.cpu().long() != ref_labels)[keep].sum())
     moved = float((ref_labels != single_labels).float().mean())
@@ -175,18 +176,6 @@ def test_whole_path_vs_cpu_oracle(hip):
     assert out_share <= 0.10
     assert differ == 0
     assert moved > 0.02                     # a property of the oracle alone (11.6 % on the CPU): the extra views matter, so ignoring them cannot pass the label gate
-
-
-EVAL_ARGS = ['--model', 'pspnet_pop', '--backbone', 'resnet50', '--dataset', 'synthetic', '--base-size', '128,128', '--restore-from', '/nonexistent', '--allow-random-init',
-             '--random-seed', '123']
-
-
-def run_eval(out, extra, ft=False):
-    from segland_amd import eval_base
-    torch.manual_seed(0)
-    res = eval_base.main(EVAL_ARGS + ['--save-path', str(out)] + extra, ft=ft)
-    assert 123 in res
-    return np.load(os.path.join(str(out), 'cmatrix_123.npy'))
 
 
 def test_eval_driver_with_flip(hip, tmp_path):

@@ -38,7 +38,3 @@ def fuse(views, size, mode='prob'):
     fused = acc / wsum
     return fused.argmax(dim=1), fused
 
-
-def top2_margin(fused):
-    top = fused.topk(min(2, fused.shape[1]), dim=1).values
-    return top[:, 0] - top[:, 1] if top.shape[1] == 2 else torch.full_like(top[:, 0], float('inf'))

@@ -10,6 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import torch
 import slide_reference as sr
+from eval_common import top2_margin
 from segland_amd import ops
 p = argparse.ArgumentParser()
 p.add_argument('--classes', type=int, default=12); p.add_argument('--size', type=int, default=1024); p.add_argument('--crop', type=int, default=512)
@@ -38,7 +39,7 @@ _, map64 = torch_composition(logits.double())
 lab_k, map_k = VERSIONS[1][1]()
 lab_n, none = VERSIONS[2][1]()
 e_k, e_t, floor = float((map_k.double() - map64).abs().max()), float((map_t.double() - map64).abs().max()), 2e-6 * float(map64.abs().max())
-keep = sr.top2_margin(map_t) >= 1e-5
+keep = top2_margin(map_t) >= 1e-5
 differ = int((lab_k.long() != lab_t)[keep].sum())
 print('B=%d K=%d scene %dx%d, crop %dx%d, stride %d (offsets %s: %d windows), window logits %dx%d, mode %s, blend %s' % (
     B, K, H, W, ch, cw, a.stride, ','.join(map(str, ys)), N, a.logits, a.logits, a.mode, a.blend))
