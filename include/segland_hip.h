@@ -464,6 +464,35 @@ int sl_upsample_ce_dice_finalize(const float* partial, const float* class_weight
 int sl_upsample_ce_dice_bwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing,
                             const float* loss3, const float* coef, const float* gscale, int B, int K, int h, int w, int H, int W,
                             int ignore_index, float* dlogits, sl_stream_t stream);
+/* Focal modulation (Lin et al., (1 - p_t)^gamma * CE) of the cross-entropy term of the criteria above.  For a valid pixel (label t != ignore_index, 0 <= t < K):
+ *   v = the bilinear (align_corners=True) logits of the pixel,  m = max_k v_k,  e_k = exp(v_k - m),  s = sum_k e_k in index order,  p_k = e_k / s;
+ *   u = (sum_{k != t} e_k) / s, the sum in index order, skipping t: 1 - p_t without the cancellation of 1 - e_t / s; exactly 0 when every other exponential underflows;
+ *   mod = u^gamma (0 where u == 0);
+ *   num0, den = the pixel's cross-entropy numerator and denominator as above (plain: -log p_t, 1;  weighted / smoothed: -sum_k c_k log p_k, w_t);
+ *   pixel numerator = mod * num0, pixel denominator = den (the mean is over the same weight sum as the cross-entropy's);  loss = sum num / sum den.
+ * Label smoothing is modulated as a whole (mod multiplies the smoothed numerator); the class weights are the focal "alpha".  Gradient of a pixel's numerator, with
+ * ceform_k the cross-entropy form (p_k C_t - c_k, or p_k - [k == t]):
+ *   d / d v_k = mod * ceform_k + beta * (p_k - [k == t]),   beta = gamma * num0 * (mod / u) * p_t   (beta = 0 where u == 0).
+ * The kernels evaluate mod / u = u^(gamma - 1) as exp2f((gamma - 1) * log2f(u)) and mod = u * (mod / u).
+ * gamma: finite and >= 1 (below 1 the factor u^(gamma - 1) is unbounded, and with label smoothing num0 does not vanish with u, so the gradient itself is).
+ * class_weight: K floats on the device or NULL (weights of one; with label_smoothing == 0 the plain arithmetic runs).
+ * All four: 1 <= K <= 33 (the message names the limit), 0 <= label_smoothing <= 1, gamma as above (the message holds the value), shapes > 0 and H * W < 2^30, no NULL
+ * buffer but class_weight, else SL_EINVAL before any launch.  No atomics: two runs give the same bits.
+ * sl_upsample_focal_fwd: partial has sl_upsample_ce_rows rows of (sum of pixel numerators, sum of denominators); sl_upsample_ce_finalize finishes it.
+ * sl_upsample_focal_bwd: dlogits = gscale[0] / loss_and_count[1] * transposed bilinear weights applied to the pixel gradients; the three kernel routes (and the
+ *   sl_debug_ce_tiled hook) of sl_upsample_ce_bwd; the channel-sliced kernel keeps (mod, beta) as two more words per footprint pixel in the LDS, under the same 150 KiB plan.
+ * sl_upsample_focal_dice_fwd / _bwd: the hybrid pair with only its cross-entropy part modulated; rows, partial layout, finalize (sl_upsample_ce_dice_rows,
+ *   sl_upsample_ce_dice_finalize) and coef are the hybrid pair's, the Dice sums are untouched. */
+int sl_upsample_focal_fwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing, float gamma,
+                          int B, int K, int h, int w, int H, int W, int ignore_index, float* partial, sl_stream_t stream);
+int sl_upsample_focal_bwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing, float gamma,
+                          const float* loss_and_count, const float* gscale, int B, int K, int h, int w, int H, int W,
+                          int ignore_index, float* dlogits, sl_stream_t stream);
+int sl_upsample_focal_dice_fwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing, float gamma,
+                               int B, int K, int h, int w, int H, int W, int ignore_index, float* partial, sl_stream_t stream);
+int sl_upsample_focal_dice_bwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing, float gamma,
+                               const float* loss3, const float* coef, const float* gscale, int B, int K, int h, int w, int H, int W,
+                               int ignore_index, float* dlogits, sl_stream_t stream);
 /* Online hard-pixel mining (OHEM, bootstrapped cross-entropy) in front of the criterion above: three passes that turn (logits, target) into a MINED label map, the
  * target with every dropped pixel set to ignore_index; the forward, finalize and backward entry points above then run on it unchanged.  Per call (per GPU batch):
  *   valid pixel: label != ignore_index and inside [0, K) (the rule of the loss kernels); n = number of valid pixels;

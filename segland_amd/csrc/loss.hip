@@ -24,30 +24,47 @@ template <> struct CeW<true> { const float* w; float keep, epsk; };   // w[K] on
 //   d dice / d v_k = p_k (q_k - sum_c p_c q_c),
 // added to the pixel's cross-entropy gradient BEFORE the bilinear scatter: per-pixel gradient = f0 * (cross-entropy form) + f1 * (Dice form), f0 = gscale[0] / denominator,
 // f1 = gscale[1].  CeD<false> is empty and every statement of the hybrid form sits under `if constexpr (DC)`: the <DC = false> instantiations are the kernels as they were.
-// In the hybrid kernels the class-weight pointer may be null (weights of one): cew_at.
+// In the hybrid kernels, and in the focal ones (FC below), the class-weight pointer may be null (weights of one): cew_at, whose first argument says so.
 template <bool DC> struct CeD {};
 template <> struct CeD<true> { const float* coef; };                  // [B][K][2] on the device
-template <bool DC, bool WT>
+template <bool NULLOK, bool WT>
 __device__ __forceinline__ float cew_at(const CeW<WT>& cw, int k) {
   if constexpr (!WT) return 1.f;
-  else if constexpr (DC) return cw.w ? cw.w[k] : 1.f;
+  else if constexpr (NULLOK) return cw.w ? cw.w[k] : 1.f;
   else return cw.w[k];
 }
 __device__ __forceinline__ float dice_q(int k, int t, float qa, float qg) { return qg + (k == t ? qa : 0.f); }   // q_k = g_k + a_k [k == t]
 
+// Focal modulation (Lin et al.) of the cross-entropy term, <FC = true>; the contract is in include/segland_hip.h.  With e_k = exp(v_k - m), s = sum_k e_k (index order),
+//   u = (sum_{k != t} e_k) / s   (index order, skipping t: 1 - p_t without the cancellation of 1 - e_t / s; exactly 0 when every other exponential underflows),
+//   mod = u^gamma,   pixel numerator = mod * num0   (num0, den: the cross-entropy numerator and denominator of ce_pixel; den is unchanged),
+//   d numerator / d v_k = mod * (cross-entropy form)_k + beta * (p_k - [k == t]),   beta = gamma * num0 * (mod / u) * p_t,   mod = beta = 0 where u == 0.
+// The kernels evaluate mod / u = u^(gamma - 1) = exp2f((gamma - 1) * log2f(u)) once (gamma >= 1: at most 1, and exactly 1 for gamma == 1) and mod = u * (mod / u):
+// one logarithm and one exponential of the hardware's base, no division by u.  The gfx950 exp2f / log2f are good to ~1 ulp; the power's relative error is that of the
+// exponent, |(gamma - 1) log2 u| * 2^-24 * ln 2, and a pixel whose exponent is large (u tiny) enters the sums with a weight that small.  powf costs a polynomial
+// with extended-precision bookkeeping per pixel for digits the 2e-5 / 1e-3 bounds of these kernels never see.
+// CeF<false> is empty and every statement of the focal form sits under `if constexpr (FC)`: the <FC = false> instantiations are the kernels as they were (the same
+// instructions; their symbols carry one template argument more).
+template <bool FC> struct CeF {};
+template <> struct CeF<true> { float gamma; };
+__device__ __forceinline__ float focal_modu(float u, float gamma) { return u > 0.f ? exp2f((gamma - 1.f) * log2f(u)) : 0.f; }
+
 // The gradient of one valid pixel of label t with respect to its interpolated logits, in the three forms above: built once per pixel, at(k) once per channel.  wt = w_t,
 // wsum = sum_j w_j, p = softmax_k, w = w_k, (qa, qg) = coef[b][k], sq = sum_c p_c q_c.  <false, false> is p - [k == t] and nothing else; without DC the caller applies
 // the scale gscale[0] / denominator after the bilinear scatter, with DC f0 and f1 are inside.  A new loss term goes here and into ce_pixel, nowhere else.
-template <bool WT, bool DC>
+// FC: (mod, beta) of the pixel from ce_pixel; the cross-entropy form becomes mod * form + beta * (p - [k == t]), before f0 as before the scatter.
+template <bool WT, bool DC, bool FC = false>
 struct PixGrad {
-  int t; float hit, ct, epsk, f0, f1, sq;
-  __device__ __forceinline__ PixGrad(int t_, float wt, const CeW<WT>& cw, float wsum, float f0_, float f1_, float sq_) : t(t_), hit(1.f), ct(1.f), epsk(0.f), f0(f0_), f1(f1_), sq(sq_) {
+  int t; float hit, ct, epsk, f0, f1, sq, mod, beta;
+  __device__ __forceinline__ PixGrad(int t_, float wt, const CeW<WT>& cw, float wsum, float f0_, float f1_, float sq_, float mod_ = 1.f, float beta_ = 0.f)
+      : t(t_), hit(1.f), ct(1.f), epsk(0.f), f0(f0_), f1(f1_), sq(sq_), mod(mod_), beta(beta_) {
     if constexpr (WT) { hit = cw.keep * wt; ct = hit + cw.epsk * wsum; epsk = cw.epsk; }
   }
   __device__ __forceinline__ float at(int k, float p, float w, float qa, float qg) const {
     float ce;
     if constexpr (WT) ce = p * ct - ((k == t ? hit : 0.f) + epsk * w);
     else ce = p - (k == t ? 1.f : 0.f);
+    if constexpr (FC) ce = mod * ce + beta * (p - (k == t ? 1.f : 0.f));
     if constexpr (DC) return f0 * ce + f1 * (p * (dice_q(k, t, qa, qg) - sq));
     else return ce;
   }
@@ -133,28 +150,37 @@ __device__ __forceinline__ float ce_max(const float* v, int t, float& vt) {
   for (int k = 0; k < KW; ++k) { m = fmaxf(m, v[k]); if (k == t) vt = v[k]; }
   return m;
 }
-struct CePix { float num, den; };
-template <int KW, bool WT, bool DC>
-__device__ __forceinline__ CePix ce_pixel(int K, const float* v, float m, float s, float vt, int t, const CeW<WT>& cw) {
+// FC: the caller also hands so = sum_{k != t} e_k and et = e_t from the exponentials of its sum s; num becomes mod * num0, and (mod, beta) are the PixGrad's.
+struct CePix { float num, den, mod, beta; };
+template <int KW, bool WT, bool DC, bool FC = false>
+__device__ __forceinline__ CePix ce_pixel(int K, const float* v, float m, float s, float vt, int t, const CeW<WT>& cw, const CeF<FC>& cf = CeF<FC>(), float so = 0.f, float et = 0.f) {
   CePix o;
   if constexpr (WT) {
-    const float lse = logf(s) + m, wt = cew_at<DC>(cw, t);
+    const float lse = logf(s) + m, wt = cew_at<DC || FC>(cw, t);
     float sm = 0.f;                                     // sum_k w_k (-logp_k), in index order
 #pragma unroll
-    for (int k = 0; k < KW; ++k) if (k < K) sm += cew_at<DC>(cw, k) * (lse - v[k]);
+    for (int k = 0; k < KW; ++k) if (k < K) sm += cew_at<DC || FC>(cw, k) * (lse - v[k]);
     o.num = cw.keep * wt * (lse - vt) + cw.epsk * sm;
     o.den = wt;
   } else {
     o.num = logf(s) + m - vt;
     o.den = 1.f;
   }
+  if constexpr (FC) {
+    const float u = so / s, modu = focal_modu(u, cf.gamma);
+    o.mod = modu * u;
+    o.beta = cf.gamma * o.num * modu * (et / s);
+    o.num = o.mod * o.num;
+  }
   return o;
 }
 
 // part[blk] = (sum of pixel losses, number of valid pixels); WT: (sum of the pixel numerators, sum of w_t)
-template <int KW, bool WT>
+// cf sits in the four bytes of padding behind `ignore`: at the end, the empty CeF<false> moves the grid size this kernel reads behind its arguments by eight bytes
+// (one immediate of the weighted instantiations would differ from the kernel as it was).
+template <int KW, bool WT, bool FC>
 __global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(UpGeom g, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
-                                                              int ignore, float* __restrict__ part, CeW<WT> cw) {
+                                                              int ignore, CeF<FC> cf, float* __restrict__ part, CeW<WT> cw) {
   __shared__ float red[2][4];
   const long long total = (long long)g.B * g.H * g.W;
   float loss = 0.f, cnt = 0.f;
@@ -167,10 +193,15 @@ __global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(UpGeom g, const fl
     pixel_logits<KW>(g, lg, b, Y, X, v);
     float vt;
     const float m = ce_max<KW>(v, (int)t, vt);
-    float s = 0.f;
+    float s = 0.f, so = 0.f, et = 0.f;
+    if constexpr (FC) {
 #pragma unroll
-    for (int k = 0; k < KW; ++k) if (k < g.K) s += expf(v[k] - m);
-    const CePix px = ce_pixel<KW, WT, false>(g.K, v, m, s, vt, (int)t, cw);
+      for (int k = 0; k < KW; ++k) if (k < g.K) { const float e = expf(v[k] - m); s += e; if (k == (int)t) et = e; else so += e; }
+    } else {
+#pragma unroll
+      for (int k = 0; k < KW; ++k) if (k < g.K) s += expf(v[k] - m);
+    }
+    const CePix px = ce_pixel<KW, WT, false, FC>(g.K, v, m, s, vt, (int)t, cw, cf, so, et);
     loss += px.num; cnt += px.den;
   }
   loss = wave_sum(loss); cnt = wave_sum(cnt);
@@ -199,9 +230,9 @@ __global__ void upsample_ce_finalize_kernel(const float* __restrict__ part, int 
 // Forward of the hybrid form.  Block blockIdx.x = b * nbs + j strides over the H * W pixels of sample b alone (a row of partials never mixes samples), evaluates each
 // pixel's softmax once and reduces the cross-entropy partials (the arithmetic of upsample_ce_fwd_kernel) and the per-class Dice sums:
 //   part[blk][2 + 3K] = (cross-entropy numerator, denominator, I[0..K), P[0..K), T[0..K))
-template <int KW, bool WT>
+template <int KW, bool WT, bool FC>
 __global__ __launch_bounds__(256) void upsample_ce_dice_fwd_kernel(UpGeom g, int nbs, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
-                                                                   int ignore, float* __restrict__ part, CeW<WT> cw) {
+                                                                   int ignore, float* __restrict__ part, CeW<WT> cw, CeF<FC> cf) {
   __shared__ float red[4][2 + 3 * KW];
   const int b = blockIdx.x / nbs, jb = blockIdx.x - b * nbs;
   const int hw = g.H * g.W;
@@ -224,7 +255,12 @@ __global__ __launch_bounds__(256) void upsample_ce_dice_fwd_kernel(UpGeom g, int
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < KW; ++k) { e[k] = k < g.K ? expf(v[k] - m) : 0.f; if (k < g.K) s += e[k]; }
-    const CePix px = ce_pixel<KW, WT, true>(g.K, v, m, s, vt, (int)t, cw);
+    float so = 0.f, et = 0.f;
+    if constexpr (FC) {
+#pragma unroll
+      for (int k = 0; k < KW; ++k) if (k < g.K) { if (k == (int)t) et = e[k]; else so += e[k]; }
+    }
+    const CePix px = ce_pixel<KW, WT, true, FC>(g.K, v, m, s, vt, (int)t, cw, cf, so, et);
     loss += px.num; cnt += px.den;
     const float inv = 1.f / s;
 #pragma unroll
@@ -301,10 +337,10 @@ __global__ __launch_bounds__(1024) void upsample_ce_dice_finalize_kernel(const f
 
 // four lanes per low-resolution cell (each takes every 4th footprint row), gather over the pixels whose bilinear
 // footprint touches the cell, then a 4-lane shuffle reduction: deterministic, no atomics.
-template <int KW, bool WT, bool DC>
+template <int KW, bool WT, bool DC, bool FC>
 __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
                                                               const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
-                                                              int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd) {
+                                                              int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd, CeF<FC> cf) {
   const long long cells = (long long)g.B * g.h * g.w;
   const long long ci = (blockIdx.x * 256LL + threadIdx.x) >> 2;
   const int sub = threadIdx.x & 3;
@@ -320,7 +356,7 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
   float wsum = 0.f;
   if constexpr (WT) {
 #pragma unroll
-    for (int k = 0; k < KW; ++k) if (k < g.K) wsum += cew_at<DC>(cw, k);
+    for (int k = 0; k < KW; ++k) if (k < g.K) wsum += cew_at<DC || FC>(cw, k);
   }
   float qa[DC ? KW : 1], qg[DC ? KW : 1], f0 = 0.f, f1 = 0.f;      // DC: the (a, g) of this cell's sample and the two scales
   if constexpr (DC) {
@@ -350,8 +386,21 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
 #pragma unroll
         for (int k = 0; k < KW; ++k) m = fmaxf(m, v[k]);
         float s = 0.f;
+        CePix px = {};                                    // FC: the pixel's (mod, beta), from the logits before the exponentials take their place
+        if constexpr (FC) {
+          float e[KW], vt = 0.f, so = 0.f, et = 0.f;
 #pragma unroll
-        for (int k = 0; k < KW; ++k) { v[k] = k < g.K ? expf(v[k] - m) : 0.f; s += v[k]; }
+          for (int k = 0; k < KW; ++k) {
+            e[k] = k < g.K ? expf(v[k] - m) : 0.f; s += e[k];
+            if (k == (int)t) { vt = v[k]; et = e[k]; } else so += e[k];
+          }
+          px = ce_pixel<KW, WT, DC, true>(g.K, v, m, s, vt, (int)t, cw, cf, so, et);
+#pragma unroll
+          for (int k = 0; k < KW; ++k) v[k] = e[k];
+        } else {
+#pragma unroll
+          for (int k = 0; k < KW; ++k) { v[k] = k < g.K ? expf(v[k] - m) : 0.f; s += v[k]; }
+        }
         const float wgt = wy * wx, inv = 1.f / s;
         float sq = 0.f;                                   // DC: sum_c p_c q_c, in index order
 #pragma unroll
@@ -359,11 +408,11 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
           v[k] *= inv;
           if constexpr (DC) sq += v[k] * dice_q(k, (int)t, qa[k], qg[k]);
         }
-        const PixGrad<WT, DC> pg((int)t, cew_at<DC>(cw, (int)t), cw, wsum, f0, f1, sq);
+        const PixGrad<WT, DC, FC> pg((int)t, cew_at<DC || FC>(cw, (int)t), cw, wsum, f0, f1, sq, FC ? px.mod : 1.f, FC ? px.beta : 0.f);
         constexpr bool PLAIN = !WT && !DC;                // reads no table: runs over all KW unguarded (acc beyond K is never stored)
 #pragma unroll
         for (int k = 0; k < KW; ++k)
-          if (PLAIN || k < g.K) acc[k] += wgt * pg.at(k, v[k], cew_at<DC>(cw, k), DC ? qa[k] : 0.f, DC ? qg[k] : 0.f);
+          if (PLAIN || k < g.K) acc[k] += wgt * pg.at(k, v[k], cew_at<DC || FC>(cw, k), DC ? qa[k] : 0.f, DC ? qg[k] : 0.f);
       }
     }
   }
@@ -395,7 +444,8 @@ enum TileBuf {
   T_WX0,   // [NX][3]
   T_WXJ,   // [NX][CT] weight of footprint column X on cell j0 + jr
   T_WYI,   // [NY][CT]
-  T_ST,    // wide: [NY][NX][SW] max, 1 / sum, label as int (-1: the pixel does not count); DC: the fourth word is sum_c p_c q_c over ALL K channels
+  T_ST,    // wide: [NY][NX][SW] max, 1 / sum, label as int (-1: the pixel does not count); DC: the fourth word is sum_c p_c q_c over ALL K channels;
+           // FC: the last two words are the pixel's (mod, beta)
   T_H1,    // [NY][CT][KS]
   T_G,     // [NY][NX][KS]
   T_WL,    // WT: [K] class weights
@@ -404,17 +454,17 @@ enum TileBuf {
 };
 // I: size_t on the host, which sizes a launch it may still refuse; int on the device, where the sum has passed the host's 150 KiB limit
 template <typename I>
-__host__ __device__ inline void tile_extents(int K, const UpTile& ut, bool wt, bool dc, bool wide, I* n) {
+__host__ __device__ inline void tile_extents(int K, const UpTile& ut, bool wt, bool dc, bool fc, bool wide, I* n) {
   const I NY = ut.NYmax, NX = ut.NXmax;
   n[T_LGT] = (I)(CT + 2) * (CT + 2) * K;
   n[T_WY0] = 3 * NY; n[T_WX0] = 3 * NX; n[T_WXJ] = CT * NX; n[T_WYI] = CT * NY;
-  n[T_ST] = wide ? (dc ? 4 : 3) * NY * NX : 0;
+  n[T_ST] = wide ? ((dc ? 4 : 3) + (fc ? 2 : 0)) * NY * NX : 0;
   n[T_H1] = NY * CT * ut.KS; n[T_G] = NY * NX * ut.KS;
   n[T_WL] = wt ? K : 0; n[T_CF] = dc ? 2 * K : 0;
 }
-inline size_t tile_lds_bytes(int K, const UpTile& ut, bool wt, bool dc, bool wide) {
+inline size_t tile_lds_bytes(int K, const UpTile& ut, bool wt, bool dc, bool fc, bool wide) {
   size_t n[T_NBUF], s = 0;
-  tile_extents(K, ut, wt, dc, wide, n);
+  tile_extents(K, ut, wt, dc, fc, wide, n);
   for (int i = 0; i < T_NBUF; ++i) s += n[i];
   return s * sizeof(float);
 }
@@ -425,12 +475,12 @@ struct TileFrame {
   float* buf[T_NBUF];
 };
 // Carves the LDS and fills lgt, the weight and coefficient tables and wy0 / wx0 / wyi / wxj; ends with the barrier.
-template <int NT, bool WT, bool DC, bool WIDE>
+template <int NT, bool WT, bool DC, bool WIDE, bool FC = false>
 __device__ __forceinline__ TileFrame tile_frame(const UpGeom& g, const UpTile& ut, float* sm, const float* __restrict__ lg, const CeW<WT>& cw, const CeD<DC>& cd) {
   TileFrame f;
   const int K = g.K, tid = threadIdx.x;
   int n[T_NBUF];
-  tile_extents(K, ut, WT, DC, WIDE, n);
+  tile_extents(K, ut, WT, DC, FC, WIDE, n);
 #pragma unroll
   for (int i = 0; i < T_NBUF; ++i) { f.buf[i] = sm; sm += n[i]; }
   float *lgt = f.buf[T_LGT], *wy0 = f.buf[T_WY0], *wx0 = f.buf[T_WX0], *wxj = f.buf[T_WXJ], *wyi = f.buf[T_WYI];
@@ -449,7 +499,7 @@ __device__ __forceinline__ TileFrame tile_frame(const UpGeom& g, const UpTile& u
     const int yy = min(max(i0 - 1 + cy, 0), g.h - 1), xx = min(max(j0 - 1 + cx, 0), g.w - 1);
     lgt[e] = lb[((size_t)k * g.h + yy) * g.w + xx];
   }
-  if constexpr (WT) for (int e = tid; e < K; e += NT) f.buf[T_WL][e] = cew_at<DC>(cw, e);
+  if constexpr (WT) for (int e = tid; e < K; e += NT) f.buf[T_WL][e] = cew_at<DC || FC>(cw, e);
   if constexpr (DC) for (int e = tid; e < 2 * K; e += NT) f.buf[T_CF][e] = cd.coef[(size_t)b * K * 2 + e];
   for (int e = tid; e < NY; e += NT) {
     int y0, y1; float ly; src_index_ac1(Ylo + e, g.h, g.sy, y0, y1, ly);
@@ -520,10 +570,10 @@ __device__ __forceinline__ void scatter_y_store(const UpGeom& g, const TileFrame
   }
 }
 
-template <int NT, bool WT, bool DC>
+template <int NT, bool WT, bool DC, bool FC>
 __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpTile ut, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
-                                                                    const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
-                                                                    int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd) {
+                                                                   const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
+                                                                   int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd, CeF<FC> fo) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int KW = KNC;                            // this kernel serves K <= KNC (G holds all K channels of every footprint pixel)
   const int K = g.K;
@@ -556,7 +606,7 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
     const int yy = min(max(i0 - 1 + cy, 0), g.h - 1), xx = min(max(j0 - 1 + cx, 0), g.w - 1);
     lgt[e] = lb[((size_t)k * g.h + yy) * g.w + xx];
   }
-  if constexpr (WT) for (int e = tid; e < K; e += NT) wl[e] = cew_at<DC>(cw, e);
+  if constexpr (WT) for (int e = tid; e < K; e += NT) wl[e] = cew_at<DC || FC>(cw, e);
   if constexpr (DC) for (int e = tid; e < 2 * K; e += NT) cf[e] = cd.coef[(size_t)b * K * 2 + e];
   for (int e = tid; e < NY; e += NT) {
     int y0, y1; float ly; src_index_ac1(Ylo + e, g.h, g.sy, y0, y1, ly);
@@ -609,8 +659,21 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
       else v[k] = -INFINITY;
     }
     float ssum = 0.f;
+    CePix px = {};                                     // FC: the pixel's (mod, beta), from the logits before the exponentials take their place
+    if constexpr (FC) {
+      float e[KW], vt = 0.f, so = 0.f, et = 0.f;
 #pragma unroll
-    for (int k = 0; k < KW; ++k) { v[k] = k < K ? __expf(v[k] - m) : 0.f; ssum += v[k]; }      // hardware exp2-based: 2 ulp, the gradient's tolerance is 1e-3
+      for (int k = 0; k < KW; ++k) {
+        e[k] = k < K ? __expf(v[k] - m) : 0.f; ssum += e[k];
+        if (k == (int)t) { vt = v[k]; et = e[k]; } else so += e[k];
+      }
+      px = ce_pixel<KW, WT, DC, true>(K, v, m, ssum, vt, (int)t, cw, fo, so, et);
+#pragma unroll
+      for (int k = 0; k < KW; ++k) v[k] = e[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < KW; ++k) { v[k] = k < K ? __expf(v[k] - m) : 0.f; ssum += v[k]; }      // hardware exp2-based: 2 ulp, the gradient's tolerance is 1e-3
+    }
     const float inv = 1.f / ssum;
     // DC normalises v first (sq = sum_c p_c q_c, in index order, needs every p); the other forms multiply by inv at the one use below, under the same k < K guard as
     // the store: a normalising loop of its own costs them 16 selects per pixel (measured: +3 % on this kernel)
@@ -619,7 +682,7 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
 #pragma unroll
       for (int k = 0; k < KW; ++k) if (k < K) { v[k] *= inv; sq += v[k] * dice_q(k, (int)t, cf[2 * k], cf[2 * k + 1]); }
     }
-    const PixGrad<WT, DC> pg((int)t, WT ? wl[t] : 1.f, cw, wsum, f0, f1, sq);
+    const PixGrad<WT, DC, FC> pg((int)t, WT ? wl[t] : 1.f, cw, wsum, f0, f1, sq, FC ? px.mod : 1.f, FC ? px.beta : 0.f);
 #pragma unroll
     for (int k = 0; k < KW; ++k) if (k < K) out[k] = pg.at(k, DC ? v[k] : v[k] * inv, WT ? wl[k] : 0.f, DC ? cf[2 * k] : 0.f, DC ? cf[2 * k + 1] : 0.f);
   }
@@ -654,14 +717,16 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
 // The tiled gradient for K > KNC, channels in slices of ut.KS.  One pass over the footprint first computes every pixel's max and 1 / sum over ALL K channels from lgt
 // and keeps them with the label (three words per pixel); pass 1 and the scatter then run once per slice on those statistics.
 // Each pixel's softmax is still evaluated once (2 K exponentials instead of K); sums in a fixed order, no atomics.
-template <int NT, bool WT, bool DC>
+// FC: the focal (mod, beta) of a pixel need all K channels (the cross-entropy numerator, the sum without t), so pass 0, the only one that sees them all, evaluates
+// ce_pixel on the pixel's K logits in registers and keeps the two values as two more statistics words; the slices read them back into their PixGrad.
+template <int NT, bool WT, bool DC, bool FC>
 __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g, UpTile ut, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
-                                                                         const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
-                                                                         int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd) {
+                                                                        const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
+                                                                        int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd, CeF<FC> fo) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  constexpr int SW = DC ? 4 : 3;                     // statistics words per footprint pixel
+  constexpr int SW = (DC ? 4 : 3) + (FC ? 2 : 0);    // statistics words per footprint pixel
   const int K = g.K, KS = ut.KS, tid = threadIdx.x;
-  const TileFrame f = tile_frame<NT, WT, DC, true>(g, ut, sm, lg, cw, cd);
+  const TileFrame f = tile_frame<NT, WT, DC, true, FC>(g, ut, sm, lg, cw, cd);
   const int b = f.b, i0 = f.i0, j0 = f.j0, Ylo = f.Ylo, Xlo = f.Xlo, NY = f.NY, NX = f.NX;
   float *st = f.buf[T_ST], *G = f.buf[T_G];
   const float *lgt = f.buf[T_LGT], *wy0 = f.buf[T_WY0], *wx0 = f.buf[T_WX0], *wl = f.buf[T_WL], *cf = f.buf[T_CF];
@@ -675,7 +740,20 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
     float m = -INFINITY;
     for (int k = 0; k < K; ++k) m = fmaxf(m, tap.at(k));
     float ssum = 0.f;
-    if constexpr (DC) {
+    if constexpr (FC) {
+      float v[KMAXC], vt = 0.f, so = 0.f, et = 0.f, sq = 0.f;
+#pragma unroll
+      for (int k = 0; k < KMAXC; ++k) {
+        v[k] = k < K ? tap.at(k) : -INFINITY;
+        const float e = k < K ? __expf(v[k] - m) : 0.f;
+        ssum += e;
+        if (k == (int)t) { vt = v[k]; et = e; } else so += e;
+        if constexpr (DC) if (k < K) sq += e * dice_q(k, (int)t, cf[2 * k], cf[2 * k + 1]);
+      }
+      if constexpr (DC) s[3] = sq * (1.f / ssum);
+      const CePix px = ce_pixel<KMAXC, WT, DC, true>(K, v, m, ssum, vt, (int)t, cw, fo, so, et);
+      s[SW - 2] = px.mod; s[SW - 1] = px.beta;
+    } else if constexpr (DC) {
       float sq = 0.f;                                  // sum_c e_c q_c from the same exponentials, in index order
       for (int k = 0; k < K; ++k) { const float e = __expf(tap.at(k) - m); ssum += e; sq += e * dice_q(k, (int)t, cf[2 * k], cf[2 * k + 1]); }
       s[3] = sq * (1.f / ssum);
@@ -704,7 +782,7 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
       }
       const UpTap tap = up_tap(lgt, wy0, wx0, yr, xr, i0, j0, K);
       const float m = s[0], inv = s[1];
-      const PixGrad<WT, DC> pg(t, WT ? wl[t] : 1.f, cw, wsum, f0, f1, DC ? s[3] : 0.f);
+      const PixGrad<WT, DC, FC> pg(t, WT ? wl[t] : 1.f, cw, wsum, f0, f1, DC ? s[3] : 0.f, FC ? s[SW - 2] : 1.f, FC ? s[SW - 1] : 0.f);
       for (int kk = 0; kk < kn; ++kk) {
         const int k = k0 + kk;
         out[kk] = pg.at(k, __expf(tap.at(k) - m) * inv, WT ? wl[k] : 0.f, DC ? cf[2 * k] : 0.f, DC ? cf[2 * k + 1] : 0.f);
@@ -1044,10 +1122,11 @@ inline UpGeom make_up(int B, int K, int h, int w, int H, int W) {
 inline int ce_blocks(long long total) { long long b = (total + 255) / 256; return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); }
 
 // One launch plan for the plain (WT = false) and the weighted (WT = true) forms: which kernel runs depends on K, the scale and the hook only.
-template <bool WT>
-int launch_ce_fwd(const UpGeom& g, const float* logits, const int64_t* target, int ignore_index, float* partial, hipStream_t stream, CeW<WT> cw) {
+// FC (the focal forms): the same plan, rows and partial layout; gamma rides in cf.
+template <bool WT, bool FC = false>
+int launch_ce_fwd(const UpGeom& g, const float* logits, const int64_t* target, int ignore_index, float* partial, hipStream_t stream, CeW<WT> cw, CeF<FC> cf = CeF<FC>()) {
   const int nblk = ce_blocks((long long)g.B * g.H * g.W);
-  return sl_launch("upsample_ce_fwd_kernel", g.K <= KNC ? upsample_ce_fwd_kernel<KNC, WT> : upsample_ce_fwd_kernel<KMAXC, WT>, dim3(nblk), dim3(256), 0, stream, g, logits, target, ignore_index, partial, cw);
+  return sl_launch("upsample_ce_fwd_kernel", g.K <= KNC ? upsample_ce_fwd_kernel<KNC, WT, FC> : upsample_ce_fwd_kernel<KMAXC, WT, FC>, dim3(nblk), dim3(256), 0, stream, g, logits, target, ignore_index, cf, partial, cw);
 }
 
 // nbs: blocks per sample of the hybrid forward (its partial buffer has B * nbs rows).  About 1024 blocks in all, a quarter of the plain forward's: a block ends in 3 K wave
@@ -1057,20 +1136,21 @@ inline int ce_dice_blocks(int B, long long hw) {
   return (int)(need < 1 ? 1 : (need > cap ? (cap < 1 ? 1 : cap) : need));
 }
 
-template <bool WT>
-int launch_ce_dice_fwd(const UpGeom& g, const float* logits, const int64_t* target, int ignore_index, float* partial, hipStream_t stream, CeW<WT> cw) {
+template <bool WT, bool FC = false>
+int launch_ce_dice_fwd(const UpGeom& g, const float* logits, const int64_t* target, int ignore_index, float* partial, hipStream_t stream, CeW<WT> cw, CeF<FC> cf = CeF<FC>()) {
   const int nbs = ce_dice_blocks(g.B, (long long)g.H * g.W);
   // three per-thread accumulators per channel: a width of 8 (the bench head) keeps the kernel at twice the waves per SIMD of the width of 16
-  return sl_launch("upsample_ce_dice_fwd_kernel", g.K <= 8 ? upsample_ce_dice_fwd_kernel<8, WT> : g.K <= KNC ? upsample_ce_dice_fwd_kernel<KNC, WT> : upsample_ce_dice_fwd_kernel<KMAXC, WT>,
+  return sl_launch("upsample_ce_dice_fwd_kernel", g.K <= 8 ? upsample_ce_dice_fwd_kernel<8, WT, FC> : g.K <= KNC ? upsample_ce_dice_fwd_kernel<KNC, WT, FC> : upsample_ce_dice_fwd_kernel<KMAXC, WT, FC>,
                    dim3((unsigned)(g.B * nbs)), dim3(256), 0, stream,
-                   g, nbs, logits, target, ignore_index, partial, cw);
+                   g, nbs, logits, target, ignore_index, partial, cw, cf);
 }
 
 // DC (the hybrid form): the tiled kernels keep 2 K coefficients more in the LDS and the channel-sliced one a fourth word per footprint pixel; the same 150 KiB limit decides
 // (more slices, then the gather kernel).  loss_and_count is then the finalize's (cross-entropy, denominator, dice) and gscale holds two values.
-template <bool WT, bool DC = false>
+// FC (the focal forms): two words more per footprint pixel in the channel-sliced kernel's statistics, decided by the same list and limit.
+template <bool WT, bool DC = false, bool FC = false>
 int launch_ce_bwd(const UpGeom& g, const float* logits, const int64_t* target, const float* loss_and_count, const float* gscale, int ignore_index, float* dlogits,
-                  hipStream_t stream, CeW<WT> cw, CeD<DC> cd = CeD<DC>()) {
+                  hipStream_t stream, CeW<WT> cw, CeD<DC> cd = CeD<DC>(), CeF<FC> cf = CeF<FC>()) {
   const int B = g.B, K = g.K, h = g.h, w = g.w, H = g.H, W = g.W;
   const long long cells = (long long)B * h * w;
   // tiled kernel when the joint footprint of a CT x CT cell tile fits the LDS (always for an upsampling factor <= ~12 at K <= 16); test hook sl_debug_ce_tiled(0): never
@@ -1086,21 +1166,21 @@ int launch_ce_bwd(const UpGeom& g, const float* logits, const int64_t* target, c
     const size_t limit = 150 * 1024;
     if (!wide) {                                     // all K channels in one pass, or not tiled
       ut.KS = K;
-      const size_t lds = tile_lds_bytes(K, ut, WT, DC, false);
+      const size_t lds = tile_lds_bytes(K, ut, WT, DC, FC, false);
       if (lds <= limit)
-        return sl_launch("upsample_ce_bwd_tiled_kernel", upsample_ce_bwd_tiled_kernel<SL_UPCE_NT, WT, DC>, tiles, dim3(SL_UPCE_NT), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw, cd);
+        return sl_launch("upsample_ce_bwd_tiled_kernel", upsample_ce_bwd_tiled_kernel<SL_UPCE_NT, WT, DC, FC>, tiles, dim3(SL_UPCE_NT), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw, cd, cf);
     } else {
       // channel-sliced form: the fewest slices (of at most KNC channels) whose G and H1 fit next to the per-pixel statistics
       for (int ns = cdiv(K, KNC); ns <= K; ++ns) {
         ut.KS = cdiv(K, ns);
-        const size_t lds = tile_lds_bytes(K, ut, WT, DC, true);
+        const size_t lds = tile_lds_bytes(K, ut, WT, DC, FC, true);
         if (lds > limit) continue;
-        return sl_launch("upsample_ce_bwd_tiled_wide_kernel", upsample_ce_bwd_tiled_wide_kernel<512, WT, DC>, tiles, dim3(512), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw, cd);
+        return sl_launch("upsample_ce_bwd_tiled_wide_kernel", upsample_ce_bwd_tiled_wide_kernel<512, WT, DC, FC>, tiles, dim3(512), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw, cd, cf);
       }
     }
   }
-  return sl_launch("upsample_ce_bwd_kernel", K <= KNC ? upsample_ce_bwd_kernel<KNC, WT, DC> : upsample_ce_bwd_kernel<KMAXC, WT, DC>, dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, stream, g, logits, target,
-                   loss_and_count, gscale, ignore_index, dlogits, cw, cd);
+  return sl_launch("upsample_ce_bwd_kernel", K <= KNC ? upsample_ce_bwd_kernel<KNC, WT, DC, FC> : upsample_ce_bwd_kernel<KMAXC, WT, DC, FC>, dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, stream, g, logits, target,
+                   loss_and_count, gscale, ignore_index, dlogits, cw, cd, cf);
 }
 
 inline CeW<true> make_cew(const float* class_weight, float label_smoothing, int K) {
@@ -1191,6 +1271,55 @@ extern "C" int sl_upsample_ce_dice_bwd(const float* logits, const int64_t* targe
   if (!class_weight && label_smoothing == 0.f)
     return launch_ce_bwd<false, true>(g, logits, target, loss3, gscale, ignore_index, dlogits, (hipStream_t)stream, CeW<false>(), cd);
   return launch_ce_bwd<true, true>(g, logits, target, loss3, gscale, ignore_index, dlogits, (hipStream_t)stream, make_cew(class_weight, label_smoothing, K), cd);
+}
+
+// ---- focal modulation of the cross-entropy term (CeF above; the contract is in the header).  class_weight may be null: weights of one, as in the hybrid pair.
+#define SL_FOCAL_COMMON(what)                                                                                                                       \
+  SL_CE_DICE_COMMON(what);                                                                                                                          \
+  SL_REQUIRE(gamma >= 1.f && gamma <= 3.402823466e38f, what ": gamma %g is not a finite value >= 1 (u^(gamma - 1) is unbounded below 1)", (double)gamma)
+
+inline CeF<true> make_cef(float gamma) { CeF<true> cf; cf.gamma = gamma; return cf; }
+
+extern "C" int sl_upsample_focal_fwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing, float gamma,
+                                     int B, int K, int h, int w, int H, int W, int ignore_index, float* partial, sl_stream_t stream) {
+  SL_FOCAL_COMMON("upsample_focal_fwd");
+  SL_REQUIRE(logits && target && partial, "upsample_focal_fwd: null buffer");
+  const UpGeom g = make_up(B, K, h, w, H, W);
+  if (!class_weight && label_smoothing == 0.f) return launch_ce_fwd<false, true>(g, logits, target, ignore_index, partial, (hipStream_t)stream, CeW<false>(), make_cef(gamma));
+  return launch_ce_fwd<true, true>(g, logits, target, ignore_index, partial, (hipStream_t)stream, make_cew(class_weight, label_smoothing, K), make_cef(gamma));
+}
+
+extern "C" int sl_upsample_focal_bwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing, float gamma,
+                                     const float* loss_and_count, const float* gscale, int B, int K, int h, int w, int H, int W,
+                                     int ignore_index, float* dlogits, sl_stream_t stream) {
+  SL_FOCAL_COMMON("upsample_focal_bwd");
+  SL_REQUIRE(logits && target && loss_and_count && gscale && dlogits, "upsample_focal_bwd: null buffer");
+  const UpGeom g = make_up(B, K, h, w, H, W);
+  if (!class_weight && label_smoothing == 0.f)
+    return launch_ce_bwd<false, false, true>(g, logits, target, loss_and_count, gscale, ignore_index, dlogits, (hipStream_t)stream, CeW<false>(), CeD<false>(), make_cef(gamma));
+  return launch_ce_bwd<true, false, true>(g, logits, target, loss_and_count, gscale, ignore_index, dlogits, (hipStream_t)stream, make_cew(class_weight, label_smoothing, K),
+                                          CeD<false>(), make_cef(gamma));
+}
+
+extern "C" int sl_upsample_focal_dice_fwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing, float gamma,
+                                          int B, int K, int h, int w, int H, int W, int ignore_index, float* partial, sl_stream_t stream) {
+  SL_FOCAL_COMMON("upsample_focal_dice_fwd");
+  SL_REQUIRE(logits && target && partial, "upsample_focal_dice_fwd: null buffer");
+  const UpGeom g = make_up(B, K, h, w, H, W);
+  if (!class_weight && label_smoothing == 0.f) return launch_ce_dice_fwd<false, true>(g, logits, target, ignore_index, partial, (hipStream_t)stream, CeW<false>(), make_cef(gamma));
+  return launch_ce_dice_fwd<true, true>(g, logits, target, ignore_index, partial, (hipStream_t)stream, make_cew(class_weight, label_smoothing, K), make_cef(gamma));
+}
+
+extern "C" int sl_upsample_focal_dice_bwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing, float gamma,
+                                          const float* loss3, const float* coef, const float* gscale, int B, int K, int h, int w, int H, int W,
+                                          int ignore_index, float* dlogits, sl_stream_t stream) {
+  SL_FOCAL_COMMON("upsample_focal_dice_bwd");
+  SL_REQUIRE(logits && target && loss3 && coef && gscale && dlogits, "upsample_focal_dice_bwd: null buffer");
+  const UpGeom g = make_up(B, K, h, w, H, W);
+  CeD<true> cd; cd.coef = coef;
+  if (!class_weight && label_smoothing == 0.f)
+    return launch_ce_bwd<false, true, true>(g, logits, target, loss3, gscale, ignore_index, dlogits, (hipStream_t)stream, CeW<false>(), cd, make_cef(gamma));
+  return launch_ce_bwd<true, true, true>(g, logits, target, loss3, gscale, ignore_index, dlogits, (hipStream_t)stream, make_cew(class_weight, label_smoothing, K), cd, make_cef(gamma));
 }
 
 // ---- online hard-pixel mining: probability pass, exact k-th smallest selection, mined label map (the kernels above; one call of each per head)

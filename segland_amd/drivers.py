@@ -74,15 +74,28 @@ def ohem_min_kept(v):
     return n
 
 
+def focal_gamma(v):
+    try:
+        gamma = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError('float expected (got %r)' % (v,))
+    if gamma != 0.0 and not (np.isfinite(gamma) and gamma >= 1.0):
+        raise argparse.ArgumentTypeError('the focal exponent must be finite and >= 1, or 0 for off (got %r)' % (v,))
+    return gamma
+
+
 def log_loss_options(args):
-    """One line at start: the controls of the segmentation criterion (loss.get_loss reads the same fields); the Dice weight and the mining controls only where they are on."""
+    """One line at start: the controls of the segmentation criterion (loss.get_loss reads the same fields); the Dice weight, the focal exponent and the mining controls only where they are on."""
     import logging
     w = class_weights(getattr(args, 'class_weights', ()) or ())
     lam = float(getattr(args, 'dice_weight', 0.0))
     th = float(getattr(args, 'ohem_thresh', 0.0) or 0.0)
+    gamma = float(getattr(args, 'focal_gamma', 0.0))
     logging.getLogger('Segmentation').info('segmentation loss: class weights %s, label smoothing %g' + (', dice weight %g' if lam > 0.0 else '')
+                                           + (', focal gamma %g' if gamma > 0.0 else '')
                                            + (', hard-pixel mining: threshold %g, at least %d pixels per batch' if th > 0.0 else ''),
                                            ','.join('%g' % x for x in w) if w else 'none', float(getattr(args, 'label_smoothing', 0.0)), *((lam,) if lam > 0.0 else ()),
+                                           *((gamma,) if gamma > 0.0 else ()),
                                            *((th, int(getattr(args, 'ohem_min_kept', 100000))) if th > 0.0 else ()))
 
 
@@ -122,6 +135,9 @@ _COMMON = [
     ('--label-smoothing', dict(type=label_smoothing, default=0.0, help='label smoothing of the segmentation cross-entropy, in [0, 1]; default 0.')),
     ('--dice-weight', dict(type=dice_weight, default=0.0, help='weight of the multiclass soft Dice term added to the segmentation cross-entropy (main and auxiliary '
                                                                'head; class weights scale its per-class terms, ignored pixels are left out); default 0: cross-entropy only.')),
+    ('--focal-gamma', dict(type=focal_gamma, default=0.0, help='focal loss: every pixel\'s segmentation cross-entropy is scaled by (1 - p_t)^gamma, p_t the probability of its '
+                                                               'label (main and auxiliary head; class weights are the focal alpha; with --dice-weight the Dice term is left '
+                                                               'as it is); finite and >= 1; default 0: off.')),
     ('--ohem-thresh', dict(type=ohem_thresh, default=0.0, help='online hard-pixel mining (bootstrapped cross-entropy): only pixels whose probability of the true class '
                                                                'is at most this threshold, in (0, 1], enter the segmentation loss of a head, but never fewer than '
                                                                '--ohem-min-kept of them; default 0: off.')),

@@ -1034,3 +1034,46 @@ class UpsampleCEDiceFn(torch.autograd.Function):
         logits, target, out, coef, weight = ctx.saved_tensors
         gs = torch.stack([g_ce.detach().reshape(()).float(), g_dice.detach().reshape(()).float()])
         return ops.upsample_ce_dice_bwd(logits, target, out, coef, gs, ctx.ignore, weight, ctx.eps), None, None, None, None, None
+
+
+class UpsampleFocalFn(torch.autograd.Function):
+    """UpsampleCEFn with every pixel's cross-entropy numerator scaled by (1 - p_t)^gamma (focal loss, Lin et al.; include/segland_hip.h has the definition), fused in
+    the same kernels: gamma is a plain float, finite and >= 1; `weight` is the focal alpha, the mean divides by the cross-entropy's weight sum."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, gamma, weight=None, label_smoothing=0.0):
+        logits = logits.contiguous()
+        out = ops.upsample_focal_fwd(logits, target, ignore_index, gamma, weight, label_smoothing)
+        ctx.ignore = ignore_index
+        ctx.gamma = gamma
+        ctx.eps = label_smoothing
+        ctx.save_for_backward(logits, target, out, weight)
+        return out[0].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        logits, target, out, weight = ctx.saved_tensors
+        gs = g.detach().reshape(1).float().contiguous()
+        return ops.upsample_focal_bwd(logits, target, out, gs, ctx.ignore, ctx.gamma, weight, ctx.eps), None, None, None, None, None
+
+
+class UpsampleFocalDiceFn(torch.autograd.Function):
+    """UpsampleCEDiceFn with the cross-entropy part focal-modulated (UpsampleFocalFn); the Dice term is the hybrid criterion's, bit for bit."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, gamma, weight=None, label_smoothing=0.0, smooth=1.0):
+        logits = logits.contiguous()
+        out, coef = ops.upsample_focal_dice_fwd(logits, target, ignore_index, gamma, weight, label_smoothing, smooth)
+        ctx.ignore = ignore_index
+        ctx.gamma = gamma
+        ctx.eps = label_smoothing
+        ctx.save_for_backward(logits, target, out, coef, weight)
+        return out[0].clone(), out[2].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_ce, g_dice):
+        logits, target, out, coef, weight = ctx.saved_tensors
+        gs = torch.stack([g_ce.detach().reshape(()).float(), g_dice.detach().reshape(()).float()])
+        return ops.upsample_focal_dice_bwd(logits, target, out, coef, gs, ctx.ignore, ctx.gamma, weight, ctx.eps), None, None, None, None, None, None

@@ -4,7 +4,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..functional import UpsampleCEDiceFn, UpsampleCEFn
+from ..functional import UpsampleCEDiceFn, UpsampleCEFn, UpsampleFocalDiceFn, UpsampleFocalFn
 
 
 class OrthTerm:
@@ -33,9 +33,20 @@ class OrthLoss(nn.Module):
     with the dropped pixels set to ignore_index, in a new buffer: `target` is never written) by the same kernels; the kept set is a constant for the gradient.  Each
     head mines by its own probabilities; `weight` and `label_smoothing` do not enter them.  ohem_min_kept counts pixels per call (per GPU batch).  The dict gains
     'ohem_frac', the kept fraction of the main head's valid pixels (a device scalar; no read-back, so the step stays capturable).  Both are plain Python values: no
-    buffer, no state_dict key.  Off is the code path without it."""
+    buffer, no state_dict key.  Off is the code path without it.
 
-    def __init__(self, ignore_index=255, reduction='mean', weight=None, label_smoothing=0.0, dice_weight=0.0, dice_smooth=1.0, ohem_thresh=None, ohem_min_kept=100000):
+    `focal_gamma` (0: off, else a finite value >= 1) makes the cross-entropy a focal loss (Lin et al.), the smooth counterpart of the mining's hard cut: every valid
+    pixel's cross-entropy numerator is scaled by (1 - p_t)^focal_gamma, p_t the softmax probability of its label, computed as the sum of the other classes'
+    exponentials over the sum of all (no cancellation near p_t = 1; exactly 0 once the other classes underflow), inside the same fused kernels, gradient included.
+    The mean still divides by the cross-entropy's own denominator (the number, or with `weight` the weight sum, of the valid pixels), so `weight` acts as the focal
+    alpha; label smoothing is modulated as a whole (the factor multiplies the smoothed numerator).  Values below 1 are refused: the gradient carries
+    (1 - p_t)^(focal_gamma - 1), unbounded there.  With dice_weight > 0 only the cross-entropy part is modulated, the Dice term is unchanged; with mining on, the
+    pixels are mined by the unmodulated probabilities first and the focal criterion runs on the mined label map; the auxiliary head uses the same criterion.  The dict
+    gains no key: 'seg_loss' is the focal loss.  A plain float: no buffer, no state_dict key -- and, unlike the `weight` buffer, a kernel ARGUMENT: a captured
+    training step bakes the value in, so changing focal_gamma needs a new capture.  focal_gamma == 0 is the code path without it."""
+
+    def __init__(self, ignore_index=255, reduction='mean', weight=None, label_smoothing=0.0, dice_weight=0.0, dice_smooth=1.0, ohem_thresh=None, ohem_min_kept=100000,
+                 focal_gamma=0.0):
         super().__init__()
         if reduction != 'mean':
             raise ValueError('segland_amd OrthLoss implements reduction="mean" (what the reference uses)')
@@ -55,6 +66,9 @@ class OrthLoss(nn.Module):
                 raise ValueError('OrthLoss: ohem_thresh %r outside (0, 1] (None or 0: off)' % (ohem_thresh,))
         if isinstance(ohem_min_kept, bool) or int(ohem_min_kept) != ohem_min_kept or int(ohem_min_kept) < 1:
             raise ValueError('OrthLoss: ohem_min_kept %r is not an integer >= 1' % (ohem_min_kept,))
+        focal_gamma = float(focal_gamma)
+        if focal_gamma != 0.0 and not 1.0 <= focal_gamma < float('inf'):
+            raise ValueError('OrthLoss: focal_gamma %r is neither 0 (off) nor a finite value >= 1' % (focal_gamma,))
         if weight is not None:
             weight = torch.as_tensor(weight, dtype=torch.float32).detach().clone().contiguous()
             if weight.dim() != 1 or weight.numel() == 0:
@@ -66,6 +80,7 @@ class OrthLoss(nn.Module):
         self.dice_smooth = dice_smooth
         self.ohem_thresh = ohem_thresh
         self.ohem_min_kept = int(ohem_min_kept)
+        self.focal_gamma = focal_gamma
         self.w = 10.0
         self._triu = {}
 
@@ -90,15 +105,20 @@ class OrthLoss(nn.Module):
 
     def head_loss(self, preds, target):
         """(segmentation loss of one head, its unscaled Dice term or None, its kept fraction or None): with dice_weight > 0 one forward pass and one backward launch for
-        both terms; with mining on, both run on the head's mined label map"""
+        both terms; with mining on, both run on the head's mined label map; with focal_gamma > 0 the focal forms of the same two functions"""
         if self.weight is not None and self.weight.numel() != preds.shape[1]:
             raise ValueError('OrthLoss: %d class weights for %d logit channels' % (self.weight.numel(), preds.shape[1]))
         frac = None
         if self.ohem_thresh is not None:
             target, frac = self.mine(preds, target)
         if self.dice_weight > 0.0:
-            ce, dice = UpsampleCEDiceFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.weight, self.label_smoothing, self.dice_smooth)
+            if self.focal_gamma > 0.0:
+                ce, dice = UpsampleFocalDiceFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.focal_gamma, self.weight, self.label_smoothing, self.dice_smooth)
+            else:
+                ce, dice = UpsampleCEDiceFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.weight, self.label_smoothing, self.dice_smooth)
             return torch.add(ce, dice, alpha=self.dice_weight), dice, frac
+        if self.focal_gamma > 0.0:
+            return UpsampleFocalFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.focal_gamma, self.weight, self.label_smoothing), None, frac
         return UpsampleCEFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.weight, self.label_smoothing), None, frac
 
     def seg_loss(self, preds, target):

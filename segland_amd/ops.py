@@ -1112,6 +1112,69 @@ def upsample_ce_dice_bwd(logits, target, out, coef, gscale, ignore_index, weight
     return dl
 
 
+def upsample_focal_fwd(logits, target, ignore_index, gamma, weight=None, label_smoothing=0.0):
+    """float [2] = (focal loss of the upsampled logits: sum of (1 - p_t)^gamma * cross-entropy numerators over the cross-entropy's denominator, that denominator), as
+    include/segland_hip.h defines it; gamma finite and >= 1.  `weight` (the focal alpha) and `label_smoothing` as in upsample_ce_fwd; the partial rows and the finalize
+    launch are upsample_ce_fwd's."""
+    B, K, h, w = logits.shape
+    H, W = target.shape[1:]
+    L = _lib.lib()
+    cw = _ce_dice_weight(weight, K, logits.device)
+    nblk = L.sl_upsample_ce_rows(B, H, W)
+    part = _f32((nblk, 2), logits.device)
+    tok = PROFILER.begin_bytes('upsample_focal_fwd', logits.numel() * 4 + target.numel() * target.element_size())
+    check(L.sl_upsample_focal_fwd(_p(logits), _p(target), _p(cw), label_smoothing, gamma, B, K, h, w, H, W, ignore_index, _p(part), _s()), 'upsample_focal_fwd')
+    PROFILER.end_bytes(tok)
+    out = _f32((2,), logits.device)
+    check(L.sl_upsample_ce_finalize(_p(part), nblk, _p(out), _s()), 'upsample_ce_finalize')
+    return out
+
+
+def upsample_focal_bwd(logits, target, loss_cnt, gscale, ignore_index, gamma, weight=None, label_smoothing=0.0):
+    """d (gscale[0] * focal loss) / d logits; `loss_cnt` from upsample_focal_fwd."""
+    B, K, h, w = logits.shape
+    H, W = target.shape[1:]
+    cw = _ce_dice_weight(weight, K, logits.device)
+    dl = torch.empty_like(logits)
+    tok = PROFILER.begin_bytes('upsample_focal_bwd', 2 * logits.numel() * 4 + target.numel() * target.element_size())
+    check(_lib.lib().sl_upsample_focal_bwd(_p(logits), _p(target), _p(cw), label_smoothing, gamma, _p(loss_cnt), _p(gscale), B, K, h, w, H, W, ignore_index,
+                                            _p(dl), _s()), 'upsample_focal_bwd')
+    PROFILER.end_bytes(tok)
+    return dl
+
+
+def upsample_focal_dice_fwd(logits, target, ignore_index, gamma, weight=None, label_smoothing=0.0, smooth=1.0):
+    """upsample_ce_dice_fwd with the cross-entropy part focal-modulated (gamma finite and >= 1); the Dice term, the coefficient table, the partial layout and the
+    finalize launch are the hybrid pair's."""
+    B, K, h, w = logits.shape
+    H, W = target.shape[1:]
+    L = _lib.lib()
+    cw = _ce_dice_weight(weight, K, logits.device)
+    rows = L.sl_upsample_ce_dice_rows(B, H, W)
+    part = _f32((max(rows, 1), 2 + 3 * K), logits.device)
+    tok = PROFILER.begin_bytes('upsample_focal_dice_fwd', logits.numel() * 4 + target.numel() * target.element_size())
+    check(L.sl_upsample_focal_dice_fwd(_p(logits), _p(target), _p(cw), label_smoothing, gamma, B, K, h, w, H, W, ignore_index, _p(part), _s()), 'upsample_focal_dice_fwd')
+    PROFILER.end_bytes(tok)
+    out, coef = _f32((3,), logits.device), _f32((B, K, 2), logits.device)
+    check(L.sl_upsample_ce_dice_finalize(_p(part), _p(cw), smooth, B, K, H, W, _p(out), _p(coef), _s()), 'upsample_ce_dice_finalize')
+    return out, coef
+
+
+def upsample_focal_dice_bwd(logits, target, out, coef, gscale, ignore_index, gamma, weight=None, label_smoothing=0.0):
+    """d (gscale[0] * focal cross-entropy + gscale[1] * dice) / d logits in one launch; `out` and `coef` from upsample_focal_dice_fwd, gscale float [2] on the device."""
+    B, K, h, w = logits.shape
+    H, W = target.shape[1:]
+    if gscale.numel() != 2:
+        raise ValueError('upsample_focal_dice_bwd: gscale holds the two upstream gradients (got %d values)' % gscale.numel())
+    cw = _ce_dice_weight(weight, K, logits.device)
+    dl = torch.empty_like(logits)
+    tok = PROFILER.begin_bytes('upsample_focal_dice_bwd', 2 * logits.numel() * 4 + target.numel() * target.element_size())
+    check(_lib.lib().sl_upsample_focal_dice_bwd(_p(logits), _p(target), _p(cw), label_smoothing, gamma, _p(out), _p(coef), _p(gscale), B, K, h, w, H, W, ignore_index,
+                                                 _p(dl), _s()), 'upsample_focal_dice_bwd')
+    PROFILER.end_bytes(tok)
+    return dl
+
+
 def ohem_prob(logits, target, ignore_index):
     """float [B, H, W]: the softmax probability of the true class of every valid pixel of the upsampled logits (the forward kernel's arithmetic), 2.0 elsewhere"""
     B, K, h, w = logits.shape

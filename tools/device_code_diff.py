@@ -3,7 +3,10 @@
 function instruction by instruction (mnemonics, operands and branch labels).  A host-only refactor must print `identical` for every object it touched.
 
     python tools/device_code_diff.py parent/conv_wgrad.o segland_amd/csrc/conv_wgrad.o
-    python tools/device_code_diff.py parent/segland_amd/csrc segland_amd/csrc        # every *.o of two build directories; exit status 1 if any differs or is missing"""
+    python tools/device_code_diff.py parent/segland_amd/csrc segland_amd/csrc        # every *.o of two build directories; exit status 1 if any differs or is missing
+    python tools/device_code_diff.py --added-ok parent/loss.o segland_amd/csrc/loss.o # a change that adds kernels: functions of the second object alone are listed, not counted
+
+An instantiation whose template gained an argument has a new symbol; it is paired with the old one where the qualified name and every instruction are the same."""
 import os
 import re
 import subprocess
@@ -12,6 +15,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import loop_density  # noqa: E402
 
+ADDED_OK = False
+
 
 def local_labels(items):
     """Branch labels renumbered per function in order of appearance: the assembler numbers them through the whole object, so a function added in front of an untouched
@@ -19,6 +24,37 @@ def local_labels(items):
     seen = {}
     sub = lambda m: seen.setdefault(m.group(0), 'L#%d' % len(seen))
     return [tuple(re.sub(r'\bL\d+\b', sub, x) if isinstance(x, str) else x for x in it) for it in items]
+
+
+def base_name(sym):
+    """The qualified name of a mangled function without its template arguments and parameters (`_ZN12_GLOBAL__N_14nameILi16E...` -> `_GLOBAL__N_1::name`); the symbol
+    itself where it is not of that shape."""
+    m = re.match(r'_ZN?', sym)
+    if not m:
+        return sym
+    at, parts = m.end(), []
+    while True:
+        d = re.match(r'\d+', sym[at:])
+        if not d:
+            break
+        n = int(d.group(0))
+        parts.append(sym[at + d.end():at + d.end() + n])
+        at += d.end() + n
+    return '::'.join(parts) or sym
+
+
+def pair_renamed(a, b):
+    """[(symbol of a, symbol of b)]: functions on one side only whose template gained or lost an argument -- the same qualified name and the same instructions.  A kernel
+    template that takes one more parameter has new symbols for the instantiations it had; this is how `identical` is still shown for them."""
+    only_a, only_b = [s for s in sorted(a) if s not in b], [s for s in sorted(b) if s not in a]
+    pairs = []
+    for sa in only_a:
+        for sb in only_b:
+            if base_name(sa) == base_name(sb) and a[sa] == b[sb]:
+                pairs.append((sa, sb))
+                only_b.remove(sb)
+                break
+    return pairs
 
 
 def diff_objects(pa, pb):
@@ -34,10 +70,16 @@ def diff_objects(pa, pb):
         return 0 if a is b else 1
     nice = loop_density.demangle(sorted(set(a) | set(b)))
     bad = 0
+    renamed = pair_renamed(a, b)
+    for sa, sb in renamed:
+        print('same code, new symbol: %s -> %s' % (nice[sa], nice[sb]))
+    paired = {s for p in renamed for s in p}
     for sym in sorted(set(a) | set(b)):
+        if sym in paired:
+            continue
         if sym not in a or sym not in b:
             print('only in %s: %s' % (pa if sym in a else pb, nice[sym]))
-            bad += 1
+            bad += sym in a or not ADDED_OK
         elif a[sym] != b[sym]:
             at = next((i for i, (x, y) in enumerate(zip(a[sym], b[sym])) if x != y), min(len(a[sym]), len(b[sym])))
             print('differs: %s (%d vs %d items, first at %d)' % (nice[sym], len(a[sym]), len(b[sym]), at))
@@ -48,7 +90,10 @@ def diff_objects(pa, pb):
 
 
 def main():
-    pa, pb = sys.argv[1:3]
+    global ADDED_OK
+    args = [x for x in sys.argv[1:] if x != '--added-ok']
+    ADDED_OK = len(args) != len(sys.argv) - 1
+    pa, pb = args[:2]
     if not (os.path.isdir(pa) and os.path.isdir(pb)):
         return 1 if diff_objects(pa, pb) else 0
     # two build directories: every *.o that both hold, one line each; an object on one side only counts as a difference
