@@ -614,6 +614,14 @@ int sl_grad_norm_finalize(const float* partial, int nchunks, float max_norm, flo
 int sl_sgd_multi(const void* table_dev, int n, long long total_chunks, float momentum, const float* hyper_dev, const float* grad_scale, sl_stream_t stream);
 /* n <= 16 host floats -> device memory as kernel arguments (stream-ordered, no host -> device copy) */
 int sl_store_floats(float* dst_dev, int n, const float* values_host, sl_stream_t stream);
+/* Exponential moving average of n tensors in one launch (segland_amd/ema.py ModelEma: the averaged weights a run validates and saves):
+ *   ema = ema + (src - ema) * w   for every element, in float (the compiler may contract it to an FMA), no atomics,
+ * with w = one_minus_decay_dev[0] = 1 - decay read BY THE KERNEL from device memory, so the launch can sit in a captured HIP graph while the decay warms up step by step.
+ * table_dev: device array of n 32-byte records { float* ema; const float* src; long long numel; long long start; } with `start` the running count of 4096-element
+ * chunks (ceil(numel/4096)) of the preceding records and total_chunks their grand total.  ema and src need 4-byte alignment only (views at any element offset); 16-byte
+ * accesses are used where both are 16-byte aligned.  Two exact invariants, for a finite src - ema: w == 0 leaves ema bit for bit, and src == ema leaves ema bit for
+ * bit (an increment of +-0 is not added, so a negative-zero ema keeps its sign too).  src is never written. */
+int sl_ema_multi(const void* table_dev, int n, long long total_chunks, const float* one_minus_decay_dev, sl_stream_t stream);
 
 /* Many small strided fp32 copies in one launch (the zero-padded staging copies of weights / biases / BatchNorm vectors at the channel pitch, refreshed once per
  * optimizer step).  table_dev: n entries {float* dst; const float* src; int rows, cols, dst_pitch, pad; int64 start} (40 bytes): src is [rows][cols] contiguous,

@@ -129,6 +129,65 @@ extern "C" int sl_store_floats(float* dst_dev, int n, const float* values_host, 
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------
+// Exponential moving average of a model's weights (segland_amd/ema.py) over ALL tracked tensors in one launch:  ema = ema + (src - ema) * w,  w = 1 - decay read by the
+// KERNEL from device memory (a warm-up decay changes every step; the launch sits in the captured training step behind the optimizer kernel).  HBM-bound: 8 B read + 4 B
+// written per element.  Exact by construction: w == 0 makes the increment (src - ema) * 0 = +-0 and src == ema makes it +-0 * w = +-0 (finite values), and a zero increment
+// leaves ema as it is, bit for bit.
+// Chunk lookup and grid-stride loop as adamw_multi_kernel.  16-byte accesses only where BOTH base pointers are 16-byte aligned (a chunk starts 16 KiB into its tensor and
+// a group 16 B into its chunk, so a group is aligned exactly when the bases are: parameters may be views at 4-byte offsets, numel % 4 says nothing) and the whole float4
+// lies inside the tensor; a full chunk issues its eight loads before the first store.
+namespace {
+struct EmaEntry { float* ema; const float* src; long long numel; long long start; };
+static_assert(sizeof(EmaEntry) == 32, "table layout is part of the ABI");
+
+__device__ __forceinline__ float ema_step(float e, float s, float w) {
+  const float d = (s - e) * w;
+  return d == 0.f ? e : e + d;        // e + (+-0) == e in value; the select also keeps the sign bit of a negative-zero ema (-0 + +0 is +0)
+}
+__device__ __forceinline__ float4 ema_step4(float4 e, float4 s, float w) {
+  return make_float4(ema_step(e.x, s.x, w), ema_step(e.y, s.y, w), ema_step(e.z, s.z, w), ema_step(e.w, s.w, w));
+}
+
+__global__ __launch_bounds__(256) void ema_multi_kernel(const EmaEntry* __restrict__ tab, int n, long long total_chunks, const float* __restrict__ w_dev) {
+  const float w = w_dev[0];
+  for (long long chunk = blockIdx.x; chunk < total_chunks; chunk += gridDim.x) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].start <= chunk) lo = mid; else hi = mid - 1; }
+    const EmaEntry t = tab[lo];
+    const long long base = (chunk - t.start) * AD_CHUNK;
+    const bool vec = ((((size_t)t.ema) | ((size_t)t.src)) & 15) == 0;
+    if (vec && base + AD_CHUNK <= t.numel) {
+      float4* ev = (float4*)(t.ema + base);
+      const float4* sv = (const float4*)(t.src + base);
+      float4 E[4], S[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { E[u] = ev[u * 256 + threadIdx.x]; S[u] = sv[u * 256 + threadIdx.x]; }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) ev[u * 256 + threadIdx.x] = ema_step4(E[u], S[u], w);
+      continue;
+    }
+    for (int k = threadIdx.x * 4; k < AD_CHUNK; k += 1024) {
+      const long long e = base + k;
+      if (e >= t.numel) break;
+      if (vec && e + 4 <= t.numel) {
+        *(float4*)(t.ema + e) = ema_step4(*(const float4*)(t.ema + e), *(const float4*)(t.src + e), w);
+      } else {
+        const int cnt = (int)((t.numel - e) < 4 ? (t.numel - e) : 4);
+        for (int j = 0; j < cnt; ++j) t.ema[e + j] = ema_step(t.ema[e + j], t.src[e + j], w);
+      }
+    }
+  }
+}
+}  // namespace
+
+extern "C" int sl_ema_multi(const void* table_dev, int n, long long total_chunks, const float* one_minus_decay_dev, sl_stream_t stream) {
+  SL_REQUIRE(table_dev && one_minus_decay_dev, "ema_multi: null table or null one_minus_decay");
+  SL_REQUIRE(n > 0 && total_chunks > 0, "ema_multi: bad args (n and total_chunks must be positive)");
+  const int blocks = (int)(total_chunks < 8192 ? total_chunks : 8192);
+  return sl_launch("ema_multi_kernel", ema_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const EmaEntry*)table_dev, n, total_chunks, one_minus_decay_dev);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------
 // Many small strided fp32 copies in ONE launch: src [rows][cols] contiguous -> dst rows of pitch dst_pitch (the zero-padded staging copies of a model's
 // weights / biases / BatchNorm vectors at the channel pitch, re-filled once per optimizer step: ~55 launches of 4.4 us per Swin-T step otherwise).
 // table: device array of n entries {dst, src (float*), rows, cols, dst_pitch (int), pad, start (int64)} = 40 bytes; start = running count of 1024-element chunks.

@@ -84,6 +84,46 @@ def focal_gamma(v):
     return gamma
 
 
+def ema_decay(v):
+    """--ema-decay: 0 (off) or a decay in (0, 1); anything else -- NaN included -- is a ValueError that holds the value.  Not an argparse `type`: argparse would turn
+    the error into its own exit message."""
+    d = float(v)
+    if d != 0.0 and not 0.0 < d < 1.0:
+        raise ValueError('--ema-decay must be 0 (off) or lie strictly between 0 and 1 (got %r)' % (v,))
+    return d
+
+
+def make_ema(args, model, optimizer, log=False):
+    """The weight average of a run (segland_amd/ema.py) attached to its optimizer, or None when --ema-decay is 0.  `model`: the wrapped model, on its device and in the
+    mode it trains in (the tracked set is fixed here).  The update rides on the step of a segland_amd.optim optimizer; torch's optimizers have no such hook."""
+    d = ema_decay(getattr(args, 'ema_decay', 0.0))
+    if d == 0.0:
+        return None
+    if not hasattr(optimizer, 'attach_ema'):
+        raise ValueError('--ema-decay %g: the weight average is updated by a kernel behind the step of segland_amd.optim.AdamW / SGD (the GPU path); %s.%s has no '
+                         'such hook (no GPU?)' % (d, type(optimizer).__module__, type(optimizer).__name__))
+    from .ema import ModelEma
+    ema = ModelEma(model, d, warmup=getattr(args, 'ema_warmup', True))
+    optimizer.attach_ema(ema)
+    if log:
+        import logging
+        logging.getLogger('Segmentation').info('weight EMA: decay %g%s, %d tensors (%d values) averaged after every step; validation, best and *_ema checkpoints use the average',
+                                               d, ' with warm-up min(decay, (1 + t) / (10 + t))' if ema.warmup else '', len(ema.names),
+                                               sum(s.numel() for s in ema.shadows.values()))
+    return ema
+
+
+def averaged(ema):
+    """Context of a validation: the averaged weights stand in the model (ModelEma.applied), or nothing changes without an EMA."""
+    import contextlib
+    return ema.applied() if ema is not None else contextlib.nullcontext()
+
+
+def save_ema_checkpoint(ema, path):
+    """The averaged weights in the format of save_checkpoint (eval_base / eval_ft load the file unchanged)."""
+    torch.save(ema.model_state_dict(), path, _use_new_zipfile_serialization=False)
+
+
 def log_loss_options(args):
     """One line at start: the controls of the segmentation criterion (loss.get_loss reads the same fields); the Dice weight, the focal exponent and the mining controls only where they are on."""
     import logging
@@ -142,6 +182,10 @@ _COMMON = [
                                                                'is at most this threshold, in (0, 1], enter the segmentation loss of a head, but never fewer than '
                                                                '--ohem-min-kept of them; default 0: off.')),
     ('--ohem-min-kept', dict(type=ohem_min_kept, default=100000, help='pixels per GPU batch that hard-pixel mining keeps at least (the hardest ones); default 100000.')),
+    ('--ema-decay', dict(type=float, default=0.0, help='exponential moving average of the trainable weights and the training BatchNorm statistics, updated after every '
+                                                       'optimizer step; validation and best.pth use the average, epoch_N_ema.pth holds it next to the raw epoch_N.pth; '
+                                                       'strictly between 0 and 1 (0.999 is common); default 0: off.')),
+    ('--ema-warmup', dict(type=str2bool, default=True, help='the decay of step t is min(--ema-decay, (1 + t) / (10 + t)); default True.')),
     ('--fp16', dict(action='store_true', default=False, help='mixed precision: bf16 MFMA with fp32 accumulate on MI355X '
                                                                 '(the reference uses fp16 autocast + GradScaler); default is exact-fp32 MFMA.')),
 ]
@@ -258,21 +302,32 @@ def save_checkpoint(model, path):
     torch.save(model.state_dict(), path, _use_new_zipfile_serialization=False)
 
 
-def save_training_state(model, optimizer, path, epoch, best=0.0, best_epoch=0):
+def save_training_state(model, optimizer, path, epoch, best=0.0, best_epoch=0, ema=None):
     """Everything a true resume needs (the reference saves the bare model state_dict only, train_base.py:286-292, and parses
     `-c/--continue` without using it, engine.py:62-65): model weights in the reference's `module.`-prefixed format under 'state_dict' (so
-    utils.pyt_utils.load_model reads this file too), the optimizer state (torch.optim layout), the finished epoch and the best validation score."""
-    torch.save({'state_dict': model.state_dict(), 'optimizer': optimizer.state_dict(), 'epoch': int(epoch), 'best': float(best), 'best_epoch': int(best_epoch)},
-               path, _use_new_zipfile_serialization=False)
+    utils.pyt_utils.load_model reads this file too), the optimizer state (torch.optim layout), the finished epoch and the best validation score;
+    with a weight average (ema: segland_amd.ema.ModelEma) its state under 'ema'.  The weights under 'state_dict' are always the raw ones."""
+    state = {'state_dict': model.state_dict(), 'optimizer': optimizer.state_dict(), 'epoch': int(epoch), 'best': float(best), 'best_epoch': int(best_epoch)}
+    if ema is not None:
+        state['ema'] = ema.state_dict()
+    torch.save(state, path, _use_new_zipfile_serialization=False)
 
 
-def load_training_state(model, optimizer, path):
-    """-> (epoch to continue with, best, best_epoch).  `model` is the wrapped model (its keys carry `module.`)."""
+def load_training_state(model, optimizer, path, ema=None):
+    """-> (epoch to continue with, best, best_epoch).  `model` is the wrapped model (its keys carry `module.`).  ema: restored from the file's 'ema'; a file written
+    without one starts the average from the loaded weights."""
     ckpt = torch.load(path, map_location='cpu')
     if 'optimizer' not in ckpt or 'state_dict' not in ckpt:
         raise RuntimeError('%s is not a training state written by save_training_state (a bare state_dict restores weights only: use --restore-from)' % path)
     model.load_state_dict(ckpt['state_dict'], strict=True)
     optimizer.load_state_dict(ckpt['optimizer'])
+    if ema is not None:
+        if 'ema' in ckpt:
+            ema.load_state_dict(ckpt['ema'])
+        else:
+            import logging
+            logging.getLogger('Segmentation').warning('%s holds no weight average (written without --ema-decay): the average starts from the loaded weights', path)
+            ema.reset_to_model()
     from .functional import weights_changed
     weights_changed()                      # the derived GEMM-layout weight copies follow the loaded parameters
     return int(ckpt['epoch']), float(ckpt.get('best', 0.0)), int(ckpt.get('best_epoch', 0))

@@ -12,7 +12,8 @@ import torch.optim as optim
 from . import dataset as dataset_pkg
 from . import networks
 from . import graph_step
-from .drivers import adjust_learning_rate_poly, build_parser, checkpoint_or_none, compute_dtype, ft_batch_to_device, log_loss_options, resolve, save_checkpoint, validate
+from .drivers import (adjust_learning_rate_poly, averaged, build_parser, checkpoint_or_none, compute_dtype, ema_decay, ft_batch_to_device, log_loss_options, make_ema, resolve,
+                      save_checkpoint, save_ema_checkpoint, validate)
 from .engine import Engine
 from .loss import get_loss
 from .utils import pyt_utils as my_utils
@@ -66,6 +67,7 @@ def main(argv=None):
     parser = build_parser(ft=True)
     with Engine(custom_parser=parser, argv=argv) as engine:
         args = engine.args
+        ema_decay(args.ema_decay)                                       # a bad value stops the run here, before any data is touched
         logger = my_utils.prep_experiment(args) if engine.is_main else None
         input_size = tuple(map(int, args.input_size.split(',')))
         base_size = tuple(map(int, args.base_size.split(',')))
@@ -101,6 +103,9 @@ def main(argv=None):
             optimizer.zero_grad()
             model = engine.data_parallel(seg_model)
             loss_scaler = my_utils.NativeScalerWithGradNormCount()
+            if args.ema_decay != 0.0:
+                model.module.train_mode()                               # BatchNorm frozen: the weight average tracks novel_emb / classifier_n only
+            ema = make_ema(args, model, optimizer, log=engine.is_main)  # --ema-decay: updated behind every SGD step, eager or replayed; None when off
             graphed = None
             if not args.no_step_graph and graph_step.eligible(model, optimizer, engine.device, need_adamw=False):
                 in_graph = optimizer if hasattr(optimizer, 'graph_prepare') else None
@@ -130,17 +135,20 @@ def main(argv=None):
                 if args.update_base and (epoch + 1) % args.update_epoch == 0:
                     trainset.update_base_list()
                 if epoch % args.update_epoch == 0 or epoch == args.num_epoch - 1:
-                    inter, union = validate(model, test_loader, args.num_classes, args.ignore_label, engine.device)
-                    inter, union = engine.all_reduce_tensor(inter, norm=False), engine.all_reduce_tensor(union, norm=False)
-                    arr = (inter / union).cpu().numpy()
-                    b_iou, n_iou, t_iou = np.nanmean(arr[:args.base_classes + 1]), np.nanmean(arr[args.base_classes + 1:]), np.nanmean(arr)
-                    if engine.is_main:
-                        if t_iou >= best and b_iou - best_b > 0.001:
+                    with averaged(ema):                                 # the averaged weights are scored, and best_<seed>.pth holds what was scored
+                        inter, union = validate(model, test_loader, args.num_classes, args.ignore_label, engine.device)
+                        inter, union = engine.all_reduce_tensor(inter, norm=False), engine.all_reduce_tensor(union, norm=False)
+                        arr = (inter / union).cpu().numpy()
+                        b_iou, n_iou, t_iou = np.nanmean(arr[:args.base_classes + 1]), np.nanmean(arr[args.base_classes + 1:]), np.nanmean(arr)
+                        if engine.is_main and t_iou >= best and b_iou - best_b > 0.001:
                             save_checkpoint(model, osp.join(args.snapshot_dir, 'best_%d.pth' % seed))
                             best, best_b = t_iou, b_iou
+                    if engine.is_main:
                         logger.info('>>>>>>> Evaluation Results: meanIU: {:.2%}, baseIU: {:.2%}, novelIU: {:.2%}, best_IU: {:.2%} <<<<<<<'.format(t_iou, b_iou, n_iou, best))
                         if epoch % 50 == 0 or epoch == args.num_epoch - 1:
-                            save_checkpoint(model, osp.join(args.snapshot_dir, 'epoch_%d_%d.pth' % (epoch, seed)))
+                            save_checkpoint(model, osp.join(args.snapshot_dir, 'epoch_%d_%d.pth' % (epoch, seed)))      # the raw weights
+                            if ema is not None:
+                                save_ema_checkpoint(ema, osp.join(args.snapshot_dir, 'epoch_%d_%d_ema.pth' % (epoch, seed)))
 
 
 if __name__ == '__main__':

@@ -1358,6 +1358,11 @@ def store_floats(dst, values):
     check(_lib.lib().sl_store_floats(_p(dst), len(values), arr, _s()), 'store_floats')
 
 
+def ema_multi(table, n, total_chunks, w_dev):
+    """ema += (src - ema) * w_dev[0] over the n (ema, src, numel, chunk start) records of the device table in one launch (csrc/optim.hip sl_ema_multi)."""
+    check(_lib.lib().sl_ema_multi(_p(table), int(n), int(total_chunks), _p(w_dev), _s()), 'ema_multi')
+
+
 def confusion_matrix(pred_u8, target, K, ignore_index):
     """[K][K] int64 counts, rows = ground truth, columns = prediction, pixels with target == ignore_index dropped."""
     cm = torch.zeros((K, K), dtype=torch.int64, device=target.device)

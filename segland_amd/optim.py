@@ -23,6 +23,7 @@ class AdamW(torch.optim.Optimizer):
         self.repeat_next = 1          # drivers: set to 2 to fold the reference's second step() into the next one
         self._cap = None              # HIP-graph capture: launch slot -> persistent {pinned table, device table, device hyper-parameters}
         self._graph_plan = []         # [(slot, parameters, repeat)] of the captured step(), replayed by graph_prepare()
+        self._ema = None              # attach_ema(): a segland_amd.ema.ModelEma updated at the end of every step()
 
     @torch.no_grad()
     def step(self, closure=None, repeat=None, grad_scale=None):
@@ -85,8 +86,14 @@ class AdamW(torch.optim.Optimizer):
                 ent = self._tables[slot] = (bytes(rec), torch.frombuffer(bytearray(rec), dtype=torch.uint8).pin_memory().to(dev, non_blocking=True))
             bc = [(1.0 - b1 ** (step_t + r), math.sqrt(1.0 - b2 ** (step_t + r))) for r in (0, 1)]
             ops.adamw_multi(ent[1], n, total, b1, b2, eps, bc[0][0], bc[0][1], bc[1][0], bc[1][1], repeat, grad_scale=grad_scale)
+        if self._ema is not None:
+            self._ema.update()        # one update per call, also with repeat == 2: the folded double step is one iteration
         return loss
 
+    def attach_ema(self, ema):
+        """ema: a segland_amd.ema.ModelEma (or None to detach).  step() then ends with ema.update() -- one more launch behind the optimizer kernel, recorded into a captured
+        step like it -- and capture_begin() / graph_prepare() pass on to it, so the eager loop body and both step graphs average the weights with no edit of their own."""
+        self._ema = ema
 
     # ---- whole-step HIP graphs (segland_amd/graph_step.py) ---------------------------------------------------------------------------
     def capture_begin(self):
@@ -110,6 +117,8 @@ class AdamW(torch.optim.Optimizer):
         if dev is None:
             raise RuntimeError('segland_amd.optim.AdamW.capture_begin: no GPU parameters')
         self._cap, self._graph_plan = {}, []
+        if self._ema is not None:
+            self._ema.capture_begin()
         for slot in range(max(1, len(counts))):
             self._cap[slot] = dict(pinned=torch.zeros(64 * n, dtype=torch.uint8).pin_memory(), dev=torch.zeros(64 * n, dtype=torch.uint8, device=dev),
                                    hyp=torch.zeros(4 + 2 * len(self.param_groups), dtype=torch.float32, device=dev))
@@ -135,6 +144,8 @@ class AdamW(torch.optim.Optimizer):
                 rows = [[1.0 - b1 ** tt, math.sqrt(1.0 - b2 ** tt), 1.0 - b1 ** (tt + 1), math.sqrt(1.0 - b2 ** (tt + 1))] + tail for tt in range(t, t + n * repeat, repeat)]
                 tab = cap['tab'] = dict(sig=sig, t0=t, n=n, dev=torch.tensor(rows, dtype=torch.float32).pin_memory().to(cap['hyp'].device, non_blocking=True))
             cap['hyp'].copy_(tab['dev'][(t - tab['t0']) // repeat], non_blocking=True)
+        if self._ema is not None:
+            self._ema.graph_prepare()
 
 
 class SGD(torch.optim.Optimizer):
@@ -157,6 +168,11 @@ class SGD(torch.optim.Optimizer):
         self._table = None            # (record bytes, device table) of the last eager launch
         self._cap = None              # HIP-graph capture: persistent {pinned table, device table, device (lr, wd) vector}
         self._captured = False
+        self._ema = None              # attach_ema(): a segland_amd.ema.ModelEma updated at the end of every step()
+
+    def attach_ema(self, ema):
+        """As AdamW.attach_ema: step() ends with ema.update(), capture_begin() / graph_prepare() pass on to it."""
+        self._ema = ema
 
     def _records(self, capturing=False):
         """The per-parameter launch records.  (lr, weight_decay) are NOT in them: the kernel reads both from the device vector `hyper` (one entry pair per group), so the
@@ -207,6 +223,8 @@ class SGD(torch.optim.Optimizer):
             cap['dev'].copy_(cap['pinned'], non_blocking=True)
             ops.sgd_multi(cap['dev'], n, chunks, mom, hyper=cap['hyp'], grad_scale=grad_scale)
             self._captured = True
+            if self._ema is not None:
+                self._ema.update()
             return loss
         ent = self._table
         if ent is None or ent[0] != rec:
@@ -216,6 +234,8 @@ class SGD(torch.optim.Optimizer):
                                  torch.zeros(16, dtype=torch.float32, device=dev))
         ops.store_floats(ent[2], [v for g in self.param_groups for v in (g['lr'], g['weight_decay'])])      # kernel arguments of a one-block launch: no host -> device copy
         ops.sgd_multi(ent[1], n, chunks, mom, hyper=ent[2], grad_scale=grad_scale)
+        if self._ema is not None:
+            self._ema.update()
         return loss
 
     # ---- whole-step HIP graphs (segland_amd/graph_step.py): same protocol as AdamW
@@ -234,12 +254,16 @@ class SGD(torch.optim.Optimizer):
         self._cap = dict(pinned=torch.zeros(64 * n, dtype=torch.uint8).pin_memory(), dev=torch.zeros(64 * n, dtype=torch.uint8, device=dev),
                          hyp=torch.zeros(16, dtype=torch.float32, device=dev))
         self._captured = False
+        if self._ema is not None:
+            self._ema.capture_begin()
 
     def graph_prepare(self):
         """Before every replay of a graph that holds a captured step(): this iteration's (lr, weight_decay) per group -> the device vector the kernel reads, as
         kernel arguments of a one-block launch (no host -> device copy in front of the graph)."""
         if self._cap is not None and self._captured:
             ops.store_floats(self._cap['hyp'], [v for g in self.param_groups for v in (g['lr'], g['weight_decay'])])
+        if self._ema is not None:
+            self._ema.graph_prepare()
 
 
 _NORM_KERNEL = True      # test hook: clip_coefficient through csrc/optim.hip's gradient-norm kernels (False: torch's _foreach_norm chain)

@@ -15,7 +15,8 @@ from . import dataset as dataset_pkg
 from . import networks
 from . import bucket_step
 from . import graph_step
-from .drivers import adjust_learning_rate_poly, batch_to_device, build_parser, load_training_state, save_training_state, checkpoint_or_none, compute_dtype, log_loss_options, miou, resolve, save_checkpoint, validate
+from .drivers import (adjust_learning_rate_poly, averaged, batch_to_device, build_parser, load_training_state, save_training_state, checkpoint_or_none, compute_dtype, ema_decay,
+                      log_loss_options, make_ema, miou, resolve, save_checkpoint, save_ema_checkpoint, validate)
 from .engine import Engine
 from .loss import get_loss
 from .utils import pyt_utils as my_utils
@@ -38,6 +39,7 @@ def main(argv=None):
     parser = build_parser(ft=False)
     with Engine(custom_parser=parser, argv=argv) as engine:
         args = engine.args
+        ema_decay(args.ema_decay)                                       # a bad value stops the run here, before any data is touched
         logger = my_utils.prep_experiment(args) if engine.is_main else None
         if args.random_seed > 0:
             my_utils.set_seed(args.random_seed)
@@ -88,17 +90,7 @@ def main(argv=None):
             graphed = graph_step.GraphedTrainStep(train_iteration, model, optimizer, loss_scaler, double_step=not args.single_step)
             step = lambda m, o, s, img, mask, double_step: graphed(img, mask)      # noqa: E731  (one HIP graph launch per step)
 
-        best, best_epoch = 0.0, 0
-        if engine.continue_state_object:                                # -c / --continue FILE (engine.py:62-65 parses it; the reference never uses it)
-            args.start_epoch, best, best_epoch = load_training_state(model, optimizer, engine.continue_state_object)
-            if engine.is_main:
-                logger.info('continuing from %s: epoch %d, best mIoU %.4f', engine.continue_state_object, args.start_epoch, best)
-        it = args.start_epoch * len(train_loader)
-        for epoch in range(args.start_epoch, args.num_epoch):
-            if args.random_seed > 0:
-                my_utils.set_seed(args.random_seed + epoch)
-            if engine.distributed:
-                train_sampler.set_epoch(epoch)
+        def set_train_mode():
             if args.freeze_backbone:
                 # train_base.py:244 passes backbone_only=args.finetune; pspnet_pop.GFSS_Model.train_mode() takes no argument there (the
                 # reference crashes), swin_pop's does (swin_pop.py:220)
@@ -107,6 +99,23 @@ def main(argv=None):
                 tm(backbone_only=args.finetune) if 'backbone_only' in inspect.signature(tm).parameters else tm()
             else:
                 model.train()
+
+        if args.ema_decay != 0.0:
+            set_train_mode()                                            # the weight average tracks the BatchNorm layers that train
+        ema = make_ema(args, model, optimizer, log=engine.is_main)      # --ema-decay: updated behind every optimizer step, eager or replayed; None when off
+
+        best, best_epoch = 0.0, 0
+        if engine.continue_state_object:                                # -c / --continue FILE (engine.py:62-65 parses it; the reference never uses it)
+            args.start_epoch, best, best_epoch = load_training_state(model, optimizer, engine.continue_state_object, ema=ema)
+            if engine.is_main:
+                logger.info('continuing from %s: epoch %d, best mIoU %.4f', engine.continue_state_object, args.start_epoch, best)
+        it = args.start_epoch * len(train_loader)
+        for epoch in range(args.start_epoch, args.num_epoch):
+            if args.random_seed > 0:
+                my_utils.set_seed(args.random_seed + epoch)
+            if engine.distributed:
+                train_sampler.set_epoch(epoch)
+            set_train_mode()
             lr = adjust_learning_rate_poly(optimizer, args.learning_rate, epoch, args.num_epoch, args.power,
                                            split=-1 if args.freeze_backbone else 0)      # per EPOCH (train_base.py:248)
             for i, batch in enumerate(train_loader):
@@ -120,19 +129,22 @@ def main(argv=None):
                                     + ''.join(' %s=%.4f' % kv for kv in vals.items()))
             e1 = epoch + 1
             if engine.is_main and (e1 % 10 == 0 or e1 >= args.num_epoch):
-                save_checkpoint(model, osp.join(args.snapshot_dir, 'epoch_%d.pth' % e1))
+                save_checkpoint(model, osp.join(args.snapshot_dir, 'epoch_%d.pth' % e1))      # the raw weights: what a resume continues from
+                if ema is not None:
+                    save_ema_checkpoint(ema, osp.join(args.snapshot_dir, 'epoch_%d_ema.pth' % e1))
             if e1 > 35 and (e1 % 10 == 0 or epoch == args.num_epoch - 1):
-                inter, union = validate(model, test_loader, args.base_classes + 1, args.ignore_label, engine.device)
-                inter, union = engine.all_reduce_tensor(inter, norm=False), engine.all_reduce_tensor(union, norm=False)
-                m = miou(inter, union)
-                if engine.is_main:
-                    if m >= best:
+                with averaged(ema):                                     # the averaged weights are scored, and best.pth holds what was scored
+                    inter, union = validate(model, test_loader, args.base_classes + 1, args.ignore_label, engine.device)
+                    inter, union = engine.all_reduce_tensor(inter, norm=False), engine.all_reduce_tensor(union, norm=False)
+                    m = miou(inter, union)
+                    if engine.is_main and m >= best:
                         save_checkpoint(model, osp.join(args.snapshot_dir, 'best.pth'))
                         best, best_epoch = m, e1
+                if engine.is_main:
                     logger.info('>>>>>>> Evaluation Results: meanIU: {:.2%}, best_IU: {:.2%}, best_epoch: {} <<<<<<<'.format(m, best, best_epoch))
             if engine.is_main and (e1 % 10 == 0 or e1 >= args.num_epoch):
                 # AFTER this epoch's validation, so a resume from state_<e1>.pth carries the epoch's best / best_epoch
-                save_training_state(model, optimizer, osp.join(args.snapshot_dir, 'state_%d.pth' % e1), e1, best, best_epoch)
+                save_training_state(model, optimizer, osp.join(args.snapshot_dir, 'state_%d.pth' % e1), e1, best, best_epoch, ema=ema)
 
 if __name__ == '__main__':
     main()
