@@ -335,7 +335,7 @@ def test_window_attention_mfma_vs_valu(hip, Cn, heads, H, W, shift):
     """The bf16 MFMA window-attention kernels (one wavefront per window and head, probabilities kept in registers between the two MFMA stages)
     against the fp32-arithmetic VALU kernel on the same bf16 inputs, and both against a plain torch evaluation of swintransformer.py:118-149 +
     :208-238 (pad, roll, partition, mask) on those inputs."""
-    from oracle import swin_oracle as so
+    import swin_reference as sr
     from segland_amd import _lib
     from segland_amd import ops_swin as osw
     from segland_amd.ops_swin import pad_to
@@ -358,27 +358,10 @@ def test_window_attention_mfma_vs_valu(hip, Cn, heads, H, W, shift):
         finally:
             L.sl_debug_attn_valu(-1)
         res[name] = (out.float().cpu(), [t.float().cpu() for t in grads])
-    # torch evaluation on the bf16-rounded inputs (pad tokens carry the bf16-rounded bias, as the qkv GEMM would have stored it)
-    qr = qg.float().cpu()[..., :3 * Cn].requires_grad_(True)
-    br = bias.clone().requires_grad_(True)
-    rr = relb.clone().requires_grad_(True)
+    # plain torch evaluation (tests/swin_reference.py, float64) on the bf16-rounded inputs; pad tokens carry the bf16-rounded bias, as the qkv GEMM would have stored it
     Hp, Wp = -(-H // 7) * 7, -(-W // 7) * 7
-    brr = (br + (br.detach().to(torch.bfloat16).float() - br.detach())).view(1, 1, 1, -1).expand(B, Hp, Wp, 3 * Cn)
-    canvas = torch.cat([torch.cat([qr, brr[:, :H, W:]], 2), brr[:, H:]], 1) if (Hp > H or Wp > W) else qr
-    if shift:
-        canvas = torch.roll(canvas, (-shift, -shift), (1, 2))
-    xw = canvas.view(B, Hp // 7, 7, Wp // 7, 7, 3 * Cn).permute(0, 1, 3, 2, 4, 5).reshape(-1, 49, 3, heads, 32)
-    q, k, v = xw[:, :, 0].transpose(1, 2), xw[:, :, 1].transpose(1, 2), xw[:, :, 2].transpose(1, 2)
-    att = (q * 32 ** -0.5) @ k.transpose(-2, -1) + rr.unsqueeze(0)
-    if shift:
-        m = so.shift_mask(Hp, Wp, 7, 3)
-        att = (att.view(B, -1, heads, 49, 49) + m[None, :, None]).view(-1, heads, 49, 49)
-    o = (torch.softmax(att, -1) @ v).transpose(1, 2).reshape(B, Hp // 7, Wp // 7, 7, 7, Cn).permute(0, 1, 3, 2, 4, 5).reshape(B, Hp, Wp, Cn)
-    if shift:
-        o = torch.roll(o, (shift, shift), (1, 2))
-    o = o[:, :H, :W]
-    (o * dg.float().cpu()[..., :Cn]).sum().backward()
-    want = (o.detach(), [qr.grad, rr.grad, br.grad])
+    ref = sr.attention(qg.cpu(), sr.pad_bias_of(bias, torch.bfloat16), relb, dg.cpu(), Cn, heads, shift)
+    want = (ref['out'], [ref['dqkv'], ref['drel'], ref['dpad']])
     for name in ('valu', 'mfma'):
         out, (dqkv, drel, dpad) = res[name]
         tol = 1.5e-2 if name == 'valu' else 2.5e-2
