@@ -717,6 +717,31 @@ int sl_window_attention_bwd(const SlWinDesc* d, const void* qkv, const float* qk
 int sl_augment_batch(const void* tiles_dev, const int* flip_rot_dev, int B, int crop_h, int crop_w, const double* mean3_host,
                      const double* std3_host, int ignore_label, const uint8_t* label_lut_dev, float* out_img, long long* out_lbl,
                      sl_stream_t stream);
+/* The same preparation with a random rescale before the crop and a colour jitter behind it (neither is in the reference: this comment is the definition), one launch, no
+ * atomics, no synchronisation, no copy.  tiles_dev: device array of B 80-byte records
+ *   offset  0  const uint8_t* img    [rows][W][3]: source rows [row0, row0 + rows) of the tile
+ *           8  const uint8_t* lbl    [rows][W], or null
+ *          16  int H, W              the FULL tile size (<= 32768)
+ *          24  int row0, rows        the kernel indexes source row y as y - row0; every row a tap or a label of the crop reads must lie in the buffer
+ *          32  int Hs, Ws            size of the virtual rescaled tile, 1 <= Hs, Ws <= 16384
+ *          40  int h_off, w_off      crop origin in the RESCALED grid (>= 0)
+ *          48  int flip, rot_k       as flip_rot_dev of sl_augment_batch (which this entry does not take)
+ *          56  int jitter            0 or 1
+ *          60  float alpha, bias, sigma
+ *          72  int reserved[2]
+ * The sizes inside the table are the caller's to check (dataset/augment.py does).  Per output pixel (b, y, x):
+ *  1. (r, c) from (y, x) by undoing rot90 x k and then the flip, as sl_augment_batch.
+ *  2. Y = h_off + r, X = w_off + c.  Inside iff Y < Hs and X < Ws; outside is the padding (image 0 BEFORE normalisation, label ignore_label; no resampling, no jitter).
+ *  3. Image: bilinear, align_corners=False, coordinates in exact integers: n = max((2Y + 1) H - Hs, 0), d = 2 Hs, y0 = n / d, y1 = min(y0 + 1, H - 1),
+ *     fy = (float)((double)(n - y0 d) / d); x0, x1, fx likewise from X, W, Ws.  Per channel in float: a = v00 (1 - fx) + v01 fx, b = v10 (1 - fx) + v11 fx,
+ *     v = a (1 - fy) + b fy.  Hs == H gives y0 = Y, fy = 0 and v = v00 exactly: with Hs = H, Ws = W, jitter = 0 the output equals sl_augment_batch's bit for bit.
+ *  4. Label: nearest at the pixel centre, ly = min(((2Y + 1) H) / (2 Hs), H - 1), lx likewise, then label_lut_dev.
+ *  5. If jitter != 0, on R, G, B in [0, 255] (source channel order): v = clip(v alpha + bias, 0, 255) (the host passes bias = float(beta * 255));
+ *     g = 0.299f R + 0.587f G + 0.114f B, summed in that order; v = clip(g + (v - g) sigma, 0, 255).  jitter == 0 skips the stage.
+ *  6. The tail of sl_augment_batch: channel reversal, / 255.0f, the double subtract and divide of mean3 / std3, CHW float image, int64 label.
+ * SL_EINVAL before any launch for a null tiles_dev / mean3_host / std3_host / out_img and for B, crop_h or crop_w <= 0 (B <= 65535). */
+int sl_augment_batch_ex(const void* tiles_dev, int B, int crop_h, int crop_w, const double* mean3_host, const double* std3_host, int ignore_label,
+                        const uint8_t* label_lut_dev, float* out_img, long long* out_lbl, sl_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ import numpy as np
 from torch.utils import data
 
 from . import tiff
-from .augment import TileAugmenter, draw_train_params, remap_lut
+from .augment import TileAugmenter, augment_kwargs, draw_train_params, remap_lut, source_rows
 
 BASE_CLASSES, NOVEL_CLASSES, NUM_CLASSES = set(range(1, 8)), set(range(8, 12)), 11          # oem.py:13,32,34
 MEAN = STD = (0.5, 0.5, 0.5)                                                                   # oem.py:26-27
@@ -40,12 +40,15 @@ class _Raw(data.Dataset):
 
 
 class GFSSegTrain(_Raw):
-    """dataset/oem.py:11-76.  __getitem__ -> (image uint8 [H,W,3], label uint8 [H,W], (h_off, w_off, flip, k), id)."""
+    """dataset/oem.py:11-76.  __getitem__ -> (image uint8 [H,W,3], label uint8 [H,W], (h_off, w_off, flip, k), id).
+    augment: None, or {'scale': (lo, hi), 'jitter': (b, c, s)} -- random rescale before the crop / colour jitter (mode 'train' only; the draws are then augment.ExtDraw)."""
+    accepts_augment = True
 
     def __init__(self, root, list_path, fold, shot=1, mode='train', crop_size=(512, 512), ignore_label=255, base_size=(1024, 1024),
-                 resize_label=False, filter=False, seed=123):
+                 resize_label=False, filter=False, seed=123, augment=None):
         _decoder()
         assert mode in ('train', 'val_supp')
+        self.aug_kw = augment_kwargs(augment)
         self.root, self.crop_size, self.ignore_label, self.mode = root, tuple(crop_size), ignore_label, mode
         path = os.path.join(os.path.dirname(list_path), 'train.txt')
         if not os.path.exists(path):
@@ -61,7 +64,7 @@ class GFSSegTrain(_Raw):
         image = np.ascontiguousarray(np.rollaxis(_read(self.root, 'images', id_), 0, 3))
         label = np.ascontiguousarray(_read(self.root, 'labels', id_)[0])
         # mode 'val_supp': the same preparation with a centred crop (base_dataset.py:170-172); flip and rot90 are still drawn (oem.py:70-73)
-        return image, label, draw_train_params(label, self.crop_size, self.ignore_label, self.mode), id_
+        return image, label, draw_train_params(label, self.crop_size, self.ignore_label, self.mode, **self.aug_kw), id_
 
     def augmenter(self, device):
         return TileAugmenter(self.crop_size, MEAN, STD, self.ignore_label, lut=None, device=device)
@@ -100,7 +103,16 @@ class GFSSegVal(_Raw):
 
 def crop_rows(img, lab, prm, crop_h):
     """Only the rows the crop will read: a tile at least as tall as the crop is never padded vertically (base_dataset.py:88-104 pads tiles SMALLER than the crop),
-    so rows [h_off, h_off + crop_h) -- a contiguous slice of the row-major tile -- are all the preparation kernel looks at; the draw's h_off becomes 0."""
+    so rows [h_off, h_off + crop_h) -- a contiguous slice of the row-major tile -- are all the preparation kernel looks at; the draw's h_off becomes 0.
+    An extended draw (rescale / jitter, augment.ExtDraw) keeps its h_off, which lives in the rescaled grid: the rows its bilinear taps read (augment.source_rows) are kept and
+    the draw records where they start (row0) next to the full tile height."""
+    if len(prm) > 4:
+        if crop_h and prm.row0 == 0 and img.shape[0] == prm.H and 0 <= prm.h_off < prm.Hs:
+            row0, rows = source_rows(prm.H, prm.Hs, prm.h_off, crop_h)
+            img = img[row0:row0 + rows]
+            lab = None if lab is None else lab[row0:row0 + rows]
+            prm = prm._replace(row0=row0)
+        return img, lab, prm
     h_off, w_off, flip, k = prm
     if crop_h and img.shape[0] > crop_h and 0 <= h_off <= img.shape[0] - crop_h:
         img = img[h_off:h_off + crop_h]

@@ -18,7 +18,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from .augment import TileAugmenter, draw_train_params
+from .augment import TileAugmenter, augment_kwargs, draw_train_params
 from .oem import BASE_CLASSES, NOVEL_CLASSES, NUM_CLASSES, PackedTiles, _Raw, _decoder, _read, crop_rows
 
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)               # base_dataset.py:9 (not overridden by oem_ft.py)
@@ -64,9 +64,12 @@ pair_collate = PairCollate()
 class PairReader(_Raw):
     """The list logic and the pair rule, independent of how a tile is decoded (`read_image(id) -> uint8 [H,W,3]`, `read_label(id) -> uint8 [H,W]`)."""
     pair_tiles = True
+    accepts_augment = True        # augment={'scale': (lo, hi), 'jitter': (b, c, s)}: both tiles of a pair get their own rescale / jitter draws
+    aug_kw = {}
     collate_fn = staticmethod(pair_collate)
 
-    def _init_lists(self, list_path, shot, mode, crop_size, ignore_label, seed, filter, use_base):
+    def _init_lists(self, list_path, shot, mode, crop_size, ignore_label, seed, filter, use_base, augment=None):
+        self.aug_kw = augment_kwargs(augment)
         if mode == 'val_supp':
             raise RuntimeError("oem_ft.GFSSegTrain(mode='val_supp') rotates support tiles with cv2.warpAffine (oem_ft.py:247, base_dataset.py:117-132); "
                                'it is not on the ft_pop path and is not built')
@@ -131,8 +134,8 @@ class PairReader(_Raw):
         image, label = self.read_image(id_), self.read_label(id_)
         label = np.where(label == 0, np.uint8(self.ignore_label), label).astype(np.uint8)       # oem_ft.py:197, before the crop draw looks at the labels
         image_b, label_b = self.read_image(id_b), self.read_label(id_b)
-        prm = draw_train_params(label, self.crop_size, self.ignore_label)
-        prm_b = draw_train_params(label_b, self.crop_size, self.ignore_label)
+        prm = draw_train_params(label, self.crop_size, self.ignore_label, **self.aug_kw)
+        prm_b = draw_train_params(label_b, self.crop_size, self.ignore_label, **self.aug_kw)
         return ((image, label), (image_b, label_b)), (prm, prm_b), id_
 
     def augmenter(self, device):
@@ -143,10 +146,10 @@ class GFSSegTrain(PairReader):
     num_classes = NUM_CLASSES
 
     def __init__(self, root, list_path, fold, shot=1, mode='train', crop_size=(512, 512), ignore_label=255, base_size=(1024, 1024),
-                 resize_label=False, seed=123, filter=False, use_base=True):
+                 resize_label=False, seed=123, filter=False, use_base=True, augment=None):
         _decoder()
         self.root = root
-        self._init_lists(list_path, shot, mode, crop_size, ignore_label, seed, filter, use_base)
+        self._init_lists(list_path, shot, mode, crop_size, ignore_label, seed, filter, use_base, augment)
 
     def read_image(self, id_):
         return np.ascontiguousarray(np.rollaxis(_read(self.root, 'images', id_), 0, 3))

@@ -4,7 +4,7 @@ dataset's own class numbering, larger than the crop, with the reference's random
 import numpy as np
 import torch
 
-from .augment import TileAugmenter, draw_train_params, remap_lut
+from .augment import TileAugmenter, augment_kwargs, draw_train_params, remap_lut
 from .oem import MEAN, STD, RawCollate, _Raw, raw_collate  # noqa: F401
 
 
@@ -28,15 +28,18 @@ class _Base(_Raw):
 
 
 class GFSSegTrain(_Base):
+    accepts_augment = True
+
     def __init__(self, root=None, list_path=None, fold=0, shot=1, crop_size=(512, 512), base_size=(512, 512), mode='train', filter=False,
-                 length=64, seed=0, **kw):
+                 length=64, seed=0, augment=None, **kw):
         super().__init__(length, (crop_size[0] + 96, crop_size[1] + 64), seed)
         self.crop_size = tuple(crop_size)
+        self.aug_kw = augment_kwargs(augment)
         self.collate_fn = RawCollate(self.crop_size[0])
 
     def __getitem__(self, i):
         img, lab = self._tile(i, 8)
-        return img, lab, draw_train_params(lab, self.crop_size, self.ignore_label), i
+        return img, lab, draw_train_params(lab, self.crop_size, self.ignore_label, **self.aug_kw), i
 
     def augmenter(self, device):
         return TileAugmenter(self.crop_size, MEAN, STD, self.ignore_label, device=device)

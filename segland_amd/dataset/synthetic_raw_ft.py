@@ -13,7 +13,7 @@ class GFSSegTrain(PairReader):
     num_classes = 11
 
     def __init__(self, root=None, list_path=None, fold=0, shot=5, crop_size=(512, 512), base_size=(512, 512), mode='train', seed=123, filter=False,
-                 length=24, tile=None, **kw):
+                 length=24, tile=None, augment=None, **kw):
         self.tile = tuple(tile) if tile else (crop_size[0] + 96, crop_size[1] + 64)
         self.seed = seed
         ids = ['s%03d' % k for k in range(length)]
@@ -24,7 +24,7 @@ class GFSSegTrain(PairReader):
         open(lst, 'w').write(''.join(i + '\n' for i in ids))
         novel = [i for i in ids if self._index[i] % 3 == 2]
         open(os.path.join(d, 'list', 'all_%sshot_seed%s.txt' % (shot, seed)), 'w').write(''.join(i + '\n' for i in novel[:4 * shot]))
-        self._init_lists(lst, shot, mode, crop_size, 255, seed, False, True)
+        self._init_lists(lst, shot, mode, crop_size, 255, seed, False, True, augment)
 
     def _coarse(self, id_):
         k = self._index[id_]

@@ -64,10 +64,10 @@ class GFSSegTrain(oem.GFSSegTrain):
     """dataset/oem.py:11-76 of the reference on synthetic TIFF files (the driver's --data-dir / --train-list are ignored unless they point at such a directory)."""
 
     def __init__(self, root=None, list_path=None, fold=0, shot=5, mode='train', crop_size=(512, 512), ignore_label=255, base_size=(1024, 1024),
-                 resize_label=False, filter=False, seed=123, length=24, compression=None, **kw):
+                 resize_label=False, filter=False, seed=123, length=24, compression=None, augment=None, **kw):
         root = _root(root, crop_size, length, seed, shot, compression)
         super().__init__(root, os.path.join(root, 'list', 'train.txt'), fold, shot=shot, mode=mode, crop_size=crop_size, ignore_label=ignore_label,
-                         base_size=base_size, resize_label=resize_label, filter=filter, seed=seed)
+                         base_size=base_size, resize_label=resize_label, filter=filter, seed=seed, augment=augment)
 
 
 class GFSSegVal(oem.GFSSegVal):

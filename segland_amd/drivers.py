@@ -84,6 +84,59 @@ def focal_gamma(v):
     return gamma
 
 
+def aug_scale(v):
+    """--aug-scale: '' -> () (off); 'LO,HI' -> (lo, hi) with 0 < LO <= HI <= 4: the range the random rescale before the crop is drawn from."""
+    if isinstance(v, (tuple, list)):
+        return tuple(float(x) for x in v)
+    if not v.strip():
+        return ()
+    try:
+        r = tuple(float(x) for x in v.split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError('two comma-separated floats LO,HI expected (got %r)' % (v,))
+    if len(r) != 2 or not (0.0 < r[0] <= r[1] <= 4.0):
+        raise argparse.ArgumentTypeError('the rescale range LO,HI must satisfy 0 < LO <= HI <= 4 (got %r)' % (v,))
+    return r
+
+
+def aug_jitter(v):
+    """--aug-jitter: '' -> () (off); 'B,C,S' -> the brightness, contrast and saturation amplitudes, each in [0, 1)."""
+    if isinstance(v, (tuple, list)):
+        return tuple(float(x) for x in v)
+    if not v.strip():
+        return ()
+    try:
+        a = tuple(float(x) for x in v.split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError('three comma-separated floats B,C,S expected (got %r)' % (v,))
+    if len(a) != 3 or not all(0.0 <= x < 1.0 for x in a):
+        raise argparse.ArgumentTypeError('the jitter amplitudes B,C,S (brightness, contrast, saturation) must each lie in [0, 1) (got %r)' % (v,))
+    return a
+
+
+def augment_option(args, reader, dataset):
+    """The `augment=` keyword of a training reader from --aug-scale / --aug-jitter: {} when both are off (the reader is called as it always was), else
+    {'augment': {'scale': ..., 'jitter': ...}}.  A reader that does not hand raw tiles to the GPU preparation kernel cannot take the option: a ValueError names it and the flag."""
+    scale, jitter = aug_scale(getattr(args, 'aug_scale', ()) or ()), aug_jitter(getattr(args, 'aug_jitter', ()) or ())
+    if not scale and not jitter:
+        return {}
+    if not getattr(reader, 'accepts_augment', False):
+        flags = ' / '.join(f for f, on in (('--aug-scale', scale), ('--aug-jitter', jitter)) if on)
+        raise ValueError("dataset '%s' cannot take %s: its training reader does not emit raw tiles for the GPU preparation kernel (csrc/augment.hip); "
+                         'use oem, synthetic_tiff or synthetic_raw' % (dataset, flags))
+    return {'augment': {'scale': scale or None, 'jitter': jitter or None}}
+
+
+def log_augment_options(args):
+    """One line at start, only when --aug-scale or --aug-jitter is on."""
+    scale, jitter = aug_scale(getattr(args, 'aug_scale', ()) or ()), aug_jitter(getattr(args, 'aug_jitter', ()) or ())
+    if scale or jitter:
+        import logging
+        logging.getLogger('Segmentation').info('tile augmentation in the preparation kernel:' + (' random rescale %g..%g before the crop' % scale if scale else '')
+                                               + (',' if scale and jitter else '')
+                                               + (' colour jitter: brightness %g, contrast %g, saturation %g' % jitter if jitter else ''))
+
+
 def ema_decay(v):
     """--ema-decay: 0 (off) or a decay in (0, 1); anything else -- NaN included -- is a ValueError that holds the value.  Not an argparse `type`: argparse would turn
     the error into its own exit message."""
@@ -182,6 +235,10 @@ _COMMON = [
                                                                'is at most this threshold, in (0, 1], enter the segmentation loss of a head, but never fewer than '
                                                                '--ohem-min-kept of them; default 0: off.')),
     ('--ohem-min-kept', dict(type=ohem_min_kept, default=100000, help='pixels per GPU batch that hard-pixel mining keeps at least (the hardest ones); default 100000.')),
+    ('--aug-scale', dict(type=aug_scale, default='', help='LO,HI: every training tile is rescaled (bilinear; labels nearest) by a random factor from this range before the crop '
+                                                          'is taken, inside the tile preparation kernel; 0 < LO <= HI <= 4 (PSPNet: 0.5,2.0); raw-tile datasets only; default: off.')),
+    ('--aug-jitter', dict(type=aug_jitter, default='', help='B,C,S: random brightness, contrast and saturation of every training crop, inside the tile preparation kernel; '
+                                                            'the amplitudes, each in [0, 1) (0.2,0.2,0.2 is common); raw-tile datasets only; default: off.')),
     ('--ema-decay', dict(type=float, default=0.0, help='exponential moving average of the trainable weights and the training BatchNorm statistics, updated after every '
                                                        'optimizer step; validation and best.pth use the average, epoch_N_ema.pth holds it next to the raw epoch_N.pth; '
                                                        'strictly between 0 and 1 (0.999 is common); default 0: off.')),

@@ -12,7 +12,7 @@ import torch.optim as optim
 from . import dataset as dataset_pkg
 from . import networks
 from . import graph_step
-from .drivers import (adjust_learning_rate_poly, averaged, build_parser, checkpoint_or_none, compute_dtype, ema_decay, ft_batch_to_device, log_loss_options, make_ema, resolve,
+from .drivers import (adjust_learning_rate_poly, augment_option, averaged, build_parser, checkpoint_or_none, compute_dtype, ema_decay, ft_batch_to_device, log_augment_options, log_loss_options, make_ema, resolve,
                       save_checkpoint, save_ema_checkpoint, validate)
 from .engine import Engine
 from .loss import get_loss
@@ -73,11 +73,13 @@ def main(argv=None):
         base_size = tuple(map(int, args.base_size.split(',')))
         if engine.is_main:
             log_loss_options(args)
+            log_augment_options(args)
         for seed in map(int, args.random_seed.split(',')):
             my_utils.set_seed(seed)
             ds_ft, ds = resolve(dataset_pkg, args.dataset + '_ft'), resolve(dataset_pkg, args.dataset)
             trainset = ds_ft.GFSSegTrain(args.data_dir, args.train_list, args.fold, args.shot, crop_size=input_size, base_size=base_size,
-                                         mode='train', seed=seed, filter=args.filter_novel)
+                                         mode='train', seed=seed, filter=args.filter_novel,
+                                         **augment_option(args, ds_ft.GFSSegTrain, args.dataset + '_ft'))      # --aug-scale / --aug-jitter: training reader only
             train_loader, train_sampler = engine.get_train_loader(trainset)
             args.ignore_label, args.base_classes = trainset.ignore_label, len(trainset.base_classes)
             testset = ds.GFSSegVal(args.data_dir, args.val_list, args.fold, base_size=base_size, resize_label=True, use_novel=True, use_base=True)

@@ -15,8 +15,8 @@ from . import dataset as dataset_pkg
 from . import networks
 from . import bucket_step
 from . import graph_step
-from .drivers import (adjust_learning_rate_poly, averaged, batch_to_device, build_parser, load_training_state, save_training_state, checkpoint_or_none, compute_dtype, ema_decay,
-                      log_loss_options, make_ema, miou, resolve, save_checkpoint, save_ema_checkpoint, validate)
+from .drivers import (adjust_learning_rate_poly, augment_option, averaged, batch_to_device, build_parser, load_training_state, save_training_state, checkpoint_or_none, compute_dtype, ema_decay,
+                      log_augment_options, log_loss_options, make_ema, miou, resolve, save_checkpoint, save_ema_checkpoint, validate)
 from .engine import Engine
 from .loss import get_loss
 from .utils import pyt_utils as my_utils
@@ -47,7 +47,8 @@ def main(argv=None):
         args.base_size = tuple(map(int, args.base_size.split(',')))
         ds = resolve(dataset_pkg, args.dataset)
         trainset = ds.GFSSegTrain(args.data_dir, args.train_list, args.fold, args.shot, crop_size=args.input_size,
-                                  base_size=args.base_size, mode='train', filter=args.filter_novel)
+                                  base_size=args.base_size, mode='train', filter=args.filter_novel,
+                                  **augment_option(args, ds.GFSSegTrain, args.dataset))      # --aug-scale / --aug-jitter: training reader only
         train_loader, train_sampler = engine.get_train_loader(trainset)
         args.ignore_label, args.num_classes = trainset.ignore_label, trainset.num_classes
         args.base_classes = len(trainset.base_classes)
@@ -59,6 +60,7 @@ def main(argv=None):
         criterion = get_loss(args)
         if engine.is_main:
             log_loss_options(args)
+            log_augment_options(args)
         norm =nn.SyncBatchNorm if engine.distributed else nn.BatchNorm2d       # parameter holders; statistics are per GPU
         assert args.os in (8, 16, 32)
         model_cls = getattr(networks, args.model).GFSS_Model                    # `networks.<model>.GFSS_Model`

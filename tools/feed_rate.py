@@ -12,7 +12,10 @@ decode-free synthetic generator of rounds 2-3 (a ~30 ms torch.randint per tile).
 (35 at the 5-shot setting, ft_oem.sh runs batch size 1); with --batch 16 that is TWO batches per epoch, each made by one worker -- the flat 121 pairs/s of round 3
 whatever the worker count.  The steady state is measured with --shot large enough for many batches per epoch; --batch 1 is the driver's own setting.
 
-    python tools/feed_rate.py [--workers 16] [--batch 16] [--batches 40] [--pairs] [--shot 40] [--source tiff|randint] [--compression tiff_lzw]
+--aug-scale LO,HI / --aug-jitter B,C,S: the training drivers' flags -- the readers draw a rescale / a colour jitter per tile and the batch goes through sl_augment_batch_ex
+(a rescaled crop reads ch / s + 2 source rows instead of ch: the collate cuts the tile down to those).
+
+    python tools/feed_rate.py [--workers 16] [--batch 16] [--batches 40] [--pairs] [--shot 40] [--source tiff|randint] [--compression tiff_lzw] [--aug-scale 0.5,2.0] [--aug-jitter 0.2,0.2,0.2]
 """
 import argparse
 import os
@@ -38,7 +41,11 @@ def main():
     p.add_argument('--compression', default=None, help='tiff_lzw | tiff_adobe_deflate | packbits (default: uncompressed)')
     p.add_argument('--files', type=int, default=96, help='tiff: tiles written to disk')
     p.add_argument('--repeat', type=int, default=8, help='tiff, base tiles: how often train.txt lists each file (epoch = files x repeat samples: a 96-sample epoch is six batches of 16,\n                   each made by ONE worker -- the loader then measures epoch restarts, not the feed)')
+    from segland_amd.drivers import aug_jitter, aug_scale
+    p.add_argument('--aug-scale', type=aug_scale, default='')
+    p.add_argument('--aug-jitter', type=aug_jitter, default='')
     a = p.parse_args()
+    augment = {'scale': a.aug_scale or None, 'jitter': a.aug_jitter or None} if (a.aug_scale or a.aug_jitter) else None
     dev = torch.device('cuda', 0)
     decode = 'torch.randint stand-in'
     if a.source == 'tiff':
@@ -56,20 +63,20 @@ def main():
         decode = '%s decode of %s TIFF files (%.1f MB per image file, %.1f ms per tile = image + label in one process)' % (
             tiff.backend(), a.compression or 'uncompressed', nbytes / (a.files + 1) / 1e6, (time.perf_counter() - t0) / 8 * 1e3)
         if a.pairs:
-            ds = oem_ft.GFSSegTrain(root, lst, 0, shot=a.shot, crop_size=(a.crop, a.crop), seed=123)
+            ds = oem_ft.GFSSegTrain(root, lst, 0, shot=a.shot, crop_size=(a.crop, a.crop), seed=123, augment=augment)
             collate, per_sample = ds.collate_fn, 2
         else:
-            ds = oem.GFSSegTrain(root, lst, 0, crop_size=(a.crop, a.crop))
+            ds = oem.GFSSegTrain(root, lst, 0, crop_size=(a.crop, a.crop), augment=augment)
             collate, per_sample = ds.collate_fn, 1
     elif a.pairs:
         from segland_amd.dataset import synthetic_raw_ft as ds_mod
         from segland_amd.dataset.oem_ft import pair_collate as collate
-        ds = ds_mod.GFSSegTrain(shot=a.shot, crop_size=(a.crop, a.crop), tile=(a.tile, a.tile), length=40)
+        ds = ds_mod.GFSSegTrain(shot=a.shot, crop_size=(a.crop, a.crop), tile=(a.tile, a.tile), length=40, augment=augment)
         collate, per_sample = ds.collate_fn, 2
     else:
         from segland_amd.dataset import synthetic_raw as ds_mod
         from segland_amd.dataset.oem import raw_collate as collate
-        ds = ds_mod.GFSSegTrain(crop_size=(a.crop, a.crop), length=a.batch * a.batches)
+        ds = ds_mod.GFSSegTrain(crop_size=(a.crop, a.crop), length=a.batch * a.batches, augment=augment)
         ds.tile = (a.tile, a.tile)
         collate, per_sample = ds.collate_fn, 1
     aug = ds.augmenter(dev)
@@ -105,8 +112,8 @@ def main():
     feed_rate = tiles / (time.perf_counter() - t0)
     cpus = len(os.sched_getaffinity(0))
     unit = 'pairs/s' if a.pairs else 'tiles/s'
-    print('feed_rate: %s, raw %dx%d -> crop %dx%d, batch %d, %d samples per epoch, %s: GPU stage alone (H2D + sl_augment_batch) %.0f %s; whole feed with %d workers on %d host cores %.0f %s'
-          % ('fine-tune pairs' if a.pairs else 'base tiles', a.tile, a.tile, a.crop, a.crop, a.batch, len(ds), decode, gpu_rate / per_sample, unit, a.workers, cpus, feed_rate / per_sample, unit))
+    print('feed_rate: %s%s, raw %dx%d -> crop %dx%d, batch %d, %d samples per epoch, %s: GPU stage alone (H2D + sl_augment_batch%s) %.0f %s; whole feed with %d workers on %d host cores %.0f %s'
+          % ('fine-tune pairs' if a.pairs else 'base tiles', (' with rescale %s jitter %s' % (a.aug_scale or 'off', a.aug_jitter or 'off')) if augment else '', a.tile, a.tile, a.crop, a.crop, a.batch, len(ds), decode, '_ex' if augment else '', gpu_rate / per_sample, unit, a.workers, cpus, feed_rate / per_sample, unit))
     if a.source == 'tiff':
         import shutil
         shutil.rmtree(root, ignore_errors=True)
