@@ -516,6 +516,42 @@ int sl_ohem_threshold(const float* prob, long long n_pix, float thresh, long lon
                       sl_stream_t stream);
 int sl_ohem_mine(const float* prob, const int64_t* target, const float* theta, const long long* counts, long long n_pix, int ignore_index, int64_t* mined,
                  sl_stream_t stream);
+/* Lovasz-softmax term (Berman et al.: the convex surrogate of the Jaccard index itself) beside the criteria above, WITHOUT a sort: the Lovasz extension does not
+ * depend on the order inside ties, so with every class's errors quantised to NB = sl_lovasz_bins() = 1024 bins the loss and a valid subgradient follow from two integer
+ * histograms per class and one scan over the bins.  Per call (per head; under DDP per rank), over the valid pixels of the whole batch (label != ignore_index and inside
+ * [0, K)), for class c:
+ *   p_ic = softmax of the bilinear (align_corners=True) logits (m = max_k v_k, e_k = expf(v_k - m), s = sum_k e_k in index order, p_k = e_k / s);
+ *   fg_ic = [t_i == c];  e_ic = |fg_ic - p_ic|: p_ic for c != t_i, and u = (sum_{k != t} e_k) / s for c == t_i (the focal form's 1 - p_t without cancellation);
+ *   bin j = min(floor(e * NB), NB - 1);  F_c[j], Bk_c[j] = the foreground / background counts of the bin (unsigned 32-bit: B * H * W < 2^32, else SL_EINVAL);
+ *   walking the bins from j = NB - 1 down to 0 with running sums f, b (bin j included) and G_c = sum_j F_c[j]:
+ *     J_c(j) = 1 - (G_c - f) / (G_c + b),   dJ_c[j] = J_c(j) - J_c(j + 1),   J_c(NB) = 0;
+ *   class c is PRESENT if G_c > 0;  n_present = number of present classes;
+ *   loss L = (1 / n_present) sum_{c present} sum_j ((j + 1/2) / NB) dJ_c[j];  L = 0 if n_present == 0;
+ *   table tab[c][j] = dJ_c[j] / ((F_c[j] + Bk_c[j]) n_present): 0 for an empty bin, the whole row 0 for an absent class;
+ *   gradient of a valid pixel: q_c = (fg_ic ? -1 : +1) tab[c][bin(e_ic)],  dL / dv_k = p_k (q_k - sum_c p_c q_c); the table is a constant for the gradient.  This is the
+ *   bin-averaged subgradient of the Lovasz extension at the quantised errors.
+ * The Lovasz extension of a class's Jaccard loss is 1-Lipschitz in the sup norm (it is max <w, e> over the base polytope, w >= 0, sum w = J(V) <= 1), so
+ * |L - L of the exactly sorted errors| <= 1 / (2 NB) from the bin centres.  No class weights on this term (classes = "present") and no per-image variant.
+ * Everything stays on the device (no read-back: capturable; n_present is inside the table); integer LDS and global atomics only: two runs give the same bits.
+ * sl_lovasz_workspace: bytes of the workspace for K classes (0 for K outside [1, 33]): unsigned hist[K][NB][2] = (F, Bk), then double part[K][2] = (the class's
+ *   sum_j ((j + 1/2) / NB) dJ_c[j], 1.0 if present else 0.0).
+ * sl_upsample_lovasz_hist: zeroes the workspace and fills hist.  1 <= K <= 33 (the message names the limit), ws_bytes >= sl_lovasz_workspace(K), no NULL buffer.
+ * sl_lovasz_scan: hist -> table[K][NB] (float), part, and out[2] = (L, n_present), the present classes added in index order, in double.
+ * sl_upsample_lovasz_bwd: ONE launch for all terms: dlogits = transposed bilinear weights applied to
+ *     gscale[0] / loss_out[1] * (cross-entropy gradient of the pixel) + gscale[1] * (Dice form) + gscale[2] * p_k (q_k - sum_c p_c q_c)
+ *   with the cross-entropy part plain, weighted / smoothed (class_weight may be NULL: weights of one) and focal-modulated for gamma >= 1 (gamma == 0: not), and the
+ *   Dice form only where coef != NULL; loss_out and coef are what the existing forward + finalize of that form produced (loss_and_count, or loss3 and coef).
+ *   gscale: 3 floats on the device (the Dice one is not read without coef).  The three kernel routes (and the sl_debug_ce_tiled hook) of sl_upsample_ce_bwd; the table is
+ *   read from global memory; the channel-sliced kernel keeps two words more per footprint pixel (sum_c p_c q_c, u) under the same 150 KiB plan.  With no valid pixel
+ *   the gradient is exactly 0. */
+int sl_lovasz_bins(void);
+size_t sl_lovasz_workspace(int K);
+int sl_upsample_lovasz_hist(const float* logits, const int64_t* target, int B, int K, int h, int w, int H, int W, int ignore_index, void* workspace,
+                            size_t ws_bytes, sl_stream_t stream);
+int sl_lovasz_scan(const void* workspace, int K, float* out, float* table, sl_stream_t stream);
+int sl_upsample_lovasz_bwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing, float gamma, const float* loss_out,
+                           const float* coef, const float* table, const float* gscale, int B, int K, int h, int w, int H, int W, int ignore_index,
+                           float* dlogits, sl_stream_t stream);
 /* pspnet_pop.py:221-231: argmax of the upsampled (align_corners=True) [K2][h][w] logits of tile b, ids > 0 shifted
  * by n_base, written into mask[b] where mask == 0 (in place, int64). */
 int sl_pseudo_label(const float* logits, int K2, int h, int w, int64_t* mask, int B, int H, int W, int n_base,

@@ -49,23 +49,49 @@ template <bool FC> struct CeF {};
 template <> struct CeF<true> { float gamma; };
 __device__ __forceinline__ float focal_modu(float u, float gamma) { return u > 0.f ? exp2f((gamma - 1.f) * log2f(u)) : 0.f; }
 
+// Lovasz-softmax term (Berman et al.) of the backward kernels, <LV = true>; the contract is in include/segland_hip.h.  The forward (upsample_lovasz_hist_kernel,
+// lovasz_scan_kernel below) quantises every class's errors e_c = |[t == c] - p_c| to LOV_NB bins and leaves the table tab[c][bin] = dJ_c[bin] / (count of the bin *
+// present classes); for a valid pixel q_c = ([t == c] ? -1 : +1) * tab[c][bin(e_c)], a constant for the gradient, and
+//   d lovasz / d v_k = p_k (q_k - sum_c p_c q_c),
+// the Dice term's form, added to the pixel's gradient BEFORE the bilinear scatter with the scale f2 = gscale[2].  The label's own error is u = (sum_{k != t} e_k) / s, the
+// focal form's cancellation-free 1 - p_t.  The table is read from global memory (K * LOV_NB floats, L2-resident): no LDS buffer.
+// CeL<false> is empty and every statement of the term sits under `if constexpr (LV)`: the <LV = false> instantiations are the kernels as they were.
+constexpr int LOV_NB = 1024;
+template <bool LV> struct CeL {};
+template <> struct CeL<true> { const float* tab; };                   // [K][LOV_NB] on the device
+__device__ __forceinline__ int lov_bin(float e) { const int j = (int)(e * (float)LOV_NB); return j < 0 ? 0 : (j < LOV_NB - 1 ? j : LOV_NB - 1); }
+__device__ __forceinline__ float lov_q(const float* __restrict__ tab, int k, int t, float p, float u) {
+  return k == t ? -tab[k * LOV_NB + lov_bin(u)] : tab[k * LOV_NB + lov_bin(p)];
+}
+
 // The gradient of one valid pixel of label t with respect to its interpolated logits, in the three forms above: built once per pixel, at(k) once per channel.  wt = w_t,
 // wsum = sum_j w_j, p = softmax_k, w = w_k, (qa, qg) = coef[b][k], sq = sum_c p_c q_c.  <false, false> is p - [k == t] and nothing else; without DC the caller applies
 // the scale gscale[0] / denominator after the bilinear scatter, with DC f0 and f1 are inside.  A new loss term goes here and into ce_pixel, nowhere else.
 // FC: (mod, beta) of the pixel from ce_pixel; the cross-entropy form becomes mod * form + beta * (p - [k == t]), before f0 as before the scatter.
-template <bool WT, bool DC, bool FC = false>
-struct PixGrad {
+// LV: f2 = gscale[2], sl = sum_c p_c q_c of the Lovasz q, lq = q_k; the scales are inside as with DC (f0 too, with or without DC).
+template <bool LV> struct PixLov {};
+template <> struct PixLov<true> { float f2, sl; };
+template <bool WT, bool DC, bool FC = false, bool LV = false>
+struct PixGrad : PixLov<LV> {
   int t; float hit, ct, epsk, f0, f1, sq, mod, beta;
   __device__ __forceinline__ PixGrad(int t_, float wt, const CeW<WT>& cw, float wsum, float f0_, float f1_, float sq_, float mod_ = 1.f, float beta_ = 0.f)
       : t(t_), hit(1.f), ct(1.f), epsk(0.f), f0(f0_), f1(f1_), sq(sq_), mod(mod_), beta(beta_) {
     if constexpr (WT) { hit = cw.keep * wt; ct = hit + cw.epsk * wsum; epsk = cw.epsk; }
   }
-  __device__ __forceinline__ float at(int k, float p, float w, float qa, float qg) const {
+  __device__ __forceinline__ PixGrad(int t_, float wt, const CeW<WT>& cw, float wsum, float f0_, float f1_, float sq_, float mod_, float beta_, float f2_, float sl_)
+      : PixGrad(t_, wt, cw, wsum, f0_, f1_, sq_, mod_, beta_) {
+    if constexpr (LV) { this->f2 = f2_; this->sl = sl_; }
+  }
+  __device__ __forceinline__ float at(int k, float p, float w, float qa, float qg, float lq = 0.f) const {
     float ce;
     if constexpr (WT) ce = p * ct - ((k == t ? hit : 0.f) + epsk * w);
     else ce = p - (k == t ? 1.f : 0.f);
     if constexpr (FC) ce = mod * ce + beta * (p - (k == t ? 1.f : 0.f));
-    if constexpr (DC) return f0 * ce + f1 * (p * (dice_q(k, t, qa, qg) - sq));
+    if constexpr (LV) {
+      float r = f0 * ce + this->f2 * (p * (lq - this->sl));
+      if constexpr (DC) r += f1 * (p * (dice_q(k, t, qa, qg) - sq));
+      return r;
+    } else if constexpr (DC) return f0 * ce + f1 * (p * (dice_q(k, t, qa, qg) - sq));
     else return ce;
   }
 };
@@ -337,10 +363,11 @@ __global__ __launch_bounds__(1024) void upsample_ce_dice_finalize_kernel(const f
 
 // four lanes per low-resolution cell (each takes every 4th footprint row), gather over the pixels whose bilinear
 // footprint touches the cell, then a 4-lane shuffle reduction: deterministic, no atomics.
-template <int KW, bool WT, bool DC, bool FC>
+template <int KW, bool WT, bool DC, bool FC, bool LV>
 __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
                                                               const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
-                                                              int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd, CeF<FC> cf) {
+                                                              int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd, CeF<FC> cf, CeL<LV> cl) {
+  constexpr bool NOK = DC || FC || LV;                  // the class-weight pointer may be null
   const long long cells = (long long)g.B * g.h * g.w;
   const long long ci = (blockIdx.x * 256LL + threadIdx.x) >> 2;
   const int sub = threadIdx.x & 3;
@@ -356,9 +383,11 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
   float wsum = 0.f;
   if constexpr (WT) {
 #pragma unroll
-    for (int k = 0; k < KW; ++k) if (k < g.K) wsum += cew_at<DC || FC>(cw, k);
+    for (int k = 0; k < KW; ++k) if (k < g.K) wsum += cew_at<NOK>(cw, k);
   }
   float qa[DC ? KW : 1], qg[DC ? KW : 1], f0 = 0.f, f1 = 0.f;      // DC: the (a, g) of this cell's sample and the two scales
+  float f2 = 0.f;                                       // LV: the third scale
+  if constexpr (LV) { f0 = gscale[0] / loss_cnt[1]; f2 = gscale[2]; }
   if constexpr (DC) {
     f0 = gscale[0] / loss_cnt[1]; f1 = gscale[1];
 #pragma unroll
@@ -385,7 +414,7 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
         float m = v[0];
 #pragma unroll
         for (int k = 0; k < KW; ++k) m = fmaxf(m, v[k]);
-        float s = 0.f;
+        float s = 0.f, lso = 0.f;                         // LV: lso = sum_{k != t} e_k, in index order
         CePix px = {};                                    // FC: the pixel's (mod, beta), from the logits before the exponentials take their place
         if constexpr (FC) {
           float e[KW], vt = 0.f, so = 0.f, et = 0.f;
@@ -397,9 +426,13 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
           px = ce_pixel<KW, WT, DC, true>(g.K, v, m, s, vt, (int)t, cw, cf, so, et);
 #pragma unroll
           for (int k = 0; k < KW; ++k) v[k] = e[k];
+          if constexpr (LV) lso = so;
         } else {
 #pragma unroll
-          for (int k = 0; k < KW; ++k) { v[k] = k < g.K ? expf(v[k] - m) : 0.f; s += v[k]; }
+          for (int k = 0; k < KW; ++k) {
+            v[k] = k < g.K ? expf(v[k] - m) : 0.f; s += v[k];
+            if constexpr (LV) if (k != (int)t) lso += v[k];
+          }
         }
         const float wgt = wy * wx, inv = 1.f / s;
         float sq = 0.f;                                   // DC: sum_c p_c q_c, in index order
@@ -408,16 +441,22 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(UpGeom g, const fl
           v[k] *= inv;
           if constexpr (DC) sq += v[k] * dice_q(k, (int)t, qa[k], qg[k]);
         }
-        const PixGrad<WT, DC, FC> pg((int)t, cew_at<DC || FC>(cw, (int)t), cw, wsum, f0, f1, sq, FC ? px.mod : 1.f, FC ? px.beta : 0.f);
-        constexpr bool PLAIN = !WT && !DC;                // reads no table: runs over all KW unguarded (acc beyond K is never stored)
+        float lq[LV ? KW : 1], sl = 0.f;                  // LV: the Lovasz q of every channel and sum_c p_c q_c, in index order
+        if constexpr (LV) {
+          const float u = lso * inv;
+#pragma unroll
+          for (int k = 0; k < KW; ++k) { lq[k] = k < g.K ? lov_q(cl.tab, k, (int)t, v[k], u) : 0.f; sl += v[k] * lq[k]; }
+        }
+        const PixGrad<WT, DC, FC, LV> pg((int)t, cew_at<NOK>(cw, (int)t), cw, wsum, f0, f1, sq, FC ? px.mod : 1.f, FC ? px.beta : 0.f, f2, sl);
+        constexpr bool PLAIN = !WT && !DC && !LV;         // reads no table: runs over all KW unguarded (acc beyond K is never stored)
 #pragma unroll
         for (int k = 0; k < KW; ++k)
-          if (PLAIN || k < g.K) acc[k] += wgt * pg.at(k, v[k], cew_at<DC || FC>(cw, k), DC ? qa[k] : 0.f, DC ? qg[k] : 0.f);
+          if (PLAIN || k < g.K) acc[k] += wgt * pg.at(k, v[k], cew_at<NOK>(cw, k), DC ? qa[k] : 0.f, DC ? qg[k] : 0.f, LV ? lq[k] : 0.f);
       }
     }
   }
-  float f = 1.f;                                        // DC: the scales are inside the pixel gradients
-  if constexpr (!DC) f = gscale[0] / loss_cnt[1];
+  float f = 1.f;                                        // DC, LV: the scales are inside the pixel gradients
+  if constexpr (!DC && !LV) f = gscale[0] / loss_cnt[1];
 #pragma unroll
   for (int k = 0; k < KW; ++k) {
     float a = acc[k];
@@ -445,7 +484,7 @@ enum TileBuf {
   T_WXJ,   // [NX][CT] weight of footprint column X on cell j0 + jr
   T_WYI,   // [NY][CT]
   T_ST,    // wide: [NY][NX][SW] max, 1 / sum, label as int (-1: the pixel does not count); DC: the fourth word is sum_c p_c q_c over ALL K channels;
-           // FC: the last two words are the pixel's (mod, beta)
+           // LV: two words behind those, the Lovasz sum_c p_c q_c over ALL K channels and u;  FC: the last two words are the pixel's (mod, beta)
   T_H1,    // [NY][CT][KS]
   T_G,     // [NY][NX][KS]
   T_WL,    // WT: [K] class weights
@@ -454,17 +493,17 @@ enum TileBuf {
 };
 // I: size_t on the host, which sizes a launch it may still refuse; int on the device, where the sum has passed the host's 150 KiB limit
 template <typename I>
-__host__ __device__ inline void tile_extents(int K, const UpTile& ut, bool wt, bool dc, bool fc, bool wide, I* n) {
+__host__ __device__ inline void tile_extents(int K, const UpTile& ut, bool wt, bool dc, bool fc, bool lv, bool wide, I* n) {
   const I NY = ut.NYmax, NX = ut.NXmax;
   n[T_LGT] = (I)(CT + 2) * (CT + 2) * K;
   n[T_WY0] = 3 * NY; n[T_WX0] = 3 * NX; n[T_WXJ] = CT * NX; n[T_WYI] = CT * NY;
-  n[T_ST] = wide ? ((dc ? 4 : 3) + (fc ? 2 : 0)) * NY * NX : 0;
+  n[T_ST] = wide ? ((dc ? 4 : 3) + (lv ? 2 : 0) + (fc ? 2 : 0)) * NY * NX : 0;
   n[T_H1] = NY * CT * ut.KS; n[T_G] = NY * NX * ut.KS;
   n[T_WL] = wt ? K : 0; n[T_CF] = dc ? 2 * K : 0;
 }
-inline size_t tile_lds_bytes(int K, const UpTile& ut, bool wt, bool dc, bool fc, bool wide) {
+inline size_t tile_lds_bytes(int K, const UpTile& ut, bool wt, bool dc, bool fc, bool lv, bool wide) {
   size_t n[T_NBUF], s = 0;
-  tile_extents(K, ut, wt, dc, fc, wide, n);
+  tile_extents(K, ut, wt, dc, fc, lv, wide, n);
   for (int i = 0; i < T_NBUF; ++i) s += n[i];
   return s * sizeof(float);
 }
@@ -475,12 +514,12 @@ struct TileFrame {
   float* buf[T_NBUF];
 };
 // Carves the LDS and fills lgt, the weight and coefficient tables and wy0 / wx0 / wyi / wxj; ends with the barrier.
-template <int NT, bool WT, bool DC, bool WIDE, bool FC = false>
+template <int NT, bool WT, bool DC, bool WIDE, bool FC = false, bool LV = false>
 __device__ __forceinline__ TileFrame tile_frame(const UpGeom& g, const UpTile& ut, float* sm, const float* __restrict__ lg, const CeW<WT>& cw, const CeD<DC>& cd) {
   TileFrame f;
   const int K = g.K, tid = threadIdx.x;
   int n[T_NBUF];
-  tile_extents(K, ut, WT, DC, FC, WIDE, n);
+  tile_extents(K, ut, WT, DC, FC, LV, WIDE, n);
 #pragma unroll
   for (int i = 0; i < T_NBUF; ++i) { f.buf[i] = sm; sm += n[i]; }
   float *lgt = f.buf[T_LGT], *wy0 = f.buf[T_WY0], *wx0 = f.buf[T_WX0], *wxj = f.buf[T_WXJ], *wyi = f.buf[T_WYI];
@@ -499,7 +538,7 @@ __device__ __forceinline__ TileFrame tile_frame(const UpGeom& g, const UpTile& u
     const int yy = min(max(i0 - 1 + cy, 0), g.h - 1), xx = min(max(j0 - 1 + cx, 0), g.w - 1);
     lgt[e] = lb[((size_t)k * g.h + yy) * g.w + xx];
   }
-  if constexpr (WT) for (int e = tid; e < K; e += NT) f.buf[T_WL][e] = cew_at<DC || FC>(cw, e);
+  if constexpr (WT) for (int e = tid; e < K; e += NT) f.buf[T_WL][e] = cew_at<DC || FC || LV>(cw, e);
   if constexpr (DC) for (int e = tid; e < 2 * K; e += NT) f.buf[T_CF][e] = cd.coef[(size_t)b * K * 2 + e];
   for (int e = tid; e < NY; e += NT) {
     int y0, y1; float ly; src_index_ac1(Ylo + e, g.h, g.sy, y0, y1, ly);
@@ -570,10 +609,10 @@ __device__ __forceinline__ void scatter_y_store(const UpGeom& g, const TileFrame
   }
 }
 
-template <int NT, bool WT, bool DC, bool FC>
+template <int NT, bool WT, bool DC, bool FC, bool LV>
 __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpTile ut, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
                                                                    const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
-                                                                   int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd, CeF<FC> fo) {
+                                                                   int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd, CeF<FC> fo, CeL<LV> cl) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int KW = KNC;                            // this kernel serves K <= KNC (G holds all K channels of every footprint pixel)
   const int K = g.K;
@@ -606,7 +645,7 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
     const int yy = min(max(i0 - 1 + cy, 0), g.h - 1), xx = min(max(j0 - 1 + cx, 0), g.w - 1);
     lgt[e] = lb[((size_t)k * g.h + yy) * g.w + xx];
   }
-  if constexpr (WT) for (int e = tid; e < K; e += NT) wl[e] = cew_at<DC || FC>(cw, e);
+  if constexpr (WT) for (int e = tid; e < K; e += NT) wl[e] = cew_at<DC || FC || LV>(cw, e);
   if constexpr (DC) for (int e = tid; e < 2 * K; e += NT) cf[e] = cd.coef[(size_t)b * K * 2 + e];
   for (int e = tid; e < NY; e += NT) {
     int y0, y1; float ly; src_index_ac1(Ylo + e, g.h, g.sy, y0, y1, ly);
@@ -633,8 +672,9 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
   }
   float wsum = 0.f;
   if constexpr (WT) for (int k = 0; k < K; ++k) wsum += wl[k];
-  float f0 = 0.f, f1 = 0.f;
+  float f0 = 0.f, f1 = 0.f, f2 = 0.f;
   if constexpr (DC) { f0 = gscale[0] / loss_cnt[1]; f1 = gscale[1]; }
+  if constexpr (LV) { f0 = gscale[0] / loss_cnt[1]; f2 = gscale[2]; }
 #pragma unroll 1
   for (int u = 0; tid + NT * u < NY * NX; ++u) {
     const int pix = tid + NT * u;
@@ -659,6 +699,7 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
       else v[k] = -INFINITY;
     }
     float ssum = 0.f;
+    [[maybe_unused]] float lso = 0.f;                  // LV: sum_{k != t} e_k, in index order
     CePix px = {};                                     // FC: the pixel's (mod, beta), from the logits before the exponentials take their place
     if constexpr (FC) {
       float e[KW], vt = 0.f, so = 0.f, et = 0.f;
@@ -670,9 +711,13 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
       px = ce_pixel<KW, WT, DC, true>(K, v, m, ssum, vt, (int)t, cw, fo, so, et);
 #pragma unroll
       for (int k = 0; k < KW; ++k) v[k] = e[k];
+      if constexpr (LV) lso = so;
     } else {
 #pragma unroll
-      for (int k = 0; k < KW; ++k) { v[k] = k < K ? __expf(v[k] - m) : 0.f; ssum += v[k]; }      // hardware exp2-based: 2 ulp, the gradient's tolerance is 1e-3
+      for (int k = 0; k < KW; ++k) {
+        v[k] = k < K ? __expf(v[k] - m) : 0.f; ssum += v[k];      // hardware exp2-based: 2 ulp, the gradient's tolerance is 1e-3
+        if constexpr (LV) if (k != (int)t) lso += v[k];
+      }
     }
     const float inv = 1.f / ssum;
     // DC normalises v first (sq = sum_c p_c q_c, in index order, needs every p); the other forms multiply by inv at the one use below, under the same k < K guard as
@@ -682,9 +727,23 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
 #pragma unroll
       for (int k = 0; k < KW; ++k) if (k < K) { v[k] *= inv; sq += v[k] * dice_q(k, (int)t, cf[2 * k], cf[2 * k + 1]); }
     }
-    const PixGrad<WT, DC, FC> pg((int)t, WT ? wl[t] : 1.f, cw, wsum, f0, f1, sq, FC ? px.mod : 1.f, FC ? px.beta : 0.f);
+    if constexpr (LV) {                                // normalised v (by the loop above with DC), the Lovasz q of every channel and sum_c p_c q_c, in index order
+      float lq[KW], sl = 0.f;
+      const float u = lso * inv;
 #pragma unroll
-    for (int k = 0; k < KW; ++k) if (k < K) out[k] = pg.at(k, DC ? v[k] : v[k] * inv, WT ? wl[k] : 0.f, DC ? cf[2 * k] : 0.f, DC ? cf[2 * k + 1] : 0.f);
+      for (int k = 0; k < KW; ++k) {
+        if constexpr (!DC) v[k] *= inv;
+        lq[k] = k < K ? lov_q(cl.tab, k, (int)t, v[k], u) : 0.f;
+        sl += v[k] * lq[k];
+      }
+      const PixGrad<WT, DC, FC, LV> pg((int)t, WT ? wl[t] : 1.f, cw, wsum, f0, f1, sq, FC ? px.mod : 1.f, FC ? px.beta : 0.f, f2, sl);
+#pragma unroll
+      for (int k = 0; k < KW; ++k) if (k < K) out[k] = pg.at(k, v[k], WT ? wl[k] : 0.f, DC ? cf[2 * k] : 0.f, DC ? cf[2 * k + 1] : 0.f, lq[k]);
+    } else {
+      const PixGrad<WT, DC, FC> pg((int)t, WT ? wl[t] : 1.f, cw, wsum, f0, f1, sq, FC ? px.mod : 1.f, FC ? px.beta : 0.f);
+#pragma unroll
+      for (int k = 0; k < KW; ++k) if (k < K) out[k] = pg.at(k, DC ? v[k] : v[k] * inv, WT ? wl[k] : 0.f, DC ? cf[2 * k] : 0.f, DC ? cf[2 * k + 1] : 0.f);
+    }
   }
   __syncthreads();
   // ---- pass 2a: along X
@@ -701,8 +760,8 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
   }
   __syncthreads();
   // ---- pass 2b: along Y, scale, store
-  float f = 1.f;                                     // DC: the scales are inside G
-  if constexpr (!DC) f = gscale[0] / loss_cnt[1];
+  float f = 1.f;                                     // DC, LV: the scales are inside G
+  if constexpr (!DC && !LV) f = gscale[0] / loss_cnt[1];
   for (int e = tid; e < CT * CT * K; e += NT) {
     const int k = e % K, c = e / K, ir = c / CT, jr = c - ir * CT;
     const int i = i0 + ir, j = j0 + jr;
@@ -719,14 +778,16 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_kernel(UpGeom g, UpT
 // Each pixel's softmax is still evaluated once (2 K exponentials instead of K); sums in a fixed order, no atomics.
 // FC: the focal (mod, beta) of a pixel need all K channels (the cross-entropy numerator, the sum without t), so pass 0, the only one that sees them all, evaluates
 // ce_pixel on the pixel's K logits in registers and keeps the two values as two more statistics words; the slices read them back into their PixGrad.
-template <int NT, bool WT, bool DC, bool FC>
+// LV: pass 0 also keeps the Lovasz sum_c p_c q_c over all K channels and u, from the p = __expf(v - m) * inv the slices evaluate again (the same bins both times).
+template <int NT, bool WT, bool DC, bool FC, bool LV>
 __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g, UpTile ut, const float* __restrict__ lg, const int64_t* __restrict__ tgt,
                                                                         const float* __restrict__ loss_cnt, const float* __restrict__ gscale,
-                                                                        int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd, CeF<FC> fo) {
+                                                                        int ignore, float* __restrict__ dlg, CeW<WT> cw, CeD<DC> cd, CeF<FC> fo, CeL<LV> cl) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  constexpr int SW = (DC ? 4 : 3) + (FC ? 2 : 0);    // statistics words per footprint pixel
+  constexpr int LO = DC ? 4 : 3;                     // LV: its two statistics words
+  constexpr int SW = LO + (LV ? 2 : 0) + (FC ? 2 : 0);   // statistics words per footprint pixel
   const int K = g.K, KS = ut.KS, tid = threadIdx.x;
-  const TileFrame f = tile_frame<NT, WT, DC, true, FC>(g, ut, sm, lg, cw, cd);
+  const TileFrame f = tile_frame<NT, WT, DC, true, FC, LV>(g, ut, sm, lg, cw, cd);
   const int b = f.b, i0 = f.i0, j0 = f.j0, Ylo = f.Ylo, Xlo = f.Xlo, NY = f.NY, NX = f.NX;
   float *st = f.buf[T_ST], *G = f.buf[T_G];
   const float *lgt = f.buf[T_LGT], *wy0 = f.buf[T_WY0], *wx0 = f.buf[T_WX0], *wl = f.buf[T_WL], *cf = f.buf[T_CF];
@@ -761,11 +822,20 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
       for (int k = 0; k < K; ++k) ssum += __expf(tap.at(k) - m);
     }
     s[0] = m; s[1] = 1.f / ssum; s[2] = __int_as_float((int)t);
+    if constexpr (LV) {
+      const float inv = 1.f / ssum;
+      float so = 0.f, sl = 0.f;
+      for (int k = 0; k < K; ++k) if (k != (int)t) so += __expf(tap.at(k) - m);
+      const float u = so * inv;
+      for (int k = 0; k < K; ++k) { const float p = __expf(tap.at(k) - m) * inv; sl += p * lov_q(cl.tab, k, (int)t, p, u); }
+      s[LO] = sl; s[LO + 1] = u;
+    }
   }
   __syncthreads();
   const float f0 = gscale[0] / loss_cnt[1];          // DC: applied per pixel with f1 before the scatter
-  float f1 = 0.f;
+  float f1 = 0.f, f2 = 0.f;
   if constexpr (DC) f1 = gscale[1];
+  if constexpr (LV) f2 = gscale[2];
   float wsum = 0.f;
   if constexpr (WT) for (int k = 0; k < K; ++k) wsum += wl[k];
   for (int k0 = 0; k0 < K; k0 += KS) {
@@ -782,17 +852,20 @@ __global__ __launch_bounds__(NT) void upsample_ce_bwd_tiled_wide_kernel(UpGeom g
       }
       const UpTap tap = up_tap(lgt, wy0, wx0, yr, xr, i0, j0, K);
       const float m = s[0], inv = s[1];
-      const PixGrad<WT, DC, FC> pg(t, WT ? wl[t] : 1.f, cw, wsum, f0, f1, DC ? s[3] : 0.f, FC ? s[SW - 2] : 1.f, FC ? s[SW - 1] : 0.f);
+      const PixGrad<WT, DC, FC, LV> pg(t, WT ? wl[t] : 1.f, cw, wsum, f0, f1, DC ? s[3] : 0.f, FC ? s[SW - 2] : 1.f, FC ? s[SW - 1] : 0.f, f2, LV ? s[LO] : 0.f);
       for (int kk = 0; kk < kn; ++kk) {
         const int k = k0 + kk;
-        out[kk] = pg.at(k, __expf(tap.at(k) - m) * inv, WT ? wl[k] : 0.f, DC ? cf[2 * k] : 0.f, DC ? cf[2 * k + 1] : 0.f);
+        const float p = __expf(tap.at(k) - m) * inv;
+        float lq = 0.f;
+        if constexpr (LV) lq = lov_q(cl.tab, k, t, p, s[LO + 1]);
+        out[kk] = pg.at(k, p, WT ? wl[k] : 0.f, DC ? cf[2 * k] : 0.f, DC ? cf[2 * k + 1] : 0.f, lq);
       }
     }
     __syncthreads();
     scatter_x<NT>(g, f, kn, KS);
     __syncthreads();
     // the next slice's pass 1 writes G only, and H1 is written again after the barrier that follows it
-    scatter_y_store<NT>(g, f, k0, kn, KS, DC ? 1.f : f0, dlg);
+    scatter_y_store<NT>(g, f, k0, kn, KS, (DC || LV) ? 1.f : f0, dlg);
   }
 }
 
@@ -1115,6 +1188,104 @@ __global__ __launch_bounds__(256) void ohem_mine_kernel(const float* __restrict_
   for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += gridDim.x * 256LL) mined[i] = (none || prob[i] <= th) ? tgt[i] : (int64_t)ignore;
 }
 
+// ---- Lovasz-softmax forward (the contract is in include/segland_hip.h): no sort.  The Lovasz extension does not depend on the order inside ties, so with every class's
+// errors quantised to LOV_NB bins the loss and a subgradient follow from two integer histograms per class and one scan over the bins:
+//   1. upsample_lovasz_hist_kernel: one softmax per valid pixel (the arithmetic of upsample_ohem_prob_kernel), one increment per class into the block's LDS histograms
+//      [classes of the slice][LOV_NB][2] (foreground, background), then one integer global atomic per non-empty bin and block.  Integer sums: two runs give the same bits.
+//      A block holds LOV_KC classes (64 KiB of LDS, two blocks per CU); wider K runs cdiv(K, LOV_KC) slices side by side in gridDim.y, each evaluating the softmax again.
+//   2. lovasz_scan_kernel: one block per class, one thread per bin, integer suffix sums, then the Jaccard steps, the table row and the class's partial in double;
+//   3. lovasz_sum_kernel: one thread adds the present classes in index order.
+// workspace: unsigned hist[K][LOV_NB][2], then double part[K][2] = (sum_j centre_j dJ_c[j], class is present)
+constexpr int LOV_KC = 8, LOV_HT = 512;
+inline size_t lov_ws_bytes(int K) { return (size_t)K * LOV_NB * 2 * sizeof(unsigned) + (size_t)K * 2 * sizeof(double); }
+
+__global__ __launch_bounds__(256) void lovasz_zero_kernel(unsigned* __restrict__ ws, int n) {
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) ws[i] = 0u;
+}
+
+template <int KW>
+__global__ __launch_bounds__(LOV_HT) void upsample_lovasz_hist_kernel(UpGeom g, const float* __restrict__ lg, const int64_t* __restrict__ tgt, int ignore, unsigned* __restrict__ hist) {
+  extern __shared__ unsigned lovh[];                     // [kn][LOV_NB][2]
+  const int tid = threadIdx.x;
+  const int k0 = blockIdx.y * LOV_KC, kn = min(LOV_KC, g.K - k0);
+  for (int i = tid; i < kn * LOV_NB * 2; i += LOV_HT) lovh[i] = 0u;
+  __syncthreads();
+  const long long total = (long long)g.B * g.H * g.W;
+  for (long long i = blockIdx.x * (long long)LOV_HT + tid; i < total; i += gridDim.x * (long long)LOV_HT) {
+    const long long t = tgt[i];
+    if (t == ignore || t < 0 || t >= g.K) continue;
+    const int X = (int)(i % g.W); const long long r = i / g.W;
+    const int Y = (int)(r % g.H), b = (int)(r / g.H);
+    float v[KW];
+    pixel_logits<KW>(g, lg, b, Y, X, v);
+    float vt;
+    const float m = ce_max<KW>(v, (int)t, vt);
+    float s = 0.f, so = 0.f;
+#pragma unroll
+    for (int k = 0; k < KW; ++k) if (k < g.K) { v[k] = expf(v[k] - m); s += v[k]; if (k != (int)t) so += v[k]; }
+#pragma unroll
+    for (int k = 0; k < KW; ++k) {
+      if (k >= k0 && k < k0 + kn) {                       // k0 is the same in every lane
+        const bool fg = k == (int)t;
+        const float e = (fg ? so : v[k]) / s;
+        atomicAdd(&lovh[((k - k0) * LOV_NB + lov_bin(e)) * 2 + (fg ? 0 : 1)], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  unsigned* hs = hist + (size_t)k0 * LOV_NB * 2;
+  for (int i = tid; i < kn * LOV_NB * 2; i += LOV_HT) if (lovh[i]) atomicAdd(&hs[i], lovh[i]);
+}
+
+// Block c, thread j = bin j.  Walking the bins from the top, f and b are the foreground and background counts of the bins >= j (inclusive suffix sums, integers):
+//   J(j) = 1 - (G - f) / (G + b),  dJ[j] = J(j) - J(j + 1),  J(LOV_NB) = 0;  an empty bin has dJ == 0 exactly.  Every block counts the present classes itself (K * LOV_NB
+// words from the L2) so that the table needs no second pass.
+__global__ __launch_bounds__(LOV_NB) void lovasz_scan_kernel(const unsigned* __restrict__ hist, int K, float* __restrict__ tab, double* __restrict__ part) {
+  __shared__ unsigned sf[LOV_NB], sb[LOV_NB];
+  __shared__ double sj[LOV_NB];
+  __shared__ int flag[KMAXC];
+  const int c = blockIdx.x, j = threadIdx.x;
+  if (j < KMAXC) flag[j] = 0;
+  __syncthreads();
+  for (int k = 0; k < K; ++k) if (hist[((size_t)k * LOV_NB + j) * 2]) flag[k] = 1;
+  const unsigned F = hist[((size_t)c * LOV_NB + j) * 2], Bk = hist[((size_t)c * LOV_NB + j) * 2 + 1];
+  sf[j] = F; sb[j] = Bk;
+  __syncthreads();
+  int np = 0;
+  for (int k = 0; k < K; ++k) np += flag[k];
+  for (int o = 1; o < LOV_NB; o <<= 1) {
+    const unsigned a = j + o < LOV_NB ? sf[j + o] : 0u, d = j + o < LOV_NB ? sb[j + o] : 0u;
+    __syncthreads();
+    sf[j] += a; sb[j] += d;
+    __syncthreads();
+  }
+  const unsigned G = sf[0];
+  const bool present = G > 0u;
+  const double J = present ? 1.0 - (double)(G - sf[j]) / ((double)G + (double)sb[j]) : 0.0;
+  sj[j] = J;
+  __syncthreads();
+  const double dJ = J - (j + 1 < LOV_NB ? sj[j + 1] : 0.0);
+  const double cnt = (double)F + (double)Bk;
+  tab[(size_t)c * LOV_NB + j] = present && cnt > 0.0 ? (float)(dJ / (cnt * (double)np)) : 0.f;
+  __syncthreads();
+  sj[j] = present ? ((double)j + 0.5) / (double)LOV_NB * dJ : 0.0;
+  __syncthreads();
+  for (int o = LOV_NB / 2; o > 0; o >>= 1) {
+    if (j < o) sj[j] += sj[j + o];
+    __syncthreads();
+  }
+  if (j == 0) { part[2 * c] = sj[0]; part[2 * c + 1] = present ? 1.0 : 0.0; }
+}
+
+// out = (mean over the present classes, in index order; number of present classes); (0, 0) without one
+__global__ void lovasz_sum_kernel(const double* __restrict__ part, int K, float* __restrict__ out) {
+  if (threadIdx.x || blockIdx.x) return;
+  double L = 0.0, np = 0.0;
+  for (int c = 0; c < K; ++c) { L += part[2 * c]; np += part[2 * c + 1]; }
+  out[0] = np > 0.0 ? (float)(L / np) : 0.f;
+  out[1] = (float)np;
+}
+
 inline UpGeom make_up(int B, int K, int h, int w, int H, int W) {
   UpGeom g; g.B = B; g.K = K; g.h = h; g.w = w; g.H = H; g.W = W; g.sy = ac1_scale(h, H); g.sx = ac1_scale(w, W);
   return g;
@@ -1148,9 +1319,10 @@ int launch_ce_dice_fwd(const UpGeom& g, const float* logits, const int64_t* targ
 // DC (the hybrid form): the tiled kernels keep 2 K coefficients more in the LDS and the channel-sliced one a fourth word per footprint pixel; the same 150 KiB limit decides
 // (more slices, then the gather kernel).  loss_and_count is then the finalize's (cross-entropy, denominator, dice) and gscale holds two values.
 // FC (the focal forms): two words more per footprint pixel in the channel-sliced kernel's statistics, decided by the same list and limit.
-template <bool WT, bool DC = false, bool FC = false>
+// LV (the Lovasz term): two words more per footprint pixel in the channel-sliced kernel's statistics, by the same list and limit; gscale then holds three values.
+template <bool WT, bool DC = false, bool FC = false, bool LV = false>
 int launch_ce_bwd(const UpGeom& g, const float* logits, const int64_t* target, const float* loss_and_count, const float* gscale, int ignore_index, float* dlogits,
-                  hipStream_t stream, CeW<WT> cw, CeD<DC> cd = CeD<DC>(), CeF<FC> cf = CeF<FC>()) {
+                  hipStream_t stream, CeW<WT> cw, CeD<DC> cd = CeD<DC>(), CeF<FC> cf = CeF<FC>(), CeL<LV> cl = CeL<LV>()) {
   const int B = g.B, K = g.K, h = g.h, w = g.w, H = g.H, W = g.W;
   const long long cells = (long long)B * h * w;
   // tiled kernel when the joint footprint of a CT x CT cell tile fits the LDS (always for an upsampling factor <= ~12 at K <= 16); test hook sl_debug_ce_tiled(0): never
@@ -1166,21 +1338,21 @@ int launch_ce_bwd(const UpGeom& g, const float* logits, const int64_t* target, c
     const size_t limit = 150 * 1024;
     if (!wide) {                                     // all K channels in one pass, or not tiled
       ut.KS = K;
-      const size_t lds = tile_lds_bytes(K, ut, WT, DC, FC, false);
+      const size_t lds = tile_lds_bytes(K, ut, WT, DC, FC, LV, false);
       if (lds <= limit)
-        return sl_launch("upsample_ce_bwd_tiled_kernel", upsample_ce_bwd_tiled_kernel<SL_UPCE_NT, WT, DC, FC>, tiles, dim3(SL_UPCE_NT), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw, cd, cf);
+        return sl_launch("upsample_ce_bwd_tiled_kernel", upsample_ce_bwd_tiled_kernel<SL_UPCE_NT, WT, DC, FC, LV>, tiles, dim3(SL_UPCE_NT), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw, cd, cf, cl);
     } else {
       // channel-sliced form: the fewest slices (of at most KNC channels) whose G and H1 fit next to the per-pixel statistics
       for (int ns = cdiv(K, KNC); ns <= K; ++ns) {
         ut.KS = cdiv(K, ns);
-        const size_t lds = tile_lds_bytes(K, ut, WT, DC, FC, true);
+        const size_t lds = tile_lds_bytes(K, ut, WT, DC, FC, LV, true);
         if (lds > limit) continue;
-        return sl_launch("upsample_ce_bwd_tiled_wide_kernel", upsample_ce_bwd_tiled_wide_kernel<512, WT, DC, FC>, tiles, dim3(512), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw, cd, cf);
+        return sl_launch("upsample_ce_bwd_tiled_wide_kernel", upsample_ce_bwd_tiled_wide_kernel<512, WT, DC, FC, LV>, tiles, dim3(512), lds, stream, g, ut, logits, target, loss_and_count, gscale, ignore_index, dlogits, cw, cd, cf, cl);
       }
     }
   }
-  return sl_launch("upsample_ce_bwd_kernel", K <= KNC ? upsample_ce_bwd_kernel<KNC, WT, DC, FC> : upsample_ce_bwd_kernel<KMAXC, WT, DC, FC>, dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, stream, g, logits, target,
-                   loss_and_count, gscale, ignore_index, dlogits, cw, cd, cf);
+  return sl_launch("upsample_ce_bwd_kernel", K <= KNC ? upsample_ce_bwd_kernel<KNC, WT, DC, FC, LV> : upsample_ce_bwd_kernel<KMAXC, WT, DC, FC, LV>, dim3((unsigned)((cells * 4 + 255) / 256)), dim3(256), 0, stream, g, logits, target,
+                   loss_and_count, gscale, ignore_index, dlogits, cw, cd, cf, cl);
 }
 
 inline CeW<true> make_cew(const float* class_weight, float label_smoothing, int K) {
@@ -1360,6 +1532,65 @@ extern "C" int sl_ohem_mine(const float* prob, const int64_t* target, const floa
   SL_REQUIRE(n_pix > 0 && n_pix < (1LL << 31), "ohem_mine: %lld pixels; one call takes 1 to 2^31 - 1", n_pix);
   SL_REQUIRE(prob && target && theta && counts && mined, "ohem_mine: null buffer");
   return sl_launch("ohem_mine_kernel", ohem_mine_kernel, dim3(ce_blocks(n_pix)), dim3(256), 0, (hipStream_t)stream, prob, target, theta, counts, n_pix, ignore_index, mined);
+}
+
+// ---- Lovasz-softmax term: histogram pass, scan, and the one backward launch for cross-entropy (plain, weighted, focal) [+ Dice] + Lovasz (the kernels above)
+extern "C" int sl_lovasz_bins(void) { return LOV_NB; }
+
+extern "C" size_t sl_lovasz_workspace(int K) { return K >= 1 && K <= KMAXC ? lov_ws_bytes(K) : 0; }
+
+extern "C" int sl_upsample_lovasz_hist(const float* logits, const int64_t* target, int B, int K, int h, int w, int H, int W, int ignore_index, void* workspace,
+                                       size_t ws_bytes, sl_stream_t stream) {
+  SL_REQUIRE(K >= 1 && K <= KMAXC, "upsample_lovasz_hist: %d logit channels; this build holds at most %d", K, KMAXC);
+  SL_REQUIRE(B > 0 && h > 0 && w > 0 && H > 0 && W > 0, "upsample_lovasz_hist: bad shape");
+  SL_REQUIRE((long long)B * H * W < (1LL << 32), "upsample_lovasz_hist: %lld pixels; the bin counts are 32-bit, one call takes fewer than 2^32", (long long)B * H * W);
+  SL_REQUIRE(logits && target && workspace, "upsample_lovasz_hist: null buffer");
+  SL_REQUIRE(ws_bytes >= lov_ws_bytes(K), "upsample_lovasz_hist: workspace %zu < %zu (sl_lovasz_workspace)", ws_bytes, lov_ws_bytes(K));
+  const UpGeom g = make_up(B, K, h, w, H, W);
+  const hipStream_t s = (hipStream_t)stream;
+  const int words = (int)(lov_ws_bytes(K) / sizeof(unsigned));
+  SL_TRY(sl_launch("lovasz_zero_kernel", lovasz_zero_kernel, dim3((unsigned)cdiv(words, 256 * 8)), dim3(256), 0, s, (unsigned*)workspace, words));
+  // 8 pixels per thread and at most 512 blocks per slice: a block ends in up to LOV_KC * LOV_NB * 2 global atomics
+  const long long nb = ((long long)B * H * W + LOV_HT * 8 - 1) / (LOV_HT * 8);
+  const dim3 grid((unsigned)(nb < 1 ? 1 : (nb > 512 ? 512 : nb)), (unsigned)cdiv(K, LOV_KC));
+  const size_t lds = (size_t)(K < LOV_KC ? K : LOV_KC) * LOV_NB * 2 * sizeof(unsigned);
+  return sl_launch("upsample_lovasz_hist_kernel", K <= LOV_KC ? upsample_lovasz_hist_kernel<LOV_KC> : K <= KNC ? upsample_lovasz_hist_kernel<KNC> : upsample_lovasz_hist_kernel<KMAXC>,
+                   grid, dim3(LOV_HT), lds, s, g, logits, target, ignore_index, (unsigned*)workspace);
+}
+
+extern "C" int sl_lovasz_scan(const void* workspace, int K, float* out, float* table, sl_stream_t stream) {
+  SL_REQUIRE(K >= 1 && K <= KMAXC, "lovasz_scan: %d classes; this build holds at most %d", K, KMAXC);
+  SL_REQUIRE(workspace && out && table, "lovasz_scan: null buffer");
+  const hipStream_t s = (hipStream_t)stream;
+  const unsigned* hist = (const unsigned*)workspace;
+  double* part = (double*)(hist + (size_t)K * LOV_NB * 2);
+  SL_TRY(sl_launch("lovasz_scan_kernel", lovasz_scan_kernel, dim3((unsigned)K), dim3(LOV_NB), 0, s, hist, K, table, part));
+  return sl_launch("lovasz_sum_kernel", lovasz_sum_kernel, dim3(1), dim3(64), 0, s, part, K, out);
+}
+
+extern "C" int sl_upsample_lovasz_bwd(const float* logits, const int64_t* target, const float* class_weight, float label_smoothing, float gamma, const float* loss_out,
+                                      const float* coef, const float* table, const float* gscale, int B, int K, int h, int w, int H, int W, int ignore_index,
+                                      float* dlogits, sl_stream_t stream) {
+  SL_CE_DICE_COMMON("upsample_lovasz_bwd");
+  SL_REQUIRE(gamma == 0.f || (gamma >= 1.f && gamma <= 3.402823466e38f), "upsample_lovasz_bwd: gamma %g is neither 0 (no focal modulation) nor a finite value >= 1", (double)gamma);
+  SL_REQUIRE(logits && target && loss_out && table && gscale && dlogits, "upsample_lovasz_bwd: null buffer");
+  const UpGeom g = make_up(B, K, h, w, H, W);
+  const hipStream_t s = (hipStream_t)stream;
+  const bool wt = class_weight || label_smoothing != 0.f, dc = coef != nullptr, fc = gamma != 0.f;
+  CeD<true> cd; cd.coef = coef;
+  CeL<true> cl; cl.tab = table;
+  const CeW<true> cw = make_cew(class_weight, label_smoothing, K);
+#define SL_LOV_BWD(WT, DC, FC, cw_, cd_, cf_) \
+  return launch_ce_bwd<WT, DC, FC, true>(g, logits, target, loss_out, gscale, ignore_index, dlogits, s, cw_, cd_, cf_, cl)
+  if (!wt && !dc && !fc) SL_LOV_BWD(false, false, false, CeW<false>(), CeD<false>(), CeF<false>());
+  if (!wt && !dc && fc) SL_LOV_BWD(false, false, true, CeW<false>(), CeD<false>(), make_cef(gamma));
+  if (!wt && dc && !fc) SL_LOV_BWD(false, true, false, CeW<false>(), cd, CeF<false>());
+  if (!wt && dc && fc) SL_LOV_BWD(false, true, true, CeW<false>(), cd, make_cef(gamma));
+  if (wt && !dc && !fc) SL_LOV_BWD(true, false, false, cw, CeD<false>(), CeF<false>());
+  if (wt && !dc && fc) SL_LOV_BWD(true, false, true, cw, CeD<false>(), make_cef(gamma));
+  if (wt && dc && !fc) SL_LOV_BWD(true, true, false, cw, cd, CeF<false>());
+  SL_LOV_BWD(true, true, true, cw, cd, make_cef(gamma));
+#undef SL_LOV_BWD
 }
 
 extern "C" int sl_pseudo_label(const float* logits, int K2, int h, int w, int64_t* mask, int B, int H, int W, int n_base,

@@ -84,6 +84,16 @@ def focal_gamma(v):
     return gamma
 
 
+def lovasz_weight(v):
+    try:
+        lam = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError('float expected (got %r)' % (v,))
+    if not (np.isfinite(lam) and lam >= 0.0):
+        raise argparse.ArgumentTypeError('the Lovasz weight must be finite and >= 0 (got %r)' % (v,))
+    return lam
+
+
 def aug_scale(v):
     """--aug-scale: '' -> () (off); 'LO,HI' -> (lo, hi) with 0 < LO <= HI <= 4: the range the random rescale before the crop is drawn from."""
     if isinstance(v, (tuple, list)):
@@ -178,17 +188,19 @@ def save_ema_checkpoint(ema, path):
 
 
 def log_loss_options(args):
-    """One line at start: the controls of the segmentation criterion (loss.get_loss reads the same fields); the Dice weight, the focal exponent and the mining controls only where they are on."""
+    """One line at start: the controls of the segmentation criterion (loss.get_loss reads the same fields); the Dice weight, the focal exponent, the Lovasz weight and the mining controls only where they are on."""
     import logging
     w = class_weights(getattr(args, 'class_weights', ()) or ())
     lam = float(getattr(args, 'dice_weight', 0.0))
     th = float(getattr(args, 'ohem_thresh', 0.0) or 0.0)
     gamma = float(getattr(args, 'focal_gamma', 0.0))
+    lov = float(getattr(args, 'lovasz_weight', 0.0))
     logging.getLogger('Segmentation').info('segmentation loss: class weights %s, label smoothing %g' + (', dice weight %g' if lam > 0.0 else '')
                                            + (', focal gamma %g' if gamma > 0.0 else '')
+                                           + (', lovasz weight %g' if lov > 0.0 else '')
                                            + (', hard-pixel mining: threshold %g, at least %d pixels per batch' if th > 0.0 else ''),
                                            ','.join('%g' % x for x in w) if w else 'none', float(getattr(args, 'label_smoothing', 0.0)), *((lam,) if lam > 0.0 else ()),
-                                           *((gamma,) if gamma > 0.0 else ()),
+                                           *((gamma,) if gamma > 0.0 else ()), *((lov,) if lov > 0.0 else ()),
                                            *((th, int(getattr(args, 'ohem_min_kept', 100000))) if th > 0.0 else ()))
 
 
@@ -231,6 +243,9 @@ _COMMON = [
     ('--focal-gamma', dict(type=focal_gamma, default=0.0, help='focal loss: every pixel\'s segmentation cross-entropy is scaled by (1 - p_t)^gamma, p_t the probability of its '
                                                                'label (main and auxiliary head; class weights are the focal alpha; with --dice-weight the Dice term is left '
                                                                'as it is); finite and >= 1; default 0: off.')),
+    ('--lovasz-weight', dict(type=lovasz_weight, default=0.0, help='weight of the Lovasz-softmax term (the convex surrogate of the Jaccard index, over the classes present '
+                                                                   'in the batch; binned, no sort) added to the segmentation loss of the main and the auxiliary head; '
+                                                                   'class weights do not enter it; finite and >= 0; default 0: off.')),
     ('--ohem-thresh', dict(type=ohem_thresh, default=0.0, help='online hard-pixel mining (bootstrapped cross-entropy): only pixels whose probability of the true class '
                                                                'is at most this threshold, in (0, 1], enter the segmentation loss of a head, but never fewer than '
                                                                '--ohem-min-kept of them; default 0: off.')),

@@ -1077,3 +1077,41 @@ class UpsampleFocalDiceFn(torch.autograd.Function):
         logits, target, out, coef, weight = ctx.saved_tensors
         gs = torch.stack([g_ce.detach().reshape(()).float(), g_dice.detach().reshape(()).float()])
         return ops.upsample_focal_dice_bwd(logits, target, out, coef, gs, ctx.ignore, ctx.gamma, weight, ctx.eps), None, None, None, None, None, None
+
+
+class UpsampleLovaszFn(torch.autograd.Function):
+    """(cross-entropy, multiclass soft Dice loss or None, Lovasz-softmax loss) of the upsampled logits.  The cross-entropy (plain, weighted / smoothed, focal for
+    gamma >= 1) and, with `dice`, the Dice term come from the forward of UpsampleCEFn / UpsampleFocalFn / UpsampleCEDiceFn / UpsampleFocalDiceFn, bit for bit; the
+    Lovasz term (include/segland_hip.h has the definition: binned errors, no sort; classes = "present", batch-wide, no class weights) adds a histogram pass and a scan.
+    The backward is ONE launch that takes the three upstream gradients from a device buffer."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, gamma=0.0, weight=None, label_smoothing=0.0, dice=False, smooth=1.0):
+        logits = logits.contiguous()
+        coef = None
+        if dice:
+            if gamma > 0.0:
+                out, coef = ops.upsample_focal_dice_fwd(logits, target, ignore_index, gamma, weight, label_smoothing, smooth)
+            else:
+                out, coef = ops.upsample_ce_dice_fwd(logits, target, ignore_index, weight, label_smoothing, smooth)
+        elif gamma > 0.0:
+            out = ops.upsample_focal_fwd(logits, target, ignore_index, gamma, weight, label_smoothing)
+        else:
+            out = ops.upsample_ce_fwd(logits, target, ignore_index, weight, label_smoothing)
+        lov, table = ops.upsample_lovasz_fwd(logits, target, ignore_index)
+        ctx.ignore = ignore_index
+        ctx.gamma = gamma
+        ctx.eps = label_smoothing
+        ctx.dice = dice
+        ctx.save_for_backward(logits, target, out, coef, table, weight)
+        if dice:
+            return out[0].clone(), out[2].clone(), lov[0].clone()
+        return out[0].clone(), None, lov[0].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_ce, g_dice, g_lov):
+        logits, target, out, coef, table, weight = ctx.saved_tensors
+        zero = g_ce.new_zeros(())
+        gs = torch.stack([(zero if g is None else g).detach().reshape(()).float() for g in (g_ce, g_dice if ctx.dice else None, g_lov)])
+        return ops.upsample_lovasz_bwd(logits, target, out, coef, table, gs, ctx.ignore, ctx.gamma, weight, ctx.eps), None, None, None, None, None, None, None

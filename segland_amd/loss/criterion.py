@@ -4,7 +4,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..functional import UpsampleCEDiceFn, UpsampleCEFn, UpsampleFocalDiceFn, UpsampleFocalFn
+from ..functional import UpsampleCEDiceFn, UpsampleCEFn, UpsampleFocalDiceFn, UpsampleFocalFn, UpsampleLovaszFn
 
 
 class OrthTerm:
@@ -43,10 +43,19 @@ class OrthLoss(nn.Module):
     (1 - p_t)^(focal_gamma - 1), unbounded there.  With dice_weight > 0 only the cross-entropy part is modulated, the Dice term is unchanged; with mining on, the
     pixels are mined by the unmodulated probabilities first and the focal criterion runs on the mined label map; the auxiliary head uses the same criterion.  The dict
     gains no key: 'seg_loss' is the focal loss.  A plain float: no buffer, no state_dict key -- and, unlike the `weight` buffer, a kernel ARGUMENT: a captured
-    training step bakes the value in, so changing focal_gamma needs a new capture.  focal_gamma == 0 is the code path without it."""
+    training step bakes the value in, so changing focal_gamma needs a new capture.  focal_gamma == 0 is the code path without it.
+
+    `lovasz_weight` > 0 (a finite value >= 0) adds that multiple of the Lovasz-softmax loss (Berman et al.), the convex surrogate of the Jaccard index the runs are
+    scored by: seg_loss = cross-entropy [+ dice_weight * Dice] + lovasz_weight * Lovasz, for the main and the auxiliary head alike; the dict gains 'lovasz_loss', the
+    main head's unscaled term.  Per call and per head (under DDP per rank), over the valid pixels of the whole batch: for every class PRESENT in the labels, the Lovasz
+    extension of its Jaccard loss at the errors |[t == c] - p_c| of the softmax of the upsampled logits, mean over the present classes.  The kernels do not sort: the
+    errors are quantised to 1024 bins (include/segland_hip.h), which moves the loss by at most 1 / 2048 from the sorted one, and the gradient is the bin-averaged
+    subgradient.  No class weights on this term (`weight` does not enter it) and no per-image variant.  The cross-entropy (weighted, smoothed, focal) and the Dice term
+    are those of the criterion without it, bit for bit; the backward is one launch for all terms.  With mining on, the term runs on the head's mined label map, like
+    Dice.  A plain float: no buffer, no state_dict key.  lovasz_weight == 0 is the code path without it."""
 
     def __init__(self, ignore_index=255, reduction='mean', weight=None, label_smoothing=0.0, dice_weight=0.0, dice_smooth=1.0, ohem_thresh=None, ohem_min_kept=100000,
-                 focal_gamma=0.0):
+                 focal_gamma=0.0, lovasz_weight=0.0):
         super().__init__()
         if reduction != 'mean':
             raise ValueError('segland_amd OrthLoss implements reduction="mean" (what the reference uses)')
@@ -69,6 +78,9 @@ class OrthLoss(nn.Module):
         focal_gamma = float(focal_gamma)
         if focal_gamma != 0.0 and not 1.0 <= focal_gamma < float('inf'):
             raise ValueError('OrthLoss: focal_gamma %r is neither 0 (off) nor a finite value >= 1' % (focal_gamma,))
+        lovasz_weight = float(lovasz_weight)
+        if not 0.0 <= lovasz_weight < float('inf'):
+            raise ValueError('OrthLoss: lovasz_weight %r is not a finite value >= 0' % (lovasz_weight,))
         if weight is not None:
             weight = torch.as_tensor(weight, dtype=torch.float32).detach().clone().contiguous()
             if weight.dim() != 1 or weight.numel() == 0:
@@ -81,6 +93,7 @@ class OrthLoss(nn.Module):
         self.ohem_thresh = ohem_thresh
         self.ohem_min_kept = int(ohem_min_kept)
         self.focal_gamma = focal_gamma
+        self.lovasz_weight = lovasz_weight
         self.w = 10.0
         self._triu = {}
 
@@ -104,28 +117,38 @@ class OrthLoss(nn.Module):
         return mined, frac
 
     def head_loss(self, preds, target):
-        """(segmentation loss of one head, its unscaled Dice term or None, its kept fraction or None): with dice_weight > 0 one forward pass and one backward launch for
-        both terms; with mining on, both run on the head's mined label map; with focal_gamma > 0 the focal forms of the same two functions"""
+        """(segmentation loss of one head, its unscaled Dice term or None, its kept fraction or None): head_terms without the Lovasz entry"""
+        return self.head_terms(preds, target)[:3]
+
+    def head_terms(self, preds, target):
+        """(segmentation loss of one head, its unscaled Dice term or None, its kept fraction or None, its unscaled Lovasz term or None): with dice_weight > 0 one forward
+        pass and one backward launch for both terms; with mining on, both run on the head's mined label map; with focal_gamma > 0 the focal forms of the same two
+        functions; with lovasz_weight > 0 the same forward passes plus the Lovasz ones and one backward launch for all terms"""
         if self.weight is not None and self.weight.numel() != preds.shape[1]:
             raise ValueError('OrthLoss: %d class weights for %d logit channels' % (self.weight.numel(), preds.shape[1]))
         frac = None
         if self.ohem_thresh is not None:
             target, frac = self.mine(preds, target)
+        if self.lovasz_weight > 0.0:
+            ce, dice, lov = UpsampleLovaszFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.focal_gamma, self.weight, self.label_smoothing,
+                                                   self.dice_weight > 0.0, self.dice_smooth)
+            seg = ce if dice is None else torch.add(ce, dice, alpha=self.dice_weight)
+            return torch.add(seg, lov, alpha=self.lovasz_weight), dice, frac, lov
         if self.dice_weight > 0.0:
             if self.focal_gamma > 0.0:
                 ce, dice = UpsampleFocalDiceFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.focal_gamma, self.weight, self.label_smoothing, self.dice_smooth)
             else:
                 ce, dice = UpsampleCEDiceFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.weight, self.label_smoothing, self.dice_smooth)
-            return torch.add(ce, dice, alpha=self.dice_weight), dice, frac
+            return torch.add(ce, dice, alpha=self.dice_weight), dice, frac, None
         if self.focal_gamma > 0.0:
-            return UpsampleFocalFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.focal_gamma, self.weight, self.label_smoothing), None, frac
-        return UpsampleCEFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.weight, self.label_smoothing), None, frac
+            return UpsampleFocalFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.focal_gamma, self.weight, self.label_smoothing), None, frac, None
+        return UpsampleCEFn.apply(preds.float(), target.contiguous(), self.ignore_index, self.weight, self.label_smoothing), None, frac, None
 
     def seg_loss(self, preds, target):
         return self.head_loss(preds, target)[0]
 
     def forward(self, preds, target, is_ft=False, proto_sim=None, aux_preds=None):
-        seg_loss, dice, frac = self.head_loss(preds, target)
+        seg_loss, dice, frac, lov = self.head_terms(preds, target)
         orth_loss = self.get_orth_loss(proto_sim, is_ft=is_ft)
         if aux_preds is not None:
             aux_loss = self.seg_loss(aux_preds, target)
@@ -138,4 +161,6 @@ class OrthLoss(nn.Module):
             out['dice_loss'] = dice
         if frac is not None:
             out['ohem_frac'] = frac
+        if lov is not None:
+            out['lovasz_loss'] = lov
         return out

@@ -1175,6 +1175,47 @@ def upsample_focal_dice_bwd(logits, target, out, coef, gscale, ignore_index, gam
     return dl
 
 
+def upsample_lovasz_fwd(logits, target, ignore_index, want_hist=False):
+    """(float [2] = (Lovasz-softmax loss of the upsampled logits over the present classes of the batch, number of present classes), float [K, NB] = the backward's
+    table), as include/segland_hip.h defines them: every class's errors quantised to NB = sl_lovasz_bins() bins, two integer histograms per class and one scan, no sort
+    (at most 1 / (2 NB) from the exactly sorted loss).  No class weights and no per-image variant.  Three small launches and the histogram pass; no read-back.
+    want_hist: also a copy of the integer histograms, int32 [K, NB, 2] = (foreground, background) counts (the bits of the unsigned counters)."""
+    B, K, h, w = logits.shape
+    H, W = target.shape[1:]
+    L = _lib.lib()
+    nbytes = L.sl_lovasz_workspace(K)
+    if nbytes == 0:
+        check(L.sl_upsample_lovasz_hist(_p(logits), _p(target), B, K, h, w, H, W, ignore_index, None, 0, _s()), 'upsample_lovasz_hist')
+    ws = workspace(nbytes, logits.device)
+    tok = PROFILER.begin_bytes('upsample_lovasz_hist', logits.numel() * 4 + target.numel() * target.element_size())
+    check(L.sl_upsample_lovasz_hist(_p(logits), _p(target), B, K, h, w, H, W, ignore_index, _p(ws), nbytes, _s()), 'upsample_lovasz_hist')
+    PROFILER.end_bytes(tok)
+    out, table = _f32((2,), logits.device), _f32((K, L.sl_lovasz_bins()), logits.device)
+    check(L.sl_lovasz_scan(_p(ws), K, _p(out), _p(table), _s()), 'lovasz_scan')
+    if want_hist:
+        return out, table, ws[:K * table.shape[1] * 8].view(torch.int32).view(K, table.shape[1], 2).clone()
+    return out, table
+
+
+def upsample_lovasz_bwd(logits, target, out, coef, table, gscale, ignore_index, gamma=0.0, weight=None, label_smoothing=0.0):
+    """d (gscale[0] * cross-entropy + gscale[1] * dice + gscale[2] * lovasz) / d logits in one launch.  `out` (and `coef`, or None without a Dice term) from the forward
+    of the chosen cross-entropy form (upsample_ce_fwd / upsample_focal_fwd, or upsample_ce_dice_fwd / upsample_focal_dice_fwd), `table` from upsample_lovasz_fwd,
+    gscale float [3] on the device; gamma 0: no focal modulation."""
+    B, K, h, w = logits.shape
+    H, W = target.shape[1:]
+    if gscale.numel() != 3:
+        raise ValueError('upsample_lovasz_bwd: gscale holds the three upstream gradients (got %d values)' % gscale.numel())
+    if tuple(table.shape) != (K, _lib.lib().sl_lovasz_bins()) or table.dtype != torch.float32 or not table.is_contiguous():
+        raise ValueError('upsample_lovasz_bwd: table must be contiguous float32 [%d, %d] (got %s %s)' % (K, _lib.lib().sl_lovasz_bins(), table.dtype, tuple(table.shape)))
+    cw = _ce_dice_weight(weight, K, logits.device)
+    dl = torch.empty_like(logits)
+    tok = PROFILER.begin_bytes('upsample_lovasz_bwd', 2 * logits.numel() * 4 + target.numel() * target.element_size() + table.numel() * 4)
+    check(_lib.lib().sl_upsample_lovasz_bwd(_p(logits), _p(target), _p(cw), label_smoothing, gamma, _p(out), _p(coef), _p(table), _p(gscale), B, K, h, w, H, W,
+                                            ignore_index, _p(dl), _s()), 'upsample_lovasz_bwd')
+    PROFILER.end_bytes(tok)
+    return dl
+
+
 def ohem_prob(logits, target, ignore_index):
     """float [B, H, W]: the softmax probability of the true class of every valid pixel of the upsampled logits (the forward kernel's arithmetic), 2.0 elsewhere"""
     B, K, h, w = logits.shape
