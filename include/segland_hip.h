@@ -778,6 +778,33 @@ int sl_augment_batch(const void* tiles_dev, const int* flip_rot_dev, int B, int 
  * SL_EINVAL before any launch for a null tiles_dev / mean3_host / std3_host / out_img and for B, crop_h or crop_w <= 0 (B <= 65535). */
 int sl_augment_batch_ex(const void* tiles_dev, int B, int crop_h, int crop_w, const double* mean3_host, const double* std3_host, int ignore_label,
                         const uint8_t* label_lut_dev, float* out_img, long long* out_lbl, sl_stream_t stream);
+/* The preparation of sl_augment_batch_ex with an arbitrary-angle rotation about the crop centre and a Gaussian blur added: the counterparts of random_rotate (cv2.warpAffine) and
+ * random_gaussian (cv2.GaussianBlur) of dataset/base_dataset.py:112-132, but NOT OpenCV's fixed-point arithmetic -- this comment is the definition.  One launch, no atomics, no
+ * global intermediate buffer.  The arguments are sl_augment_batch_ex's; tiles_dev: device array of B 128-byte records whose first 72 bytes are laid out as the 80-byte record's:
+ *   offset 72  int rotate            0 or 1
+ *          76  int blur_k            0 (off) or the odd kernel size 3, 5, 7, 9, 11; the crop sides must exceed (blur_k - 1) / 2
+ *          80  double cos_t, sin_t   of the angle (positive: counter-clockwise on the screen, as cv2.getRotationMatrix2D)
+ *          96  float blur_w[6]       half kernel, centre first; entries beyond (blur_k - 1) / 2 are 0
+ *         120  int reserved[2]
+ * Per output pixel (b, y, x):
+ *  1. (r, c) from (y, x) by undoing rot90 x k and then the flip, as sl_augment_batch.
+ *  2. Crop-frame coordinates.  rotate == 0: U = w_off + c, V = h_off + r, and steps 2-4 of sl_augment_batch_ex apply unchanged, in integers: with rotate = blur_k = 0 the output
+ *     equals sl_augment_batch_ex's bit for bit.  rotate != 0, everything in double (the inverse of cv2.getRotationMatrix2D((crop_w / 2, crop_h / 2), angle, 1)):
+ *     dx = c - crop_w / 2, dy = r - crop_h / 2, u = crop_w / 2 + (cos_t dx - sin_t dy), v = crop_h / 2 + (sin_t dx + cos_t dy), U = w_off + u, V = h_off + v.
+ *  3. Inside iff 0 <= floor(U + 0.5) < Ws and 0 <= floor(V + 0.5) < Hs; anything else is the padding (image exactly 0 BEFORE normalisation, label ignore_label, no jitter).
+ *  4. Source coordinate (align_corners=False, double): sx = ((U + 0.5) W) / Ws - 0.5, sy likewise.  Image: sxc = clamp(sx, 0, W - 1), x0 = floor(sxc), x1 = min(x0 + 1, W - 1),
+ *     fx = (float)(sxc - x0), rows likewise, then the four-tap blend of sl_augment_batch_ex in float.  Label: lx = clamp(floor(sx + 0.5), 0, W - 1), ly likewise, then
+ *     label_lut_dev.  Every row index is clamped to [row0, row0 + rows) and every column index to [0, W) before it is dereferenced.
+ *  5. If blur_k != 0: a separable Gaussian of radius R = (blur_k - 1) / 2 over the crop-frame image of steps 1-4 (R, G, B in [0, 255], before the jitter), in float: first
+ *     along c, h(r, c) = w[0] p(r, c) + sum_{i=1..R} w[i] (p(r, c - i) + p(r, c + i)) summed in that order, then along r, the same form over h.  Border: reflect-101 at the
+ *     crop's edges (-i -> i, n - 1 + i -> n - 1 - i).  Kernel and border rule are symmetric, so stating the blur on the (r, c) grid, before the flip and rot90 are re-applied,
+ *     equals stating it on the output grid.  Taps that fall on padding read 0; padding pixels themselves stay exactly 0 (the blurred value is written for inside pixels only);
+ *     labels are never blurred.  The host computes the weights in double and stores them as float: sigma = 0.3 ((K - 1) / 2 - 1) + 0.8 (OpenCV's rule for sigma <= 0),
+ *     g_i = exp(-i^2 / (2 sigma^2)), w_i = g_i / (g_0 + 2 sum_{i>=1} g_i).
+ *  6. The jitter and the tail, steps 5 and 6 of sl_augment_batch_ex.
+ * SL_EINVAL before any launch for the arguments sl_augment_batch_ex refuses. */
+int sl_augment_batch_geo(const void* tiles_dev, int B, int crop_h, int crop_w, const double* mean3_host, const double* std3_host, int ignore_label,
+                         const uint8_t* label_lut_dev, float* out_img, long long* out_lbl, sl_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ import numpy as np
 from torch.utils import data
 
 from . import tiff
-from .augment import TileAugmenter, augment_kwargs, draw_train_params, remap_lut, source_rows
+from .augment import TileAugmenter, augment_kwargs, draw_train_params, remap_lut, source_rows_geo
 
 BASE_CLASSES, NOVEL_CLASSES, NUM_CLASSES = set(range(1, 8)), set(range(8, 12)), 11          # oem.py:13,32,34
 MEAN = STD = (0.5, 0.5, 0.5)                                                                   # oem.py:26-27
@@ -41,20 +41,21 @@ class _Raw(data.Dataset):
 
 class GFSSegTrain(_Raw):
     """dataset/oem.py:11-76.  __getitem__ -> (image uint8 [H,W,3], label uint8 [H,W], (h_off, w_off, flip, k), id).
-    augment: None, or {'scale': (lo, hi), 'jitter': (b, c, s)} -- random rescale before the crop / colour jitter (mode 'train' only; the draws are then augment.ExtDraw)."""
+    augment: None, or {'scale': (lo, hi), 'jitter': (b, c, s), 'rotate': (lo, hi[, p]), 'blur': (K[, p])} -- random rescale before the crop / colour jitter / rotation about the
+    crop centre / Gaussian blur (mode 'train' only; the draws are then augment.ExtDraw, or augment.GeoDraw where a rotation or a blur fired)."""
     accepts_augment = True
 
     def __init__(self, root, list_path, fold, shot=1, mode='train', crop_size=(512, 512), ignore_label=255, base_size=(1024, 1024),
                  resize_label=False, filter=False, seed=123, augment=None):
         _decoder()
         assert mode in ('train', 'val_supp')
-        self.aug_kw = augment_kwargs(augment)
+        self.aug_kw = augment_kwargs(augment, crop_size)
         self.root, self.crop_size, self.ignore_label, self.mode = root, tuple(crop_size), ignore_label, mode
         path = os.path.join(os.path.dirname(list_path), 'train.txt')
         if not os.path.exists(path):
             raise FileNotFoundError(path)
         self.data_list = open(path).read().splitlines()
-        self.collate_fn = RawCollate(self.crop_size[0])
+        self.collate_fn = RawCollate(*self.crop_size)
 
     def __len__(self):
         return len(self.novel_classes) if self.mode == 'val_supp' else len(self.data_list)        # oem.py:46-50
@@ -101,14 +102,15 @@ class GFSSegVal(_Raw):
         return TileAugmenter(size, MEAN, STD, self.ignore_label, lut=remap_lut(self.base_classes, self.novel_classes, self.use_base, self.use_novel), device=device)
 
 
-def crop_rows(img, lab, prm, crop_h):
+def crop_rows(img, lab, prm, crop_h, crop_w=None):
     """Only the rows the crop will read: a tile at least as tall as the crop is never padded vertically (base_dataset.py:88-104 pads tiles SMALLER than the crop),
     so rows [h_off, h_off + crop_h) -- a contiguous slice of the row-major tile -- are all the preparation kernel looks at; the draw's h_off becomes 0.
     An extended draw (rescale / jitter, augment.ExtDraw) keeps its h_off, which lives in the rescaled grid: the rows its bilinear taps read (augment.source_rows) are kept and
-    the draw records where they start (row0) next to the full tile height."""
+    the draw records where they start (row0) next to the full tile height.  A rotated draw (augment.GeoDraw) likewise, with the rows of augment.source_rows_geo, which needs the
+    crop's width too (crop_w; default: a square crop)."""
     if len(prm) > 4:
-        if crop_h and prm.row0 == 0 and img.shape[0] == prm.H and 0 <= prm.h_off < prm.Hs:
-            row0, rows = source_rows(prm.H, prm.Hs, prm.h_off, crop_h)
+        if crop_h and prm.row0 == 0 and img.shape[0] == prm.H and (getattr(prm, 'rotate', 0) or 0 <= prm.h_off < prm.Hs):
+            row0, rows = source_rows_geo(prm, crop_h, crop_w or crop_h)
             img = img[row0:row0 + rows]
             lab = None if lab is None else lab[row0:row0 + rows]
             prm = prm._replace(row0=row0)
@@ -159,13 +161,13 @@ class RawCollate:
     """Keeps the variable-size raw tiles of a batch apart (torch's default collate would try to stack them): (PackedTiles, [draws], [ids]).  Runs in the worker:
     the tiles are cut down to the rows their crops read when `crop_h` is given (training readers) and leave the worker as one shared-memory buffer."""
 
-    def __init__(self, crop_h=None):
-        self.crop_h = crop_h
+    def __init__(self, crop_h=None, crop_w=None):
+        self.crop_h, self.crop_w = crop_h, crop_w
 
     def __call__(self, batch):
         tiles, params = [], []
         for img, lab, prm, _ in batch:
-            img, lab, prm = crop_rows(img, lab, prm, self.crop_h)
+            img, lab, prm = crop_rows(img, lab, prm, self.crop_h, self.crop_w)
             tiles.append((img, lab))
             params.append(prm)
         return PackedTiles(tiles), params, [b[3] for b in batch]

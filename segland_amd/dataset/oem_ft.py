@@ -45,14 +45,14 @@ class PairCollate:
     """(PackedTiles of the 2B tiles in the order novel_0, base_0, novel_1, base_1, ..., [(novel draws, base draws)], [ids]): like oem.RawCollate the tiles are cut
     down to the rows their crops read and leave the worker as one shared-memory buffer.  `pairs[2 * i]` / `pairs[2 * i + 1]` are pair i's novel / base tile."""
 
-    def __init__(self, crop_h=None):
-        self.crop_h = crop_h
+    def __init__(self, crop_h=None, crop_w=None):
+        self.crop_h, self.crop_w = crop_h, crop_w
 
     def __call__(self, batch):
         tiles, params = [], []
         for (nov, base), (pn, pb), _ in batch:
-            ni, nl, pn = crop_rows(nov[0], nov[1], pn, self.crop_h)
-            bi, bl, pb = crop_rows(base[0], base[1], pb, self.crop_h)
+            ni, nl, pn = crop_rows(nov[0], nov[1], pn, self.crop_h, self.crop_w)
+            bi, bl, pb = crop_rows(base[0], base[1], pb, self.crop_h, self.crop_w)
             tiles += [(ni, nl), (bi, bl)]
             params.append((pn, pb))
         return PackedTiles(tiles), params, [b[2] for b in batch]
@@ -64,18 +64,18 @@ pair_collate = PairCollate()
 class PairReader(_Raw):
     """The list logic and the pair rule, independent of how a tile is decoded (`read_image(id) -> uint8 [H,W,3]`, `read_label(id) -> uint8 [H,W]`)."""
     pair_tiles = True
-    accepts_augment = True        # augment={'scale': (lo, hi), 'jitter': (b, c, s)}: both tiles of a pair get their own rescale / jitter draws
+    accepts_augment = True        # augment={'scale': (lo, hi), 'jitter': (b, c, s), 'rotate': (lo, hi[, p]), 'blur': (K[, p])}: both tiles of a pair get their own draws
     aug_kw = {}
     collate_fn = staticmethod(pair_collate)
 
     def _init_lists(self, list_path, shot, mode, crop_size, ignore_label, seed, filter, use_base, augment=None):
-        self.aug_kw = augment_kwargs(augment)
+        self.aug_kw = augment_kwargs(augment, crop_size)
         if mode == 'val_supp':
             raise RuntimeError("oem_ft.GFSSegTrain(mode='val_supp') rotates support tiles with cv2.warpAffine (oem_ft.py:247, base_dataset.py:117-132); "
                                'it is not on the ft_pop path and is not built')
         assert mode == 'train'
         self.list_path, self.shot, self.mode, self.crop_size, self.ignore_label, self.use_base = list_path, shot, mode, tuple(crop_size), ignore_label, use_base
-        self.collate_fn = PairCollate(self.crop_size[0])
+        self.collate_fn = PairCollate(*self.crop_size)
         self.base_classes, self.novel_classes = set(BASE_CLASSES), set(NOVEL_CLASSES)
         filter_flag = bool(filter)
         list_dir = os.path.dirname(list_path) + ('_filter' if filter_flag else '')

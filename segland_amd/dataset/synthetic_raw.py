@@ -34,8 +34,8 @@ class GFSSegTrain(_Base):
                  length=64, seed=0, augment=None, **kw):
         super().__init__(length, (crop_size[0] + 96, crop_size[1] + 64), seed)
         self.crop_size = tuple(crop_size)
-        self.aug_kw = augment_kwargs(augment)
-        self.collate_fn = RawCollate(self.crop_size[0])
+        self.aug_kw = augment_kwargs(augment, crop_size)
+        self.collate_fn = RawCollate(*self.crop_size)
 
     def __getitem__(self, i):
         img, lab = self._tile(i, 8)

@@ -124,27 +124,68 @@ def aug_jitter(v):
     return a
 
 
+def aug_rotate(v):
+    """--aug-rotate: '' -> () (off); 'LO,HI[,P]' -> (lo, hi, p): the range in degrees the rotation about the crop centre is drawn from, -180 <= LO <= HI <= 180, applied with
+    probability P in (0, 1] (default 0.5, as the reference's random_rotate)."""
+    if isinstance(v, (tuple, list)):
+        return tuple(float(x) for x in v)
+    if not v.strip():
+        return ()
+    try:
+        r = tuple(float(x) for x in v.split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError('comma-separated floats LO,HI[,P] expected (got %r)' % (v,))
+    if len(r) == 2:
+        r += (0.5,)
+    if len(r) != 3 or not (-180.0 <= r[0] <= r[1] <= 180.0) or not (0.0 < r[2] <= 1.0):
+        raise argparse.ArgumentTypeError('the rotation range LO,HI[,P] must satisfy -180 <= LO <= HI <= 180 and 0 < P <= 1 (got %r)' % (v,))
+    return r
+
+
+def aug_blur(v):
+    """--aug-blur: '' -> () (off); 'K[,P]' -> (K, p): the odd size 3, 5, 7, 9 or 11 of the Gaussian blur, applied with probability P in (0, 1] (default 0.5, as the
+    reference's random_gaussian)."""
+    if isinstance(v, (tuple, list)):
+        return tuple(int(x) if i == 0 else float(x) for i, x in enumerate(v))
+    if not v.strip():
+        return ()
+    try:
+        a = tuple(float(x) for x in v.split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError('an odd size and an optional probability K[,P] expected (got %r)' % (v,))
+    if len(a) == 1:
+        a += (0.5,)
+    if len(a) != 2 or a[0] not in (3.0, 5.0, 7.0, 9.0, 11.0) or not (0.0 < a[1] <= 1.0):
+        raise argparse.ArgumentTypeError('the blur K[,P] needs an odd K in 3..11 and 0 < P <= 1 (got %r)' % (v,))
+    return (int(a[0]), a[1])
+
+
+def _augment_flags(args):
+    return (('--aug-scale', 'scale', aug_scale(getattr(args, 'aug_scale', ()) or ())), ('--aug-jitter', 'jitter', aug_jitter(getattr(args, 'aug_jitter', ()) or ())),
+            ('--aug-rotate', 'rotate', aug_rotate(getattr(args, 'aug_rotate', ()) or ())), ('--aug-blur', 'blur', aug_blur(getattr(args, 'aug_blur', ()) or ())))
+
+
 def augment_option(args, reader, dataset):
-    """The `augment=` keyword of a training reader from --aug-scale / --aug-jitter: {} when both are off (the reader is called as it always was), else
-    {'augment': {'scale': ..., 'jitter': ...}}.  A reader that does not hand raw tiles to the GPU preparation kernel cannot take the option: a ValueError names it and the flag."""
-    scale, jitter = aug_scale(getattr(args, 'aug_scale', ()) or ()), aug_jitter(getattr(args, 'aug_jitter', ()) or ())
-    if not scale and not jitter:
+    """The `augment=` keyword of a training reader from --aug-scale / --aug-jitter / --aug-rotate / --aug-blur: {} when all are off (the reader is called as it always was), else
+    {'augment': {'scale': ..., 'jitter': ...}}, with the keys 'rotate' / 'blur' only when their flag is on.  A reader that does not hand raw tiles to the GPU preparation kernel
+    cannot take the option: a ValueError names it and the flags."""
+    flags = _augment_flags(args)
+    if not any(on for _, _, on in flags):
         return {}
     if not getattr(reader, 'accepts_augment', False):
-        flags = ' / '.join(f for f, on in (('--aug-scale', scale), ('--aug-jitter', jitter)) if on)
         raise ValueError("dataset '%s' cannot take %s: its training reader does not emit raw tiles for the GPU preparation kernel (csrc/augment.hip); "
-                         'use oem, synthetic_tiff or synthetic_raw' % (dataset, flags))
-    return {'augment': {'scale': scale or None, 'jitter': jitter or None}}
+                         'use oem, synthetic_tiff or synthetic_raw' % (dataset, ' / '.join(f for f, _, on in flags if on)))
+    return {'augment': {key: on or None for _, key, on in flags if on or key in ('scale', 'jitter')}}
 
 
 def log_augment_options(args):
-    """One line at start, only when --aug-scale or --aug-jitter is on."""
-    scale, jitter = aug_scale(getattr(args, 'aug_scale', ()) or ()), aug_jitter(getattr(args, 'aug_jitter', ()) or ())
-    if scale or jitter:
+    """One line at start, only when one of the four augmentation flags is on; it names the ones that are."""
+    scale, jitter, rotate, blur = (on for _, _, on in _augment_flags(args))
+    parts = ((' random rescale %g..%g before the crop' % scale if scale else ''), (' colour jitter: brightness %g, contrast %g, saturation %g' % jitter if jitter else ''),
+             (' rotation by %g..%g degrees about the crop centre (probability %g)' % rotate if rotate else ''), (' %dx%d Gaussian blur (probability %g)' % (blur[0], blur[0], blur[1]) if blur else ''))
+    if any(parts):
         import logging
-        logging.getLogger('Segmentation').info('tile augmentation in the preparation kernel:' + (' random rescale %g..%g before the crop' % scale if scale else '')
-                                               + (',' if scale and jitter else '')
-                                               + (' colour jitter: brightness %g, contrast %g, saturation %g' % jitter if jitter else ''))
+        logging.getLogger('Segmentation').info('tile augmentation in the preparation kernel:' + ','.join(p for p in parts if p))
 
 
 def ema_decay(v):
@@ -254,6 +295,12 @@ _COMMON = [
                                                           'is taken, inside the tile preparation kernel; 0 < LO <= HI <= 4 (PSPNet: 0.5,2.0); raw-tile datasets only; default: off.')),
     ('--aug-jitter', dict(type=aug_jitter, default='', help='B,C,S: random brightness, contrast and saturation of every training crop, inside the tile preparation kernel; '
                                                             'the amplitudes, each in [0, 1) (0.2,0.2,0.2 is common); raw-tile datasets only; default: off.')),
+    ('--aug-rotate', dict(type=aug_rotate, default='', help='LO,HI[,P]: with probability P (default 0.5) every training crop is rotated about its centre by an angle in degrees '
+                                                            'from this range (image bilinear, labels nearest, border 0 / ignore), inside the tile preparation kernel; '
+                                                            '-180 <= LO <= HI <= 180 (the reference: -10,10); raw-tile datasets only; default: off.')),
+    ('--aug-blur', dict(type=aug_blur, default='', help='K[,P]: with probability P (default 0.5) every training crop gets a K x K Gaussian blur (sigma from K by the rule of '
+                                                        'OpenCV, reflect-101 border), inside the tile preparation kernel; K in 3, 5, 7, 9, 11 (the reference: 5); raw-tile '
+                                                        'datasets only; default: off.')),
     ('--ema-decay', dict(type=float, default=0.0, help='exponential moving average of the trainable weights and the training BatchNorm statistics, updated after every '
                                                        'optimizer step; validation and best.pth use the average, epoch_N_ema.pth holds it next to the raw epoch_N.pth; '
                                                        'strictly between 0 and 1 (0.999 is common); default 0: off.')),

@@ -14,8 +14,10 @@ whatever the worker count.  The steady state is measured with --shot large enoug
 
 --aug-scale LO,HI / --aug-jitter B,C,S: the training drivers' flags -- the readers draw a rescale / a colour jitter per tile and the batch goes through sl_augment_batch_ex
 (a rescaled crop reads ch / s + 2 source rows instead of ch: the collate cuts the tile down to those).
+--aug-rotate LO,HI[,P] / --aug-blur K[,P]: likewise a rotation about the crop centre / a Gaussian blur; a batch in which one fired goes through sl_augment_batch_geo (a
+rotated crop reads the rows of its bounding box).
 
-    python tools/feed_rate.py [--workers 16] [--batch 16] [--batches 40] [--pairs] [--shot 40] [--source tiff|randint] [--compression tiff_lzw] [--aug-scale 0.5,2.0] [--aug-jitter 0.2,0.2,0.2]
+    python tools/feed_rate.py [--workers 16] [--batch 16] [--batches 40] [--pairs] [--shot 40] [--source tiff|randint] [--compression tiff_lzw] [--aug-scale 0.5,2.0] [--aug-jitter 0.2,0.2,0.2] [--aug-rotate=-10,10] [--aug-blur 5]
 """
 import argparse
 import os
@@ -41,11 +43,15 @@ def main():
     p.add_argument('--compression', default=None, help='tiff_lzw | tiff_adobe_deflate | packbits (default: uncompressed)')
     p.add_argument('--files', type=int, default=96, help='tiff: tiles written to disk')
     p.add_argument('--repeat', type=int, default=8, help='tiff, base tiles: how often train.txt lists each file (epoch = files x repeat samples: a 96-sample epoch is six batches of 16,\n                   each made by ONE worker -- the loader then measures epoch restarts, not the feed)')
-    from segland_amd.drivers import aug_jitter, aug_scale
+    from segland_amd.drivers import aug_blur, aug_jitter, aug_rotate, aug_scale
     p.add_argument('--aug-scale', type=aug_scale, default='')
     p.add_argument('--aug-jitter', type=aug_jitter, default='')
+    p.add_argument('--aug-rotate', type=aug_rotate, default='')
+    p.add_argument('--aug-blur', type=aug_blur, default='')
     a = p.parse_args()
-    augment = {'scale': a.aug_scale or None, 'jitter': a.aug_jitter or None} if (a.aug_scale or a.aug_jitter) else None
+    geo = bool(a.aug_rotate or a.aug_blur)
+    augment = ({'scale': a.aug_scale or None, 'jitter': a.aug_jitter or None, 'rotate': a.aug_rotate or None, 'blur': a.aug_blur or None}
+               if (a.aug_scale or a.aug_jitter or geo) else None)
     dev = torch.device('cuda', 0)
     decode = 'torch.randint stand-in'
     if a.source == 'tiff':
@@ -113,7 +119,7 @@ def main():
     cpus = len(os.sched_getaffinity(0))
     unit = 'pairs/s' if a.pairs else 'tiles/s'
     print('feed_rate: %s%s, raw %dx%d -> crop %dx%d, batch %d, %d samples per epoch, %s: GPU stage alone (H2D + sl_augment_batch%s) %.0f %s; whole feed with %d workers on %d host cores %.0f %s'
-          % ('fine-tune pairs' if a.pairs else 'base tiles', (' with rescale %s jitter %s' % (a.aug_scale or 'off', a.aug_jitter or 'off')) if augment else '', a.tile, a.tile, a.crop, a.crop, a.batch, len(ds), decode, '_ex' if augment else '', gpu_rate / per_sample, unit, a.workers, cpus, feed_rate / per_sample, unit))
+          % ('fine-tune pairs' if a.pairs else 'base tiles', (' with rescale %s jitter %s' % (a.aug_scale or 'off', a.aug_jitter or 'off') + (' rotation %s blur %s' % (a.aug_rotate or 'off', a.aug_blur or 'off') if geo else '')) if augment else '', a.tile, a.tile, a.crop, a.crop, a.batch, len(ds), decode, '_geo' if geo else '_ex' if augment else '', gpu_rate / per_sample, unit, a.workers, cpus, feed_rate / per_sample, unit))
     if a.source == 'tiff':
         import shutil
         shutil.rmtree(root, ignore_errors=True)
