@@ -609,6 +609,19 @@ int sl_iou_hist(const uint8_t* pred, const int64_t* target, long long n, int K, 
  * caller zeroes cm). */
 int sl_confusion_matrix(const uint8_t* pred, const int64_t* target, long long n, int K, int ignore_index, long long* cm,
                         sl_stream_t stream);
+/* Boundary IoU (Cheng et al., CVPR 2021) and trimap confusion counts of a batch of label maps in one launch (the project's own contract, no upstream
+ * counterpart).  pred: uint8 [B][H][W]; target: int64 [B][H][W].  Effective labels, per image:
+ *   T = target where 0 <= target < K and target != ignore_index, else IGN;   P = IGN where T == IGN or pred >= K, else pred;
+ *   positions outside the image carry OUT, which differs from every label and from IGN; an image's neighbourhood never reaches into the next image of the batch.
+ * band_L(y, x) is true iff some (dy, dx) in [-d, d]^2 has L(y + dy, x + dx) != L(y, x) (a Chebyshev square; crossing the image edge counts).  With Gb = band_T and
+ * Pb = band_P, ADDED over the pixels with T != IGN (int64 counts; the caller zeroes the buffers once and may accumulate batches):
+ *   counts[0][c] += [T == c and P == c and Gb and Pb]     counts[1][c] += [T == c and Gb]     counts[2][c] += [P == c and Pb]
+ *   band_cm[t][p] += [T == t and P == p and Gb]           (the confusion matrix of the pixels within d of a ground-truth border)
+ * Boundary IoU of class c = counts[0][c] / (counts[1][c] + counts[2][c] - counts[0][c]).  Without ignored pixels, counts are those of the paper's mask_to_boundary
+ * per class (1 px zero border, d 3x3 erosions, boundary = mask - eroded).  B, H, W >= 1 (any H, W: smaller than the tile, smaller than d), 1 <= K <= 64,
+ * 1 <= d <= 32 pixels, no NULL pointer, else SL_EINVAL before any launch with the value in the message.  Integer atomics only: two runs give the same counts. */
+int sl_boundary_counts(const uint8_t* pred, const int64_t* target, int B, int H, int W, int K, int ignore_index, int d, long long* counts, long long* band_cm,
+                       sl_stream_t stream);
 /* networks/pspnet.py:7-15 masked_average_pooling (dead code upstream; prototype-init utility here):
  * proto[c] = mean_b( sum_hw f*m / (sum_hw m + 1e-5) ), m = bilinear(mask, align_corners=True) at feature size.
  * feature: NHWC dtype [B][h][w][C]; mask: float [B][H][W]. */

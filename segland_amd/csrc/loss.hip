@@ -1033,6 +1033,103 @@ __global__ __launch_bounds__(256) void confusion_kernel(const uint8_t* __restric
   for (int i = threadIdx.x; i < K * K; i += 256) if (hc[i]) atomicAdd(&cm[i], (unsigned long long)hc[i]);
 }
 
+// Boundary IoU (Cheng et al.) and trimap counts of sl_boundary_counts; the contract is in include/segland_hip.h.  One block per BD_TILE x BD_TILE output tile of one
+// image.  The band test "some label in the (2d+1)^2 square differs from the centre" is separable, and with one bit per pair of neighbours it needs no loop over d:
+//   row pass     lane = column.  e(c) = [L(r,c) != L(r,c+1)] over the RW = BD_TILE + 2d columns of region row r is two ballots (128 bits); the 2d bits from x on are zero
+//                iff the row window [x, x+2d] of the region, centred on tile column x, holds one label.  v(r,x) = centre label | BD_MIX if it does not.
+//   column pass  lane = row.  g(r) = [v(r,x) != v(r+1,x) or either carries BD_MIX] down column x is two ballots again; the 2d bits from y on are zero iff the square
+//                around tile pixel (y,x) holds one label: the pixel is in the band iff they are not.  The centre label is v(y+d,x) without BD_MIX.
+// Positions outside the image carry BD_OUT, so crossing the image edge is a difference like any other, and a block reads its own image only.  Labels are bytes:
+// 0..63 a class, BD_IGN, BD_OUT (all below BD_MIX).  The T region is loaded first and run through the row pass, then every thread turns ITS bytes of the region into
+// P in place (P = BD_IGN where T is): one region buffer serves both maps.  Dynamic LDS at d = 32, K = 64: histogram (3K + K^2) x 4 = 17 152 B, region 128 x 128 =
+// 16 384 B, two v arrays 128 x BD_VP = 17 408 B: 50 944 B, below the 64 KiB that need no opt-in.  At d = 3, K = 12: 720 + 5 040 + 9 520 = 15 280 B, and the 32 waves of
+// a CU, not the LDS, bound the blocks per CU.  Only band pixels touch the histogram.  Integer atomics throughout: the sums do not depend on the block order.
+constexpr int BD_TILE = 64;            // a wave's 64 lanes are the columns of a tile row (row pass) and the rows of a tile column (column pass)
+constexpr int BD_VP = BD_TILE + 4;     // pitch of v in bytes: 17 words, so the column pass (lane = row) reads 32 different banks per lane group
+constexpr int BD_DMAX = 32;            // 2d <= 64: a window's pair bits fit one 64-bit word cut out of the two ballots
+constexpr int BD_IGN = 64, BD_OUT = 65, BD_MIX = 0x80;
+
+// bits [i, i + 2d) of the 128-bit word (hi, lo), i in [0, 64): any set?  mask = the low 2d bits.
+__device__ __forceinline__ bool bd_window(unsigned long long lo, unsigned long long hi, int i, unsigned long long mask) {
+  const unsigned long long w = (lo >> i) | (i ? hi << (64 - i) : 0ull);
+  return (w & mask) != 0ull;
+}
+
+__device__ __forceinline__ void bd_row_pass(const uint8_t* __restrict__ reg, uint8_t* __restrict__ v, int RW, int RP, int d, unsigned long long mask) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int r = wave; r < RW; r += 4) {                              // the region is square: RW rows too
+    const uint8_t* row = reg + r * RP;
+    const unsigned long long lo = __ballot(row[lane] != row[lane + 1]);                                         // RW >= 66: column lane + 1 exists
+    const unsigned long long hi = __ballot(lane + 65 < RW && row[lane + 64] != row[lane + 65]);
+    v[r * BD_VP + lane] = (uint8_t)(row[lane + d] | (bd_window(lo, hi, lane, mask) ? BD_MIX : 0));
+  }
+}
+
+__device__ __forceinline__ bool bd_pair(const uint8_t* __restrict__ v, int r, int x) {
+  const int a = v[r * BD_VP + x], b = v[(r + 1) * BD_VP + x];
+  return a != b || ((a | b) & BD_MIX);
+}
+
+__global__ __launch_bounds__(256) void boundary_counts_kernel(const uint8_t* __restrict__ pred, const int64_t* __restrict__ tgt, int H, int W, int K, int ignore, int d,
+                                                              int tiles_x, int tiles_y, unsigned long long* __restrict__ counts,
+                                                              unsigned long long* __restrict__ band_cm) {
+  extern __shared__ unsigned int bd_lds[];
+  const int nh = 3 * K + K * K, RW = BD_TILE + 2 * d, RP = (RW + 3) & ~3;
+  unsigned int* hb = bd_lds;                                         // [3][K] counts, then [K][K] band_cm
+  uint8_t* reg = (uint8_t*)(hb + nh);                                // [RW][RP]
+  uint8_t* vT = reg + RW * RP;                                       // [RW][BD_VP]
+  uint8_t* vP = vT + RW * BD_VP;
+  int tile = blockIdx.x;
+  const int tx = tile % tiles_x; tile /= tiles_x;
+  const int ty = tile % tiles_y, b = tile / tiles_y;
+  const int x0 = tx * BD_TILE - d, y0 = ty * BD_TILE - d;            // image position of region (0, 0)
+  const size_t img = (size_t)b * H * W;
+  const unsigned long long mask = 2 * d == 64 ? ~0ull : (1ull << (2 * d)) - 1ull;
+  for (int i = threadIdx.x; i < nh; i += 256) hb[i] = 0;
+  for (int i = threadIdx.x; i < RW * RW; i += 256) {
+    const int r = i / RW, c = i - r * RW, gy = y0 + r, gx = x0 + c;
+    int code = BD_OUT;
+    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+      const long long t = tgt[img + (size_t)gy * W + gx];
+      code = (t >= 0 && t < K && t != ignore) ? (int)t : BD_IGN;
+    }
+    reg[r * RP + c] = (uint8_t)code;
+  }
+  __syncthreads();
+  bd_row_pass(reg, vT, RW, RP, d, mask);
+  __syncthreads();
+  for (int i = threadIdx.x; i < RW * RW; i += 256) {                 // the same thread owns the same bytes as above: T -> P in place
+    const int r = i / RW, c = i - r * RW, gy = y0 + r, gx = x0 + c;
+    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+      const int p = pred[img + (size_t)gy * W + gx];
+      if (reg[r * RP + c] == BD_IGN || p >= K) reg[r * RP + c] = BD_IGN; else reg[r * RP + c] = (uint8_t)p;
+    }
+  }
+  __syncthreads();
+  bd_row_pass(reg, vP, RW, RP, d, mask);
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // x and the loop bound are the same in every lane of a wave, so each iteration is entered by whole waves and the four ballots see all 64 lanes.  Everything that depends
+  // on the lane (the rows past H, the ignored pixels: the `continue`s below) must stay BELOW the ballots: a lane that left before them would drop its pair bit.
+  for (int x = wave; x < BD_TILE && tx * BD_TILE + x < W; x += 4) {
+    const unsigned long long gl = __ballot(bd_pair(vT, lane, x)), gh = __ballot(lane + 65 < RW && bd_pair(vT, lane + 64, x));
+    const unsigned long long pl = __ballot(bd_pair(vP, lane, x)), ph = __ballot(lane + 65 < RW && bd_pair(vP, lane + 64, x));
+    if (ty * BD_TILE + lane >= H) continue;
+    const int t = vT[(lane + d) * BD_VP + x] & (BD_MIX - 1), p = vP[(lane + d) * BD_VP + x] & (BD_MIX - 1);
+    if (t == BD_IGN) continue;                                       // then P is BD_IGN too: the pixel is in no count
+    const bool gb = bd_window(gl, gh, lane, mask), pb = bd_window(pl, ph, lane, mask);
+    if (gb) {
+      atomicAdd(&hb[K + t], 1u);
+      if (p < K) atomicAdd(&hb[3 * K + t * K + p], 1u);
+    }
+    if (pb && p < K) atomicAdd(&hb[2 * K + p], 1u);
+    if (gb && pb && p == t) atomicAdd(&hb[t], 1u);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nh; i += 256)
+    if (hb[i]) atomicAdd(i < 3 * K ? &counts[i] : &band_cm[i - 3 * K], (unsigned long long)hb[i]);
+}
+
 template <typename T>
 __global__ void masked_avg_pool_kernel(const T* __restrict__ feat, const float* __restrict__ mask, int B, int h, int w, int C, int H, int W,
                                        float sy, float sx, float* __restrict__ proto) {
@@ -1681,6 +1778,22 @@ extern "C" int sl_confusion_matrix(const uint8_t* pred, const int64_t* target, l
   SL_REQUIRE(pred && target && cm && n > 0 && K >= 1 && K <= 64, "confusion_matrix: bad args");
   return sl_launch("confusion_kernel", confusion_kernel, dim3(ce_blocks(n)), dim3(256), (size_t)K * K * sizeof(unsigned), (hipStream_t)stream, pred, target, n, K, ignore_index,
                    (unsigned long long*)cm);
+}
+
+extern "C" int sl_boundary_counts(const uint8_t* pred, const int64_t* target, int B, int H, int W, int K, int ignore_index, int d, long long* counts,
+                                  long long* band_cm, sl_stream_t stream) {
+  SL_REQUIRE(pred && target && counts && band_cm, "boundary_counts: NULL pointer (pred %p, target %p, counts %p, band_cm %p)", (const void*)pred, (const void*)target,
+             (const void*)counts, (const void*)band_cm);
+  SL_REQUIRE(B >= 1 && H >= 1 && W >= 1, "boundary_counts: B %d, H %d, W %d must all be at least 1", B, H, W);
+  SL_REQUIRE(K >= 1 && K <= 64, "boundary_counts: %d classes outside [1, 64]", K);
+  SL_REQUIRE(d >= 1 && d <= BD_DMAX, "boundary_counts: band width %d outside [1, %d] pixels", d, BD_DMAX);
+  const int tiles_x = cdiv(W, BD_TILE), tiles_y = cdiv(H, BD_TILE);
+  const double blocks = (double)B * (double)tiles_x * (double)tiles_y;
+  SL_REQUIRE(blocks <= 2147483647.0, "boundary_counts: %.0f tiles (B %d x %d x %d) do not fit an int", blocks, B, tiles_y, tiles_x);
+  const int RW = BD_TILE + 2 * d, RP = (RW + 3) & ~3;
+  const size_t lds = (size_t)(3 * K + K * K) * sizeof(unsigned) + (size_t)RW * RP + 2 * (size_t)RW * BD_VP;       // at most 50 944 B
+  return sl_launch("boundary_counts_kernel", boundary_counts_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pred, target, H, W, K, ignore_index, d,
+                   tiles_x, tiles_y, (unsigned long long*)counts, (unsigned long long*)band_cm);
 }
 
 extern "C" int sl_masked_avg_pool(int dtype, const void* feature, const float* mask, int B, int h, int w, int C, int H, int W,

@@ -15,11 +15,14 @@ plain (the default): logits (eval-mode forward, folded BN) -> upsample(align_cor
   The tile is cut into overlapping windows of the crop (the size the model was trained at), forwarded N at a time, then ONE kernel upsamples every window's logits to the
   crop, takes the softmax or not, weights them (uniform, or a tent that favours a window's centre), averages the windows over each pixel and takes the argmax.  Refused:
   sliding together with --tta-*, or with a scoring grid that is not the image grid (eval_ft's long-side square of a non-square tile).
+--boundary-width D (1..32 pixels; 0 = off, the default): contour scores beside mIoU, whichever predictor made `pred`.  ONE more kernel per batch (sl_boundary_counts) counts
+  the Boundary IoU terms and the trimap confusion matrix of the pixels within D of a class border; bcounts_<seed>.npy / band_cmatrix_<seed>.npy and six log lines.
 The two fusing modes put their fused map, cut to the tile, into the .mat and state their geometry in one log line at the first batch.
 """
 import argparse
 import os
 import os.path as osp
+import warnings
 
 import numpy as np
 import torch
@@ -66,8 +69,22 @@ def get_parser():
     p.add_argument('--slide-mode', type=str, default='prob', choices=['prob', 'logit'], help='the windows are fused as softmax probabilities or as upsampled logits (one kernel, '
                    'segland_amd.slide); with --save-prob the .mat holds the fused map')
     p.add_argument('--slide-batch', type=int, default=0, help='sliding-window inference: windows per forward (0 = all windows of a batch at once)')
+    p.add_argument('--boundary-width', type=boundary_width, default=0, metavar='D', help='also score contours: Boundary IoU (Cheng et al.) and trimap mIoU of the pixels within '
+                   'D pixels (1..32, a Chebyshev band) of a class border, one kernel per batch (DESIGN.md section 12c); saved as bcounts_<seed>.npy and '
+                   'band_cmatrix_<seed>.npy; 0 = off')
     p.add_argument('--allow-random-init', action='store_true', help='evaluate random weights when --restore-from does not exist')
     return p
+
+
+def boundary_width(text):
+    """--boundary-width: an integer in 0..32 (0 = off; sl_boundary_counts takes bands of 1..32 pixels)."""
+    try:
+        d = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('--boundary-width %r is not an integer' % (text,))
+    if not 0 <= d <= 32:
+        raise argparse.ArgumentTypeError('--boundary-width %d is outside 0..32 pixels (0 = off; the band kernel holds widths up to 32)' % d)
+    return d
 
 
 def label_grid(label, ignore_label, pad_to_longside=False):
@@ -155,6 +172,18 @@ def miou_from_confusion(cm, n_base):
     return iou, float(np.nanmean(iou[:n_base + 1])), float(np.nanmean(iou[n_base + 1:])) if len(iou) > n_base + 1 else float('nan'), float(np.nanmean(iou))
 
 
+def boundary_iou_from_counts(counts, n_base):
+    """Boundary IoU per class from the [3][K] counts of ops.boundary_counts: intersection / (ground-truth band + prediction band - intersection), NaN for a class with
+    neither band; base / novel / total means over the class ranges of miou_from_confusion."""
+    counts = np.asarray(counts, dtype=np.float64)
+    inter, gt, pr = counts
+    with np.errstate(divide='ignore', invalid='ignore'):
+        iou = inter / (gt + pr - inter)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', RuntimeWarning)                 # nanmean of an all-NaN range is NaN, which is the answer
+        return iou, float(np.nanmean(iou[:n_base + 1])), float(np.nanmean(iou[n_base + 1:])) if len(iou) > n_base + 1 else float('nan'), float(np.nanmean(iou))
+
+
 def predict_plain(model, image, size, map_size=None):
     """The single-view predictor (eval_base.py:166-168): the forward under no_grad, then upsampling + argmax to `size` in one kernel and, when a map is wanted, the logits
     upsampled to `map_size`.  -> (labels uint8 [B,H,W], float [B,K,map_size] or None)."""
@@ -224,6 +253,9 @@ def main(argv=None, ft=False):
                 my_utils.load_model(model, path)
             model.eval()
             cm = torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=engine.device)
+            bd = args.boundary_width                                    # 0 = off: no buffer, no launch, nothing saved or logged below
+            bcounts = torch.zeros((3, args.num_classes), dtype=torch.int64, device=engine.device) if bd else None
+            band_cm = torch.zeros_like(cm) if bd else None
             dump_dir = osp.join(args.save_path, 'prob_%d' % seed) if args.save_prob and args.save_path else None
             for batch in test_loader:
                 # ready tensors (synthetic) or raw uint8 tiles + draws prepared on the GPU (oem / synthetic_raw: Engine installs raw_collate)
@@ -238,11 +270,18 @@ def main(argv=None, ft=False):
                     (logger.info if logger else print)(describe(tuple(image.shape[-2:]), size))
                     describe = None
                 if label is not None:
-                    cm += ops.confusion_matrix(pred, label_p.contiguous(), args.num_classes, args.ignore_label)
+                    label_p = label_p.contiguous()
+                    cm += ops.confusion_matrix(pred, label_p, args.num_classes, args.ignore_label)
+                    if bd:
+                        c, b = ops.boundary_counts(pred, label_p, args.num_classes, args.ignore_label, bd)
+                        bcounts += c
+                        band_cm += b
                 if out_map is not None:
                     dump_maps(out_map, tile, pred, batch[2], dump_dir, data_dir=getattr(args, 'data_dir', None))
             if engine.distributed:
                 cm = engine.all_reduce_tensor(cm, norm=False)
+                if bd:
+                    bcounts, band_cm = engine.all_reduce_tensor(bcounts, norm=False), engine.all_reduce_tensor(band_cm, norm=False)
             cmn = cm.cpu().numpy().astype(np.float64)
             iou, base_miou, novel_miou, total_miou = miou_from_confusion(cmn, args.base_classes)
             results[seed] = (base_miou, novel_miou, total_miou)
@@ -251,6 +290,13 @@ def main(argv=None, ft=False):
                     np.save(osp.join(args.save_path, 'cmatrix_%d.npy' % seed), cmn)
                 msg = ['>>>>>>> Current Seed %d: <<<<<<<' % seed, 'meanIoU---base: mIoU %.4f.' % base_miou,
                        'meanIoU---novel: mIoU %.4f.' % novel_miou, 'meanIoU---total: mIoU %.4f.' % total_miou]
+                if bd:
+                    bcn, bcmn = bcounts.cpu().numpy().astype(np.float64), band_cm.cpu().numpy().astype(np.float64)
+                    if args.save_path:
+                        np.save(osp.join(args.save_path, 'bcounts_%d.npy' % seed), bcn)
+                        np.save(osp.join(args.save_path, 'band_cmatrix_%d.npy' % seed), bcmn)
+                    for name, (_, b, n, t) in (('boundaryIoU', boundary_iou_from_counts(bcn, args.base_classes)), ('trimapIoU', miou_from_confusion(bcmn, args.base_classes))):
+                        msg += ['%s(d=%d)---%s: mIoU %.4f.' % (name, bd, part, v) for part, v in (('base', b), ('novel', n), ('total', t))]
                 for m in msg:
                     (logger.info if logger else print)(m)
         return results

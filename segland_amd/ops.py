@@ -1411,6 +1411,20 @@ def confusion_matrix(pred_u8, target, K, ignore_index):
     return cm
 
 
+def boundary_counts(pred_u8, target, K, ignore_index, d):
+    """(counts [3][K], band_cm [K][K]) int64 of pred uint8 [B,H,W] against target int64 [B,H,W] for a band of d pixels (include/segland_hip.h sl_boundary_counts):
+    counts = boundary-IoU intersection / ground-truth band / prediction band per class, band_cm = the confusion matrix of the pixels within d of a ground-truth border."""
+    if pred_u8.dim() != 3 or pred_u8.shape != target.shape or pred_u8.dtype != torch.uint8 or target.dtype != torch.int64:
+        raise ValueError('boundary_counts: pred uint8 [B,H,W] and target int64 [B,H,W] of one shape expected, got %s %s and %s %s'
+                         % (pred_u8.dtype, tuple(pred_u8.shape), target.dtype, tuple(target.shape)))
+    pp, tp = _p(pred_u8), _p(target)                                  # refuses CPU tensors before anything is allocated
+    B, H, W = target.shape
+    counts = torch.zeros((3, K), dtype=torch.int64, device=target.device)
+    band_cm = torch.zeros((K, K), dtype=torch.int64, device=target.device)
+    check(_lib.lib().sl_boundary_counts(pp, tp, B, H, W, K, ignore_index, d, _p(counts), _p(band_cm), _s()), 'boundary_counts')
+    return counts, band_cm
+
+
 def masked_avg_pool(feature_nhwc, mask):
     B, h, w, Cn = feature_nhwc.shape
     H, W = mask.shape[-2:]
